@@ -1,6 +1,22 @@
 """bench.py -- BASELINE.json's headline metric: Mkeys/s sorting uint32 keys.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--algo radix|merge] [--log2n 28]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it generates the keys, runs W
+untimed and K timed steps, writes the last step's output if --dump-outputs is given and
+prints one JSON line (value, ms_per_step, the dominant kernel's roofline from HIP events
+of the timed region itself).  Everything else described below -- the output checks, the
+merge / config 1 / config 2 / key-value legs, the copy ceiling, host_path, cpu_baseline,
+the weak-scaling field at N > 1 -- runs only with --full, after the timed region, and
+adds its fields to the same line.
+
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64,
+exact for 32-bit keys and indices): keys.npy, with --algo pairs also values.npy, at
+N > 1 keys_rank<r>.npy (rank r's range).  A run writes at most 2^22 elements in all (32 MiB),
+shared evenly by its arrays and, at N > 1, its ranks; an array above its share is sampled at
+fixed, seeded positions (ascending; first and last element included), so two builds run
+with the same arguments can be compared output for output.
 
 N = 1: one "step" is one device-resident sort of n = 2^28 uniform uint32 keys
 (BASELINE config 3: radix, 1 MI355X) through liblabsort's C-ABI
@@ -18,18 +34,18 @@ rank calls labsort_dist_sort on its communicator (labsort_comm_init_rccl, rank 0
 id broadcast over torch.distributed), which sorts its shard locally with the radix
 kernels, moves keys by grouped ncclSend/ncclRecv at the splitters and merges its received
 runs (csrc/dist_plan.h).  value = all ranks' keys / max-over-ranks time.  The same
-schedule with 2^log2n keys per rank (weak scaling) is reported beside it ("weak").
+schedule with 2^log2n keys per rank (weak scaling) is reported beside it ("weak", --full).
 --exchange pairwise runs the Python bitonic merge-split network (dist.py) instead;
 --backend gloo runs the schedule over host collectives (several ranks on one GPU: a
 rehearsal, not a measurement of xGMI).
 
-host_path (after the timed region, rank 0, in a child process): the reference's
+host_path (--full; after the timed region, rank 0, in a child process): the reference's
 own calling convention -- a pageable host int* of 2^30 keys (BASELINE config 5)
 sorted in place, PCIe copies included: labsort_sort_host on one GPU, and at N > 1
 labsort_sort_host_multi over devices 0..N-1 (per-GPU PCIe shards + RCCL exchange).
 Reported beside the headline, never as `value`.
 
-After the timed region the output is verified with size-independent properties
+With --full the output is verified after the timed region with size-independent properties
 (no descents, same sum / sum of squares / digit histograms as the input);
 a failed check aborts the bench.  The printed JSON line carries:
   roofline     the dominant kernel (radix: the onesweep scatter pass) -- achieved
@@ -37,8 +53,8 @@ a failed check aborts the bench.  The printed JSON line carries:
                / average launch duration from HIP events recorded on the sort's
                stream during the timed region; traffic = HBM bytes per launch from
                the committed rocprofv3 PMC pass (profiles/), or null.
-  cpu_baseline std::sort (the oracle: oracle/cpu_sort.cpp) on one host core over a
-               bounded sample of the same workload (rank 0, N = 1 only).
+  cpu_baseline (--full) std::sort (the oracle: oracle/cpu_sort.cpp) on one host core
+               over a bounded sample of the same workload (rank 0, N = 1 only).
 """
 from __future__ import annotations
 
@@ -79,9 +95,18 @@ def parse():
     ap.add_argument("--no-host-path", action="store_true", help="skip the host-pointer (PCIe-inclusive) leg")
     ap.add_argument("--host-log2n", type=int, default=30, help="host-pointer leg: keys = 2^host-log2n")
     ap.add_argument("--host-leg", default="", help=argparse.SUPPRESS)  # child of host_path: "peer" or "rccl"
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/<name>.npy (float64; at most 2^22 elements in "
+                         "all: a fixed seeded sample of an array above its share)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the output checks and every secondary leg (merge, config 1/2, "
+                         "key/value, copy ceiling, host_path, cpu_baseline; N > 1: the weak-scaling field)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="N>1 started without torch.distributed.run: deadline for the N child ranks (s)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def pmc_traffic(kernel_class: str, n: int):
@@ -102,6 +127,30 @@ def pmc_traffic(kernel_class: str, n: int):
                    else "read x2 (guide, 16-B reads), write as measured (uncalibrated)")
             return float(k["hbm_bytes_per_launch"]), os.path.relpath(f, REPO) + ": " + how
     return None, None
+
+
+DUMP_ELEMS = 1 << 22  # --dump-outputs: elements written in all, every rank's files together (float64: 32 MiB)
+
+
+def dump_outputs(torch, dirname, arrays, world=1):
+    """--dump-outputs: `arrays` maps a name to the device tensor (32-bit words) the timed path
+    returned in its last step; each is written as dirname/<name>.npy in float64 (uint32 value
+    of every word: exact).  `world` processes each write len(arrays) arrays into dirname: an
+    array above DUMP_ELEMS / (len(arrays) * world) elements is sampled at positions drawn once
+    from a generator seeded with SEED (sorted; 0 and n - 1 included): the same positions for
+    the same arguments, whichever build runs."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    m = DUMP_ELEMS // (max(len(arrays), 1) * max(world, 1))
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > m:
+            idx = np.random.default_rng(SEED).integers(0, n, size=m - 2, dtype=np.int64)
+            idx = np.concatenate([np.sort(idx), np.array([0, n - 1], dtype=np.int64)])
+            idx.sort()
+            t = t[torch.from_numpy(idx).to(t.device)]
+        v = (t.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
+        np.save(os.path.join(dirname, name + ".npy"), v.cpu().numpy())
 
 
 def verify(torch, ls, src, out, n, key):
@@ -387,12 +436,14 @@ def host_leg(args, timeout_s: int = 100):
     return out
 
 
-def dist_leg(torch, ls, dmod, args, dev, cdev, stream, rank, world, sizes, seed, dcomm=None, comm=None):
+def dist_leg(torch, ls, dmod, args, dev, cdev, stream, rank, world, sizes, seed, dcomm=None, comm=None,
+             dump_dir=None):
     """One N > 1 measurement: rank r sorts its shard of sizes[r] keys (keys first ..
     first + sizes[r] of the generator: the shards are the global array's pieces) as one
     step of the distributed merge sort, W untimed + K timed steps between barriers, the
-    max over ranks of the elapsed time; then the global result is verified (every range
-    sorted, ranges in rank order, the same digit histograms and sum as the input)."""
+    max over ranks of the elapsed time; then (--full) the global result is verified (every
+    range sorted, ranges in rank order, the same digit histograms and sum as the input).
+    dump_dir: every rank writes its range of the last step there (keys_rank<r>.npy)."""
     import torch.distributed as dist
     key = "u32"
     m, first = sizes[rank], sum(sizes[:rank])
@@ -431,35 +482,38 @@ def dist_leg(torch, ls, dmod, args, dev, cdev, stream, rank, world, sizes, seed,
         res = ls.DistComm.view(*res, owner=dcomm)
         dphase, dsent = dcomm.timing()
         dcoll = dcomm.collectives()
-    # global check: every range sorted, boundaries ordered, multiset preserved
-    nres = res.numel()
-    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    ls.count_descents(res, nres, cnt, key=key)
-    edges = ((torch.stack([res[0], res[-1]]).to(torch.int64) & 0xFFFFFFFF)).to(cdev) if nres else \
-        torch.tensor([2**33, -1], dtype=torch.int64, device=cdev)  # empty range: neutral for the order check
-    allg = [torch.empty_like(edges) for _ in range(world)]
-    dist.all_gather(allg, edges)
-    h_in = torch.zeros(1024, dtype=torch.int32, device=dev)
-    h_out = torch.zeros(1024, dtype=torch.int32, device=dev)
-    ls.histogram(src, m, h_in, key=key)
-    ls.histogram(res, nres, h_out, key=key)
-    s_in = (src[:m].to(torch.int64) & 0xFFFFFFFF).sum()
-    s_out = (res.to(torch.int64) & 0xFFFFFFFF).sum()
-    red = torch.stack([s_in, s_out]).to(cdev)
-    h_in, h_out = h_in.to(cdev), h_out.to(cdev)
-    dist.all_reduce(h_in)
-    dist.all_reduce(h_out)
-    dist.all_reduce(red)
-    ok = int(cnt.item()) == 0 and torch.equal(h_in, h_out) and int(red[0]) == int(red[1])
-    lastmax = -1
-    for e in allg:  # ranges in rank order: each range's first key >= every earlier key
-        if int(e[0]) > 2**32:
-            continue
-        ok = ok and int(e[0]) >= lastmax
-        lastmax = int(e[1])
-    okt = torch.tensor([1 if ok else 0], dtype=torch.int32, device=cdev)
-    dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-    ok = bool(okt.item())
+    if dump_dir:
+        dump_outputs(torch, dump_dir, {f"keys_rank{rank}": res}, world=world)
+    ok = True
+    if args.full:  # global check: every range sorted, boundaries ordered, multiset preserved
+        nres = res.numel()
+        cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+        ls.count_descents(res, nres, cnt, key=key)
+        edges = ((torch.stack([res[0], res[-1]]).to(torch.int64) & 0xFFFFFFFF)).to(cdev) if nres else \
+            torch.tensor([2**33, -1], dtype=torch.int64, device=cdev)  # empty range: neutral for the order check
+        allg = [torch.empty_like(edges) for _ in range(world)]
+        dist.all_gather(allg, edges)
+        h_in = torch.zeros(1024, dtype=torch.int32, device=dev)
+        h_out = torch.zeros(1024, dtype=torch.int32, device=dev)
+        ls.histogram(src, m, h_in, key=key)
+        ls.histogram(res, nres, h_out, key=key)
+        s_in = (src[:m].to(torch.int64) & 0xFFFFFFFF).sum()
+        s_out = (res.to(torch.int64) & 0xFFFFFFFF).sum()
+        red = torch.stack([s_in, s_out]).to(cdev)
+        h_in, h_out = h_in.to(cdev), h_out.to(cdev)
+        dist.all_reduce(h_in)
+        dist.all_reduce(h_out)
+        dist.all_reduce(red)
+        ok = int(cnt.item()) == 0 and torch.equal(h_in, h_out) and int(red[0]) == int(red[1])
+        lastmax = -1
+        for e in allg:  # ranges in rank order: each range's first key >= every earlier key
+            if int(e[0]) > 2**32:
+                continue
+            ok = ok and int(e[0]) >= lastmax
+            lastmax = int(e[1])
+        okt = torch.tensor([1 if ok else 0], dtype=torch.int32, device=cdev)
+        dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+        ok = bool(okt.item())
     # exchange statistics: max over ranks (last step); the plan's work and wait
     ph_names = ("local_sort", "plan", "plan_work", "plan_wait", "exchange", "merge")
     if args.exchange == "splitters":
@@ -510,9 +564,10 @@ def dist_main(args, torch, ls, world, rank, dev):
         comm = dmod.P2PComm() if args.backend == "nccl" else dmod.HostStagedComm()
     total = 1 << args.total_log2n
     strong = dist_leg(torch, ls, dmod, args, dev, cdev, stream, rank, world,
-                      [total * (r + 1) // world - total * r // world for r in range(world)], SEED + 5, dcomm, comm)
+                      [total * (r + 1) // world - total * r // world for r in range(world)], SEED + 5, dcomm, comm,
+                      dump_dir=args.dump_outputs)
     weak = None
-    if not args.no_weak:
+    if args.full and not args.no_weak:
         weak = dist_leg(torch, ls, dmod, args, dev, cdev, stream, rank, world, [1 << args.log2n] * world,
                         SEED + 5, dcomm, comm)
     if not (strong["ok"] and (weak is None or weak["ok"])):
@@ -526,7 +581,7 @@ def dist_main(args, torch, ls, world, rank, dev):
             print(f"bench.py: rank {rank}: communicator teardown: {e}", file=sys.stderr)
     dist.destroy_process_group()
     # the host-pointer leg runs once every rank is done with its GPU
-    hostp = host_leg(args) if rank == 0 and not args.no_host_path and args.backend == "nccl" else None
+    hostp = host_leg(args) if rank == 0 and args.full and not args.no_host_path and args.backend == "nccl" else None
     if rank != 0:
         return
     how = ("splitter exchange (labsort_dist_sort: pairwise ncclSend/ncclRecv to all peers at once, merge of "
@@ -544,7 +599,7 @@ def dist_main(args, torch, ls, world, rank, dev):
                    "n_total": strong["keys"], "n_per_gpu": strong["keys"] // world, "algo": "merge",
                    "local_algo": "radix", "key": "u32", "dist": args.dist,
                    "parallelism": f"{world} ranks, {'RCCL' if args.backend == 'nccl' else 'gloo'} {args.exchange} exchange"},
-        "verified": "sorted permutation (descents, digit histograms, sums), ranges in rank order",
+        "verified": "sorted permutation (descents, digit histograms, sums), ranges in rank order" if args.full else None,
         "xgmi": strong["xgmi"], "roofline": None, "cpu_baseline": None,
     }
     if weak:
@@ -714,9 +769,15 @@ def main():
     ls.timing_enable(False)
     elapsed = t1 - t0
     status()
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, {"keys": res, "values": vout} if args.algo == "pairs" else {"keys": res})
 
-    ok, desc = verify(torch, ls, src, res, n, key)
-    if ok and args.algo == "pairs":
+    # everything below the timed region and the dump is --full's: checks and secondary legs
+    extras = args.full and args.algo == "radix" and not args.no_merge
+    ok = True
+    if args.full:
+        ok, desc = verify(torch, ls, src, res, n, key)
+    if args.full and ok and args.algo == "pairs":
         # each payload is its key's input index: the gather reproduces the output keys,
         # and equal keys keep ascending indices (stable)
         idx = vout.to(torch.int64)
@@ -732,7 +793,7 @@ def main():
     # config 4 beside the headline: the merge sort of the same device input (N = 1,
     # radix headline only); its own verification, status check and kernel timings
     merge_leg = None
-    if args.algo == "radix" and not args.no_merge:
+    if extras:
         mws = torch.empty(max(ls.workspace_bytes(n, "merge"), 256), dtype=torch.uint8, device=dev)
         mout = torch.empty_like(src)
 
@@ -794,7 +855,7 @@ def main():
     # BASELINE config 2 beside the headline: 2^20 keys, radix (the gathered passes at this
     # size), device-resident, verified; launch-bound, so reported as time per sort
     config2 = None
-    if args.algo == "radix" and not args.no_merge and n > (1 << 20):
+    if extras and n > (1 << 20):
         n2 = 1 << 20
         s2 = torch.empty(n2, dtype=torch.int32, device=dev)
         o2 = torch.empty_like(s2)
@@ -823,7 +884,7 @@ def main():
     # SURVEY 8f row 4 beside the headline: the stable key/value radix sort of the same keys
     # with 4-byte payloads (each its input index), verified as the pairs run is
     pairs_leg = None
-    if args.algo == "radix" and not args.no_merge:
+    if extras:
         vin = torch.arange(n, dtype=torch.int32, device=dev)
         pko = torch.empty_like(src)
         pvo = torch.empty_like(src)
@@ -878,7 +939,7 @@ def main():
         del vin, pko, pvo
 
     config1 = None
-    if args.algo == "radix" and not args.no_merge:
+    if extras:
         config1 = config1_gpu(ls, torch, dev, stream)
         if config1["verified"] != "fixture":
             print("bench.py: CONFIG 1 OUTPUT CHECK FAILED", file=sys.stderr)
@@ -887,25 +948,27 @@ def main():
     value = n * args.steps / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
     # the host-pointer leg (PCIe-inclusive, child processes)
-    hostp = host_leg(args) if not args.no_host_path else None
+    hostp = host_leg(args) if args.full and not args.no_host_path else None
 
     # the copy ceiling: the library's streaming copy (labsort_copy: 16-B nontemporal loads
     # and stores in 16384-word tiles, one workgroup per CU) of the same n keys, each of 5
     # launches timed by HIP events on the stream it runs on; the median launch
-    cp = torch.empty_like(src)
-    for _ in range(2):
-        ls.copy(src, cp, n, stream=stream)
-    times = []
-    for _ in range(5):
-        ls.timing_enable(True)
-        ls.copy(src, cp, n, stream=stream)
-        torch.cuda.synchronize()
-        times.append(ls.timing_read("copy")[0])
-        ls.timing_enable(False)
-    copy_ms = sorted(times)[len(times) // 2]
-    copy_gbs = 8.0 * n / (copy_ms * 1e-3) / 1e9
-    copy_ok = torch.equal(cp, src)
-    del cp
+    copy_gbs = None
+    if args.full:
+        cp = torch.empty_like(src)
+        for _ in range(2):
+            ls.copy(src, cp, n, stream=stream)
+        times = []
+        for _ in range(5):
+            ls.timing_enable(True)
+            ls.copy(src, cp, n, stream=stream)
+            torch.cuda.synchronize()
+            times.append(ls.timing_read("copy")[0])
+            ls.timing_enable(False)
+        copy_ms = sorted(times)[len(times) // 2]
+        copy_gbs = 8.0 * n / (copy_ms * 1e-3) / 1e9
+        copy_ok = torch.equal(cp, src)
+        del cp
 
     avg_ms = k_ms / k_cnt if k_cnt else None
     per_launch_bytes = 16.0 * n if args.algo == "pairs" else 8.0 * n  # key (+ payload) read + written
@@ -919,13 +982,14 @@ def main():
                                                else f"k_{dom}"), "launches": k_cnt,
                 "avg_launch_ms": round(avg_ms, 5) if avg_ms else None,
                 "algorithmic_bytes_per_launch": per_launch_bytes, "traffic_source": tsrc}
-    roofline["copy_ceiling"] = {
-        "value": round(copy_gbs, 1), "unit": "GB/s", "frac": round(achieved / copy_gbs, 4) if achieved else None,
-        "ms": round(copy_ms, 5), "verified": bool(copy_ok),
-        "probe": "labsort_copy of the same n keys (16-B nontemporal loads and stores, 16384-word tiles, one "
-                 "1024-thread workgroup per CU), median of 5 event-timed launches, after the timed region"}
+    if args.full:
+        roofline["copy_ceiling"] = {
+            "value": round(copy_gbs, 1), "unit": "GB/s", "frac": round(achieved / copy_gbs, 4) if achieved else None,
+            "ms": round(copy_ms, 5), "verified": bool(copy_ok),
+            "probe": "labsort_copy of the same n keys (16-B nontemporal loads and stores, 16384-word tiles, one "
+                     "1024-thread workgroup per CU), median of 5 event-timed launches, after the timed region"}
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds, n, ls)
         cpu["config1"] = config1_cpu(ls)
     wl = {"radix": "LSD radix sort (8-bit digits, onesweep)", "merge": "LDS tile sort + merge-path passes",
@@ -942,7 +1006,7 @@ def main():
         "config": {"workload": f"{wl}, n=2^{args.log2n} uint32 {args.dist}, device-resident (BASELINE config 3)",
                    "n_per_gpu": n, "algo": args.algo, "key": key, "dist": args.dist, "parallelism": "single GPU"},
         "verified": "sorted permutation (descents, digit histograms, sums)" + (
-            "; payloads gather the output keys, stable" if args.algo == "pairs" else ""),
+            "; payloads gather the output keys, stable" if args.algo == "pairs" else "") if args.full else None,
         "roofline": roofline, "cpu_baseline": cpu,
     }
     for leg in (merge_leg and merge_leg["roofline"], merge_leg and merge_leg["tile_sort"],

@@ -9,7 +9,7 @@ set -o pipefail
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}"
 O="$R/gpurun_out"; mkdir -p "$O"; cd /tmp && export TMPDIR=/tmp
 TAG="$1"
-B="$R/bench.py --no-cpu-baseline --no-host-path --no-merge"
+B="$R/bench.py --full --no-cpu-baseline --no-host-path --no-merge"
 for leg in "" "_merge"; do
   A=""; [ "$leg" = "_merge" ] && A="--algo merge"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$TAG$leg" -o run -- python3 $B $A --steps 10 --warmup 2 > "$O/prof_$TAG$leg.log" 2>&1 || { echo "stats pass $leg failed"; tail -20 "$O/prof_$TAG$leg.log"; exit 1; }

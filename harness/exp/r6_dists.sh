@@ -5,7 +5,7 @@ set -e
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}"
 O="$R/gpurun_out"; mkdir -p "$O"; cd "$R"
 for d in ${DISTS:-u32 u31 mod1000 mod100 sorted reversed lowbits const}; do
-  timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --no-host-path --dist $d > "$O/dist_$d.json" 2> "$O/dist_$d.err"
+  timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --no-host-path --dist $d > "$O/dist_$d.json" 2> "$O/dist_$d.err"
   python3 - "$O/dist_$d.json" "$d" <<'PY'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -9,6 +9,6 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeou
 tail -2 "$O/${TAG}_pytest_gpu.log"
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/${TAG}_smoke.log" 2>&1
 tail -1 "$O/${TAG}_smoke.log"
-timeout -k 10 600 python3 -u bench.py > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
+timeout -k 10 600 python3 -u bench.py --full > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
 tail -c 400 "$O/${TAG}_bench.json"; echo
 timeout -k 10 900 bash "$R/harness/exp/profile_round.sh" "$TAG"

@@ -10,7 +10,7 @@ if [ -z "${NO_TESTS:-}" ]; then
   timeout -k 10 1500 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > "$O/${TAG}_pytest_gpu.log" 2>&1
   tail -2 "$O/${TAG}_pytest_gpu.log"
 fi
-timeout -k 10 600 python3 -u bench.py --gpus 8 --backend gloo --steps 2 --warmup 1 --no-host-path > "$O/${TAG}_bench_gloo8.json" 2> "$O/${TAG}_bench_gloo8.err"
+timeout -k 10 600 python3 -u bench.py --full --gpus 8 --backend gloo --steps 2 --warmup 1 --no-host-path > "$O/${TAG}_bench_gloo8.json" 2> "$O/${TAG}_bench_gloo8.err"
 tail -c 600 "$O/${TAG}_bench_gloo8.json"; echo
-timeout -k 10 600 python3 -u bench.py > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
+timeout -k 10 600 python3 -u bench.py --full > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err"
 tail -c 1500 "$O/${TAG}_bench.json"; echo

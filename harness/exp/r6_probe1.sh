@@ -8,7 +8,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}"
 O="$R/gpurun_out"; mkdir -p "$O"; cd "$R"
 timeout -k 10 120 "$R/harness/bin/write_probe" > "$O/r6_write_probe.txt" 2>&1
 for lg in 22 23 24 25 26 27 28; do
-  LABSORT_RADIX_IMPL=onesweep timeout -k 10 150 python3 bench.py --log2n $lg --steps 20 --warmup 3 --no-merge \
+  LABSORT_RADIX_IMPL=onesweep timeout -k 10 150 python3 bench.py --full --log2n $lg --steps 20 --warmup 3 --no-merge \
     --no-cpu-baseline --no-host-path > "$O/r6_ic_$lg.json" 2> "$O/r6_ic_$lg.err"
   echo "2^$lg done"
 done

@@ -151,7 +151,7 @@ def test_python_wrapper_raises(ls):
 # ---- the reference's harness drivers, compiled unchanged ---------------------------------
 @pytest.mark.parametrize("prog", ["sort", "performaceTest"])
 def test_harness_links_liblabsort(prog):
-    exe = os.path.join(REPO, "harness", "bin", prog)
+    exe = os.path.join(REPO, "oracle", "_ref", prog)
     if not os.path.exists(exe):
         pytest.skip("harness binaries not built (reference sources absent)")
     und = subprocess.run(["nm", "-u", exe], check=True, capture_output=True, text=True).stdout

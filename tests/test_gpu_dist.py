@@ -349,26 +349,30 @@ def test_bench_dist_gloo_config5():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
                         os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1",
-                        "--warmup", "0", "--no-weak", "--no-host-path"],
+                        "--warmup", "0", "--full", "--no-weak", "--no-host-path"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert "BASELINE config 5" in line["config"]["workload"]
     assert line["config"]["n_total"] == 1 << 30 and line["config"]["n_per_gpu"] == 1 << 29
+    assert line["verified"].startswith("sorted permutation")  # --full: the global check ran
     ph = line["xgmi"]["phases_ms_last_step"]
     assert ph["plan_work"] >= 0 and ph["plan_wait"] >= 0
     assert set(line["xgmi"]["collectives_ms_last_step"]) >= {"samples", "counts"}
 
 
-def test_bench_plain_gpus2_launches_ranks():
+def test_bench_plain_gpus2_launches_ranks(tmp_path):
     """`python3 bench.py --gpus 2` WITHOUT torch.distributed.run (how the driver invokes the
-    bench): bench.py starts the two ranks itself and relays rank 0's config-5 line"""
+    bench): bench.py starts the two ranks itself and relays rank 0's config-5 line; with
+    --dump-outputs every rank writes (a sample of) its range of the sorted array, the two
+    files together within the dump's budget"""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--steps", "1", "--warmup", "0", "--no-weak", "--no-host-path", "--total-log2n", "26"],
+                        "--steps", "1", "--warmup", "0", "--full", "--no-weak", "--no-host-path", "--total-log2n", "26",
+                        "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -377,6 +381,13 @@ def test_bench_plain_gpus2_launches_ranks():
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert "BASELINE config 5" in line["config"]["workload"]
     assert line["config"]["n_total"] == 1 << 26 and line["value"] > 0
+    assert line["verified"].startswith("sorted permutation")  # --full: the global check (permutation of the input) ran
+    assert sorted(os.listdir(tmp_path)) == ["keys_rank0.npy", "keys_rank1.npy"]
+    r0, r1 = (np.load(tmp_path / f"keys_rank{r}.npy") for r in (0, 1))
+    assert r0.dtype == r1.dtype == np.float64 and r0.size == r1.size == (1 << 22) // 2  # the budget is shared by the ranks
+    assert r0.nbytes + r1.nbytes <= 64 * 10**6
+    assert r0[-1] <= r1[0]
+    assert bool((np.diff(r0) >= 0).all()) and bool((np.diff(r1) >= 0).all())
 
 
 def test_bench_plain_gpus8_nccl_refused_on_one_gpu():

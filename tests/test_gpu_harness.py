@@ -1,5 +1,5 @@
 """The reference's own drivers, compiled unchanged against the drop-in headers
-(harness/build.sh), run against liblabsort.so.
+(oracle/build_ref.sh), run against liblabsort.so.
 
   main.cpp            warm-up + measured sweep 256..65536 through order_array and
                       order_with_trust, CSV in ./output.txt (main.cpp:17-51)
@@ -16,7 +16,7 @@ import subprocess
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "harness", "bin")
+BIN = os.path.join(REPO, "oracle", "_ref")
 SIZES = [256 << i for i in range(9)]  # main.cpp:24,35 / performanceTest.cpp:25,47: 256 .. 65536
 
 

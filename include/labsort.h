@@ -82,7 +82,8 @@ extern "C" {
 #define LABSORT_K_GCOPY 6        /* its final gathered copy */
 #define LABSORT_K_COPY 7         /* the streaming copy (labsort_copy: the bench's copy ceiling) */
 #define LABSORT_K_MERGE4 8       /* four-way merge pass of the merge sort (k_m4_rank + k_m4_merge) */
-#define LABSORT_K_COUNT 9
+#define LABSORT_K_SEGSORT 9      /* segmented sort: classification, the LDS class kernels, the general path's glue */
+#define LABSORT_K_COUNT 10
 
 /* ---- library info ---- */
 const char *labsort_version(void);
@@ -242,6 +243,46 @@ size_t labsort_pairs_workspace_bytes(size_t n, int algo);
 int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void *d_keys_out, void *d_vals_out,
                               size_t n, int key_type, int algo, void *d_workspace, size_t workspace_bytes,
                               void *stream);
+
+/* ---- segmented sort: many independent segments of one buffer in one call (batched row
+ * sorts, per-row argsort, per-bucket ordering; no lab.cu counterpart, the reference sorts
+ * one array) ----
+ * Segment i is [d_offsets[i], d_offsets[i+1]); d_offsets holds nseg + 1 words in device
+ * memory with d_offsets[0] == 0, d_offsets[nseg] == n and no decrease (empty segments are
+ * allowed).  Each segment is sorted on its own in key_type order; the pairs form is stable
+ * and carries a 4-byte payload.  Out of place or fully in place (the aliasing rules of
+ * labsort_sort_pairs_device).  Asynchronous on `stream`, no allocation, nothing read back:
+ * the launch sequence depends on the host arguments only, so a captured call may be
+ * replayed on new keys and new offsets in the same buffers.
+ * max_segment_keys is the caller's promise about the longest segment (a row sort: the row
+ * length).  0 < max_segment_keys <= labsort_segment_tile_keys() (pairs: .._pair_tile_keys())
+ * takes the LDS path: every segment is read once, sorted in LDS by the kernel of its length
+ * class (one wave / one 256-thread workgroup / one 1024-thread workgroup per segment) and
+ * written once.  Anything else (0 = unknown) takes the general path, two stable pair sorts
+ * (by key, then by segment id) of the whole array; n <= labsort_max_keys(LABSORT_ALGO_RADIX).
+ * n <= 2^31 - 1 and nseg <= 2^31 - 1 on both paths; n == 0 launches nothing and leaves the
+ * workspace as it was.
+ * The first kernel validates the offsets (ends, order, every length <= max_segment_keys when
+ * that is not 0) and sets the workspace's first word on failure; every later kernel of the
+ * call then returns without touching the key and payload buffers.
+ * labsort_segments_workspace_status synchronises `stream` and returns LABSORT_ERR_ARG for
+ * rejected offsets, LABSORT_ERR_DEVICE if an inner pair sort of the general path reported
+ * an error, else LABSORT_OK. */
+/* longest segment the one-pass LDS path sorts (keys only / key+payload) */
+size_t labsort_segment_tile_keys(void);
+size_t labsort_segment_pair_tile_keys(void);
+/* info for tests: the upper length bound of each LDS class, ascending; the last
+ * equals the tile size above.  Returns the number of classes. */
+int labsort_segment_class_edges(int pairs, size_t *edges, int cap);
+size_t labsort_segments_workspace_bytes(size_t n, size_t nseg, size_t max_segment_keys, int pairs);
+int labsort_sort_segments_device(const void *d_keys_in, void *d_keys_out, size_t n, const uint32_t *d_offsets,
+                                 size_t nseg, size_t max_segment_keys, int key_type, void *d_workspace,
+                                 size_t workspace_bytes, void *stream);
+int labsort_sort_segments_pairs_device(const void *d_keys_in, const void *d_vals_in, void *d_keys_out,
+                                       void *d_vals_out, size_t n, const uint32_t *d_offsets, size_t nseg,
+                                       size_t max_segment_keys, int key_type, void *d_workspace,
+                                       size_t workspace_bytes, void *stream);
+int labsort_segments_workspace_status(const void *d_workspace, void *stream);
 
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +

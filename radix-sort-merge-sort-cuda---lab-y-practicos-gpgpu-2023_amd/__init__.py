@@ -31,7 +31,7 @@ ALGO = {"radix": 0, "merge": 1, "radix1": 2, "auto": 3}
 KEY = {"u32": 0, "i32": 1}
 DIST = {"u32": 0, "u31": 1, "mod100": 2, "mod1000": 3, "sorted": 4, "reversed": 5, "const": 6, "lowbits": 7}
 KCLASS = {"histogram": 0, "onesweep": 1, "tile_sort": 2, "merge": 3, "partition": 4, "gsweep": 5, "gcopy": 6,
-          "copy": 7, "merge4": 8}
+          "copy": 7, "merge4": 8, "segsort": 9}
 
 # exported symbols of include/labsort.h + lab.h (checked by tests/test_abi.py)
 C_SYMBOLS = [
@@ -49,6 +49,9 @@ C_SYMBOLS = [
     "labsort_dist_sort", "labsort_dist_timing", "labsort_dist_last_hip_error",
     "labsort_multi_collectives", "labsort_dist_collectives", "labsort_copy",
     "labsort_comm_set_timeout", "labsort_test_fault",
+    "labsort_segment_tile_keys", "labsort_segment_pair_tile_keys", "labsort_segment_class_edges",
+    "labsort_segments_workspace_bytes", "labsort_sort_segments_device", "labsort_sort_segments_pairs_device",
+    "labsort_segments_workspace_status",
 ]
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
 MULTI_PHASES = ["h2d", "local_sort", "plan", "exchange", "merge", "d2h", "total", "plan_work", "plan_wait"]
@@ -166,6 +169,16 @@ def _load() -> ctypes.CDLL:
     L.labsort_dist_collectives.argtypes = [p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), i]
     L.labsort_copy.argtypes = [p, p, sz, p]
     L.labsort_pairs_workspace_status.argtypes = [p, sz, i, p]
+    L.labsort_segment_tile_keys.restype = sz
+    L.labsort_segment_tile_keys.argtypes = []
+    L.labsort_segment_pair_tile_keys.restype = sz
+    L.labsort_segment_pair_tile_keys.argtypes = []
+    L.labsort_segment_class_edges.argtypes = [i, ctypes.POINTER(sz), i]
+    L.labsort_segments_workspace_bytes.restype = sz
+    L.labsort_segments_workspace_bytes.argtypes = [sz, sz, sz, i]
+    L.labsort_sort_segments_device.argtypes = [p, p, sz, p, sz, sz, i, p, sz, p]
+    L.labsort_sort_segments_pairs_device.argtypes = [p, p, p, p, sz, p, sz, sz, i, p, sz, p]
+    L.labsort_segments_workspace_status.argtypes = [p, p]
     L.labsort_histogram.argtypes = [p, sz, i, i, p, p]
     L.labsort_fill.argtypes = [p, sz, u64, i, u64, u64, p]
     L.labsort_count_descents.argtypes = [p, sz, i, p, p]
@@ -548,6 +561,76 @@ def sort_pairs_device(d_keys_in, d_vals_in, d_keys_out, d_vals_out, n: int, key:
            "sort_pairs_device")
     if own:
         pairs_workspace_status(workspace, n, algo, stream)
+
+
+# ---- segmented sort: segment i = [offsets[i], offsets[i+1]) of one buffer ---------------
+def segment_tile_keys() -> int:
+    """Longest segment the one-pass LDS path sorts (keys only)."""
+    return int(lib.labsort_segment_tile_keys())
+
+
+def segment_pair_tile_keys() -> int:
+    """Longest segment the one-pass LDS path sorts (key + payload)."""
+    return int(lib.labsort_segment_pair_tile_keys())
+
+
+def segment_class_edges(pairs: bool = False) -> list:
+    """Upper length bound of each LDS class, ascending; the last is the tile size."""
+    e = (ctypes.c_size_t * 8)()
+    k = lib.labsort_segment_class_edges(1 if pairs else 0, e, 8)
+    return [int(e[j]) for j in range(k)]
+
+
+def segments_workspace_bytes(n: int, nseg: int, max_segment_keys: int = 0, pairs: bool = False) -> int:
+    return int(lib.labsort_segments_workspace_bytes(n, nseg, max_segment_keys, 1 if pairs else 0))
+
+
+def row_offsets(rows: int, cols: int, device="cuda"):
+    """uint32 offsets (as an int32 tensor of rows + 1 words) of a row-major rows x cols matrix."""
+    import torch
+    assert rows * cols < 2**31
+    return (torch.arange(rows + 1, dtype=torch.int64, device=device) * cols).to(torch.int32)
+
+
+def sort_segments_device(d_in, d_out, n: int, d_offsets, nseg: int, max_segment_keys: int = 0, key: str = "u32",
+                         workspace=None, stream=None) -> None:
+    """Sort each segment [offsets[i], offsets[i+1]) of d_in into d_out (may alias) on `stream`.
+    max_segment_keys: the longest segment (<= segment_tile_keys(): one LDS pass; 0 or longer:
+    the general path).  With a caller-owned `workspace` the call stays asynchronous (check
+    segments_workspace_status when the result is needed); without one it allocates, synchronises
+    and checks."""
+    own = workspace is None
+    if own:
+        import torch
+        workspace = torch.empty(max(segments_workspace_bytes(n, nseg, max_segment_keys), 1), dtype=torch.uint8,
+                                device="cuda")
+    wsb = workspace.numel() * workspace.element_size()
+    _check(lib.labsort_sort_segments_device(_ptr(d_in), _ptr(d_out), n, _ptr(d_offsets), nseg, max_segment_keys,
+                                            KEY[key], _ptr(workspace), wsb, _stream(stream)), "sort_segments_device")
+    if own:
+        segments_workspace_status(workspace, stream)
+
+
+def sort_segments_pairs_device(d_keys_in, d_vals_in, d_keys_out, d_vals_out, n: int, d_offsets, nseg: int,
+                               max_segment_keys: int = 0, key: str = "u32", workspace=None, stream=None) -> None:
+    """As sort_segments_device for (key, 4-byte payload) pairs; stable within each segment."""
+    own = workspace is None
+    if own:
+        import torch
+        workspace = torch.empty(max(segments_workspace_bytes(n, nseg, max_segment_keys, True), 1), dtype=torch.uint8,
+                                device="cuda")
+    wsb = workspace.numel() * workspace.element_size()
+    _check(lib.labsort_sort_segments_pairs_device(_ptr(d_keys_in), _ptr(d_vals_in), _ptr(d_keys_out), _ptr(d_vals_out),
+                                                  n, _ptr(d_offsets), nseg, max_segment_keys, KEY[key], _ptr(workspace),
+                                                  wsb, _stream(stream)), "sort_segments_pairs_device")
+    if own:
+        segments_workspace_status(workspace, stream)
+
+
+def segments_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_ARG if the last segmented sort on
+    `workspace` rejected its offsets, ERR_DEVICE if an inner sort reported a failure."""
+    _check(lib.labsort_segments_workspace_status(_ptr(workspace), _stream(stream)), "sort_segments (status)")
 
 
 def histogram(d_keys, n: int, d_hist, bits: int = 8, key: str = "u32", stream=None) -> None:

@@ -19,6 +19,7 @@
 
 #include "../../include/labsort.h"
 #include "common.h"
+#include "segsort.h"
 
 using namespace labsort;
 
@@ -896,6 +897,168 @@ int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void
         cv = nv;
     }
     return LABSORT_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// segmented sort (segsort.hip): segment i = [d_offsets[i], d_offsets[i+1])
+// ---------------------------------------------------------------------------------
+size_t labsort_segment_tile_keys(void) { return (size_t)SEG_TILE_KEYS; }
+size_t labsort_segment_pair_tile_keys(void) { return (size_t)SEG_TILE_PAIRS; }
+
+int labsort_segment_class_edges(int pairs, size_t *edges, int cap) {
+    const size_t e[SEG_CLASSES] = {(size_t)SEG_WAVE_KEYS, (size_t)SEG_WAVE2_KEYS, (size_t)SEG_WAVE3_KEYS, (size_t)SEG_BLOCK_KEYS,
+                                   pairs ? (size_t)SEG_TILE_PAIRS : (size_t)SEG_TILE_KEYS};
+    for (int i = 0; i < SEG_CLASSES && i < cap && edges; ++i) edges[i] = e[i];
+    return SEG_CLASSES;
+}
+
+namespace {
+bool seg_lds_path(size_t max_len, int pairs) {
+    return max_len > 0 && max_len <= (pairs ? (size_t)SEG_TILE_PAIRS : (size_t)SEG_TILE_KEYS);
+}
+// LDS path: header | one list of nseg words per class.
+// General path: header | three n-word buffers | the inner pair sorts' workspace.
+struct SegLayout {
+    size_t off_lists, list_stride;    // LDS path (stride in words)
+    size_t off_a, off_b, off_c, off_inner, inner_bytes;  // general path
+    size_t total;
+};
+// the inner pair sort runs LABSORT_ALGO_AUTO; sized so the function never shrinks as n grows
+// across AUTO's merge -> radix switch
+size_t seg_inner_bytes(size_t n) {
+    const size_t m = n < (size_t)LABSORT_AUTO_PAIRS_MERGE_MAX_KEYS ? n : (size_t)LABSORT_AUTO_PAIRS_MERGE_MAX_KEYS;
+    return std::max(labsort_pairs_workspace_bytes(n, LABSORT_ALGO_AUTO), labsort_pairs_workspace_bytes(m, LABSORT_ALGO_MERGE));
+}
+SegLayout seg_layout(size_t n, size_t nseg, bool lds) {
+    SegLayout L{};
+    size_t o = SEG_HDR_BYTES;
+    if (lds) {
+        L.list_stride = align_up(nseg * 4, 256) / 4;
+        L.off_lists = o;
+        o += (size_t)SEG_CLASSES * L.list_stride * 4;
+    } else {
+        L.off_a = o;
+        o = align_up(o + n * 4, 256);
+        L.off_b = o;
+        o = align_up(o + n * 4, 256);
+        L.off_c = o;
+        o = align_up(o + n * 4, 256);
+        L.off_inner = o;
+        L.inner_bytes = seg_inner_bytes(n);
+        o += L.inner_bytes;
+    }
+    L.total = o;
+    return L;
+}
+
+int sort_segments(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, size_t n, const uint32_t *off,
+                  size_t nseg, size_t max_len, int key_type, void *d_ws, size_t ws_bytes, void *stream) {
+    const bool pairs = vi != nullptr || vo != nullptr;
+    if (n == 0) return LABSORT_OK;
+    if (!ki || !ko || !off || (pairs && (!vi || !vo))) return LABSORT_ERR_ARG;
+    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
+    if (nseg == 0 || n > (size_t)0x7FFFFFFFu || nseg > (size_t)0x7FFFFFFFu) return LABSORT_ERR_ARG;
+    if (pairs) {  // the aliasing rules of labsort_sort_pairs_device
+        if ((ki == ko) != (vi == vo)) return LABSORT_ERR_ARG;
+        if (ko == vo) return LABSORT_ERR_ARG;
+    }
+    const bool lds = seg_lds_path(max_len, pairs ? 1 : 0);
+    if (!lds && n > RADIX_MAX_N) return LABSORT_ERR_ARG;
+    if (!d_ws || ws_bytes < labsort_segments_workspace_bytes(n, nseg, max_len, pairs ? 1 : 0)) return LABSORT_ERR_ARG;
+    const SegLayout L = seg_layout(n, nseg, lds);
+    const uint32_t flip = flip_of(key_type);
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(ws);
+    const bool inplace = ki == ko;
+    HIP_TRY(launch_zero(hdr, SEG_HDR_BYTES, s));  // (a kernel: graph-replayable)
+    if (lds) {
+        uint32_t *lists = reinterpret_cast<uint32_t *>(ws + L.off_lists);
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        HIP_TRY(launch_seg_bin(off, nseg, n, max_len, pairs, !inplace, hdr, lists, L.list_stride, s));
+        // the classes max_len admits (host arguments only: the launch sequence is fixed)
+        size_t edges[SEG_CLASSES];
+        labsort_segment_class_edges(pairs ? 1 : 0, edges, SEG_CLASSES);
+        int ncls = 1;
+        while (ncls < SEG_CLASSES && max_len > edges[ncls - 1]) ++ncls;
+        for (int c = 0; c < ncls; ++c)
+            HIP_TRY(launch_seg_sort(c, ki, ko, vi, vo, off, hdr, lists + (size_t)c * L.list_stride, flip, s));
+        return LABSORT_OK;
+    }
+    // general path: two stable pair sorts (by key, then by segment id) on workspace buffers;
+    // the caller's output is written by the last, guarded, kernel only
+    uint32_t *A = reinterpret_cast<uint32_t *>(ws + L.off_a), *B = reinterpret_cast<uint32_t *>(ws + L.off_b),
+             *C = reinterpret_cast<uint32_t *>(ws + L.off_c);
+    char *iws = ws + L.off_inner;
+    uint32_t *ierr = reinterpret_cast<uint32_t *>(iws);
+    HIP_TRY(launch_zero(ierr, 16, s));  // (a one-tile inner sort has no error word of its own)
+    {
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        HIP_TRY(launch_seg_bin(off, nseg, n, max_len, pairs, false, hdr, nullptr, 0, s));
+        if (pairs) HIP_TRY(launch_seg_ids(off, nseg, n, nullptr, nullptr, A, hdr, s));  // A = 0, 1, 2, ...
+        else HIP_TRY(launch_seg_ids(off, nseg, n, nullptr, A, nullptr, hdr, s));        // A = segment of each position
+    }
+    int st;
+    // (key, A) by key -> (B, C)
+    if ((st = labsort_sort_pairs_device(ki, A, B, C, n, key_type, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream))) return st;
+    HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
+    if (pairs) {
+        // C = positions in key order; B = their segments; (B, C) by segment in place: C = the permutation
+        {
+            TimingScope ts(LABSORT_K_SEGSORT, s);
+            HIP_TRY(launch_seg_ids(off, nseg, n, C, B, nullptr, hdr, s));
+        }
+        if ((st = labsort_sort_pairs_device(B, C, B, C, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
+            return st;
+        HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        if (inplace) {  // through temporaries: the gather reads what it would overwrite
+            HIP_TRY(launch_seg_gather(ki, vi, C, A, B, n, hdr, s));
+            HIP_TRY(launch_seg_gather(A, B, nullptr, ko, vo, n, hdr, s));
+        } else {
+            HIP_TRY(launch_seg_gather(ki, vi, C, ko, vo, n, hdr, s));
+        }
+    } else {
+        // (C = segment ids, B = keys) by segment id in place: B = the result
+        if ((st = labsort_sort_pairs_device(C, B, C, B, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
+            return st;
+        HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        HIP_TRY(launch_seg_gather(B, nullptr, nullptr, ko, nullptr, n, hdr, s));
+    }
+    return LABSORT_OK;
+}
+}  // namespace
+
+size_t labsort_segments_workspace_bytes(size_t n, size_t nseg, size_t max_segment_keys, int pairs) {
+    return seg_layout(n, nseg, seg_lds_path(max_segment_keys, pairs)).total;
+}
+
+int labsort_sort_segments_device(const void *d_keys_in, void *d_keys_out, size_t n, const uint32_t *d_offsets,
+                                 size_t nseg, size_t max_segment_keys, int key_type, void *d_ws, size_t ws_bytes,
+                                 void *stream) {
+    return sort_segments(static_cast<const uint32_t *>(d_keys_in), nullptr, static_cast<uint32_t *>(d_keys_out), nullptr,
+                         n, d_offsets, nseg, max_segment_keys, key_type, d_ws, ws_bytes, stream);
+}
+
+int labsort_sort_segments_pairs_device(const void *d_keys_in, const void *d_vals_in, void *d_keys_out, void *d_vals_out,
+                                       size_t n, const uint32_t *d_offsets, size_t nseg, size_t max_segment_keys,
+                                       int key_type, void *d_ws, size_t ws_bytes, void *stream) {
+    if (n == 0) return LABSORT_OK;
+    if (!d_vals_in || !d_vals_out) return LABSORT_ERR_ARG;
+    return sort_segments(static_cast<const uint32_t *>(d_keys_in), static_cast<const uint32_t *>(d_vals_in),
+                         static_cast<uint32_t *>(d_keys_out), static_cast<uint32_t *>(d_vals_out), n, d_offsets, nseg,
+                         max_segment_keys, key_type, d_ws, ws_bytes, stream);
+}
+
+int labsort_segments_workspace_status(const void *d_ws, void *stream) {
+    hipStream_t s = as_stream(stream);
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!d_ws) return LABSORT_ERR_ARG;
+    uint32_t w[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(w, d_ws, sizeof w, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return w[0] ? LABSORT_ERR_ARG : w[SEG_HDR_DEVERR] ? LABSORT_ERR_DEVICE : LABSORT_OK;
 }
 
 int labsort_histogram(const void *d_keys, size_t n, int key_type, int bits, uint32_t *d_hist, void *stream) {

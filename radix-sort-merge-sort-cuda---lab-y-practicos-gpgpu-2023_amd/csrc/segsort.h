@@ -1,0 +1,69 @@
+// segsort.h -- segmented sort (segsort.hip): shapes, workspace header and host launchers.
+#pragma once
+#include "common.h"
+
+namespace labsort {
+
+// ---- LDS classes: a segment is read once, sorted in LDS, written once ----
+// wave classes: one wave64 per segment, no workgroup barrier; 4, 8 and 16 keys per lane for
+// segments up to 256, 512 and 1024 keys.  Class-edge sweep at 2^28 keys (DESIGN.md §3.6,
+// profiles/segsort_bench.txt): rows of 384 / 512 / 768 / 1024 keys took 5.2 / 4.0 / 2.9 / 2.3 ms
+// in the block class and 1.45 / 1.27 / 1.17 / 1.05 ms in a wave class; one wave kernel with 8
+// (16) keys per lane for every length was 5-8 % slower at 64-256 keys (15 % at 384-512) than
+// the kernel with just enough registers, hence three instantiations.
+#ifndef LABSORT_SEG_WAVE_KPT
+#define LABSORT_SEG_WAVE_KPT 4  // A/B build knobs of the sweep
+#endif
+#ifndef LABSORT_SEG_WAVE2_KPT
+#define LABSORT_SEG_WAVE2_KPT 8
+#endif
+#ifndef LABSORT_SEG_WAVE3_KPT
+#define LABSORT_SEG_WAVE3_KPT 16
+#endif
+constexpr int SEG_WAVE_KPT = LABSORT_SEG_WAVE_KPT, SEG_WAVE2_KPT = LABSORT_SEG_WAVE2_KPT,
+              SEG_WAVE3_KPT = LABSORT_SEG_WAVE3_KPT;
+// longest segment of each wave class
+constexpr int SEG_WAVE_KEYS = WAVE * SEG_WAVE_KPT, SEG_WAVE2_KEYS = WAVE * SEG_WAVE2_KPT,
+              SEG_WAVE3_KEYS = WAVE * SEG_WAVE3_KPT;
+static_assert(SEG_WAVE_KEYS < SEG_WAVE2_KEYS && SEG_WAVE2_KEYS < SEG_WAVE3_KEYS, "class edges ascend");
+constexpr int SEG_WAVE_WPB = 4;  // segments (waves) per workgroup
+// block class: one 256-thread workgroup per segment, 16 keys per thread
+constexpr int SEG_BLOCK = 256;
+constexpr int SEG_BLOCK_KPT = 16;
+constexpr int SEG_BLOCK_KEYS = SEG_BLOCK * SEG_BLOCK_KPT;  // 4096
+// tile class: k_tile_sort's shapes, 1024 threads x 32 keys or x 16 pairs
+constexpr int SEG_TILE_KEYS = TS_BLOCK * TS_KPT;        // 32768
+constexpr int SEG_TILE_PAIRS = TS_BLOCK * TS_KPT_KV;    // 16384
+constexpr int SEG_CLASSES = 5;
+struct SegEdges {
+    uint32_t e[SEG_CLASSES - 1];  // upper length bounds below the tile
+};
+static_assert(SEG_WAVE3_KEYS < SEG_BLOCK_KEYS, "class edges ascend");
+
+// Workspace header (the first 256 bytes, cleared at the start of every call).
+//   word 0: offsets rejected by k_seg_bin (labsort_segments_workspace_status: ERR_ARG)
+//   word 1: an inner pair sort of the general path reported an error (ERR_DEVICE)
+//   words 4..8: entries in the class lists
+constexpr int SEG_HDR_BYTES = 256;
+constexpr int SEG_HDR_DEVERR = 1, SEG_HDR_CNT = 4;
+
+// Validate the offsets (ends, monotonicity, every length <= max_len when max_len != 0) and,
+// with lists != nullptr, append each segment to the list of its class (lists + c * stride).
+// copy1: out of place, so 1-key segments are listed too (wave class) and get copied.
+hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max_len, bool pairs, bool copy1,
+                          uint32_t *hdr, uint32_t *lists, size_t stride, hipStream_t s);
+// The sort kernel of class c (0-2 wave, 3 block, 4 tile) over its list; vin/vout nullptr: keys only.
+hipError_t launch_seg_sort(int c, const uint32_t *in, uint32_t *out, const uint32_t *vin, uint32_t *vout,
+                           const uint32_t *off, const uint32_t *hdr, const uint32_t *list, uint32_t flip,
+                           hipStream_t s);
+// general path helpers (all return at once when hdr word 0 is set)
+// ids[i] = segment of position (idx ? idx[i] : i); iota (or nullptr): iota[i] = i
+hipError_t launch_seg_ids(const uint32_t *off, size_t nseg, size_t n, const uint32_t *idx, uint32_t *ids,
+                          uint32_t *iota, const uint32_t *hdr, hipStream_t s);
+// out[i] = perm ? src[perm[i]] : src[i], for keys and (vsrc != nullptr) payloads
+hipError_t launch_seg_gather(const uint32_t *src, const uint32_t *vsrc, const uint32_t *perm, uint32_t *out,
+                             uint32_t *vout, size_t n, const uint32_t *hdr, hipStream_t s);
+// hdr[SEG_HDR_DEVERR] |= *inner_err; *inner_err = 0
+hipError_t launch_seg_err_acc(uint32_t *hdr, uint32_t *inner_err, hipStream_t s);
+
+}  // namespace labsort

@@ -1,0 +1,547 @@
+// segsort.hip -- segmented sort: many independent [start, end) ranges of one buffer sorted
+// in one call (labsort_sort_segments_device / labsort_sort_segments_pairs_device).
+//
+//   k_seg_bin    one thread per segment: validates the offsets and appends the segment to
+//                the list of its length class (wave-aggregated, one global atomic per
+//                workgroup and class)
+//   k_seg_wave   the three wave classes: one wave64 per segment, wave-private LDS, no workgroup
+//                barrier; up to 64 keys by counting ranks in registers, longer ones by 8-bit
+//                LSD passes (4, 8 or 16 keys per lane)
+//   k_seg_block  block and tile classes: k_tile_sort's LDS passes on a [start, end) range,
+//                one workgroup per segment, grid-stride over the class list
+//   k_seg_ids, k_seg_gather, k_seg_err_acc   the general path's glue around the pair sorts
+//
+// Every kernel after k_seg_bin reads the workspace's error word first and returns when
+// it is set, so rejected offsets never become addresses.
+#include "segsort.h"
+
+#include "devutil.h"
+
+namespace labsort {
+
+namespace {
+
+constexpr int BIN_BLOCK = 1024, BIN_SPT = 4;  // 4096 segments per workgroup
+
+__global__ __launch_bounds__(BIN_BLOCK) void k_seg_bin(const uint32_t *__restrict__ off, uint32_t nseg, uint32_t n,
+                                                        uint32_t max_len, SegEdges e, uint32_t copy1,
+                                                        uint32_t *__restrict__ hdr, uint32_t *__restrict__ lists,
+                                                        size_t stride) {
+    __shared__ uint32_t cnt[SEG_CLASSES], base[SEG_CLASSES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    if (tid < (uint32_t)SEG_CLASSES) cnt[tid] = 0u;
+    __syncthreads();
+    uint32_t cls[BIN_SPT], pos[BIN_SPT];
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < BIN_SPT; ++j) {
+        const uint32_t seg = blockIdx.x * (uint32_t)(BIN_BLOCK * BIN_SPT) + (uint32_t)j * BIN_BLOCK + tid;
+        uint32_t c = SEG_CLASSES;  // none: nothing to sort or copy
+        if (seg < nseg) {
+            const uint32_t a = off[seg], b = off[seg + 1];
+            if (b < a || b > n) {
+                bad = true;
+            } else {
+                const uint32_t len = b - a;
+                if (max_len && len > max_len) bad = true;
+                if (len > 1u || (len == 1u && copy1)) {
+                    c = 0u;
+#pragma unroll
+                    for (int q = 0; q < SEG_CLASSES - 1; ++q) c += len > e.e[q] ? 1u : 0u;
+                }
+            }
+            if (seg == 0u && a != 0u) bad = true;
+            if (seg == nseg - 1u && b != n) bad = true;
+        }
+        cls[j] = c;
+        pos[j] = 0u;
+        if (lists) {
+#pragma unroll
+            for (uint32_t cc = 0; cc < (uint32_t)SEG_CLASSES; ++cc) {
+                const uint64_t m = __ballot(c == cc);
+                if (m == 0ull) continue;  // wave-uniform
+                const uint32_t leader = (uint32_t)__ffsll((long long)m) - 1u;
+                uint32_t wb = 0u;
+                if (lane == leader) wb = atomicAdd(&cnt[cc], (uint32_t)__popcll(m));
+                wb = __shfl(wb, (int)leader);
+                if (c == cc) pos[j] = wb + mbcnt64(m);
+            }
+        }
+    }
+    if (bad) atomicOr(hdr, 1u);
+    if (!lists) return;
+    __syncthreads();
+    if (tid < (uint32_t)SEG_CLASSES) base[tid] = cnt[tid] ? atomicAdd(hdr + SEG_HDR_CNT + tid, cnt[tid]) : 0u;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < BIN_SPT; ++j) {
+        const uint32_t seg = blockIdx.x * (uint32_t)(BIN_BLOCK * BIN_SPT) + (uint32_t)j * BIN_BLOCK + tid;
+        // (a class list holds at most nseg entries: one per segment)
+        if (cls[j] < (uint32_t)SEG_CLASSES) lists[(size_t)cls[j] * stride + base[cls[j]] + pos[j]] = seg;
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// wave class
+// ---------------------------------------------------------------------------------
+template <int KPT, bool KV>
+struct SwSmem {
+    uint32_t keys[WAVE * KPT];
+    uint32_t vals[KV ? WAVE * KPT : 1];
+    uint32_t hist[256];
+    uint32_t probe[WAVE];
+};
+
+template <int KPT, bool KV>
+__global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_seg_wave(const uint32_t *in, uint32_t *out, const uint32_t *vin,
+                                                                  uint32_t *vout, const uint32_t *__restrict__ off,
+                                                                  const uint32_t *__restrict__ hdr,
+                                                                  const uint32_t *__restrict__ list, int cls,
+                                                                  uint32_t flip) {
+    constexpr uint32_t CAP = WAVE * KPT;
+    __shared__ SwSmem<KPT, KV> sm_all[SEG_WAVE_WPB];
+    if (ld_agent(hdr) != 0u) return;  // rejected offsets: touch nothing
+    const uint32_t cnt = hdr[SEG_HDR_CNT + cls];
+    const uint32_t lane = threadIdx.x & 63u, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (blockIdx.x * SEG_WAVE_WPB + wid >= cnt) return;  // (an empty class costs its launch only)
+    SwSmem<KPT, KV> &sm = sm_all[wid];
+    const uint32_t sentinel = ~flip;
+    const bool atomic_rank = lds_lane_ordered(sm.probe, lane);
+    for (uint32_t it = blockIdx.x * SEG_WAVE_WPB + wid; it < cnt; it += gridDim.x * SEG_WAVE_WPB) {
+        const uint32_t seg = __builtin_amdgcn_readfirstlane(list[it]);
+        const uint32_t b = __builtin_amdgcn_readfirstlane(off[seg]);
+        const uint32_t len = __builtin_amdgcn_readfirstlane(off[seg + 1]) - b;
+        if (len == 0u || len > CAP) continue;
+        if (len <= (uint32_t)WAVE) {
+            // one key per lane: its stable rank is the count of keys before it in (key, lane) order
+            const bool ok = lane < len;
+            const uint32_t x = ok ? (in[b + lane] ^ flip) : 0xFFFFFFFFu;
+            uint32_t v = 0u;
+            if constexpr (KV) v = ok ? vin[b + lane] : 0u;
+            uint32_t r = 0u;
+            for (uint32_t i = 0; i < len; ++i) {
+                const uint32_t xi = __builtin_amdgcn_readlane(x, (int)i);
+                r += (xi < x || (xi == x && i < lane)) ? 1u : 0u;
+            }
+            if (ok) {  // r < len: fewer than len keys come before one of them
+                out[b + r] = x ^ flip;
+                if constexpr (KV) vout[b + r] = v;
+            }
+            continue;
+        }
+        const uint32_t jn = (len + WAVE - 1u) / WAVE;  // 64-key groups that hold keys (<= KPT)
+        uint32_t k[KPT];
+        uint32_t v[KV ? KPT : 1];
+        uint32_t a = ~0u, o = 0u;
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const uint32_t idx = (uint32_t)j * WAVE + lane;
+            const bool ok = idx < len;
+            k[j] = ok ? in[b + idx] : sentinel;
+            if constexpr (KV) v[j] = ok ? vin[b + idx] : 0u;
+            const uint32_t x = k[j] ^ flip;
+            a &= ok ? x : ~0u;
+            o |= ok ? x : 0u;
+        }
+#pragma unroll
+        for (int offx = 32; offx > 0; offx >>= 1) {
+            a &= __shfl_xor(a, offx);
+            o |= __shfl_xor(o, offx);
+        }
+        const uint32_t diff = __builtin_amdgcn_readfirstlane(a ^ o);
+        for (int pass = 0; pass < 4; ++pass) {
+            const uint32_t shift = pass * 8;
+            if (((diff >> shift) & 0xFFu) == 0u) continue;  // uniform over the segment
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sm.hist[q * WAVE + lane] = 0u;
+            __builtin_amdgcn_wave_barrier();
+            uint32_t rank[KPT];
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                rank[j] = 0u;
+                if ((uint32_t)j < jn) {  // wave-uniform; a group past the end holds padding only
+                    const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
+                    if (atomic_rank) {
+                        rank[j] = wave_atomic_rank(sm.hist, d, lane);
+                    } else {
+                        const uint64_t m = match8(d);
+                        const uint32_t pre = mbcnt64(m);
+                        const uint32_t old = sm.hist[d];
+                        if (pre == 0) sm.hist[d] = old + (uint32_t)__popcll(m);
+                        rank[j] = old + pre;
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            {  // exclusive scan of the 256 counters: four per lane, then across the wave
+                uint32_t c[4], s = 0u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    c[q] = sm.hist[4u * lane + q];
+                    s += c[q];
+                }
+                uint32_t xs = s;
+#pragma unroll
+                for (int offx = 1; offx < 64; offx <<= 1) {
+                    const uint32_t t = __shfl_up(xs, offx);
+                    if (lane >= (uint32_t)offx) xs += t;
+                }
+                uint32_t run = xs - s;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    sm.hist[4u * lane + q] = run;
+                    run += c[q];
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < jn) rank[j] += sm.hist[((k[j] ^ flip) >> shift) & 0xFFu];  // < 64 jn <= CAP
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < jn) {
+                    sm.keys[rank[j]] = k[j];
+                    if constexpr (KV) sm.vals[rank[j]] = v[j];
+                }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < jn) {
+                    k[j] = sm.keys[(uint32_t)j * WAVE + lane];
+                    if constexpr (KV) v[j] = sm.vals[(uint32_t)j * WAVE + lane];
+                }
+            __builtin_amdgcn_wave_barrier();
+        }
+        // padding sorts behind every key (stable, largest digits), so slots < len hold the keys
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const uint32_t idx = (uint32_t)j * WAVE + lane;
+            if (idx < len) {
+                out[b + idx] = k[j];
+                if constexpr (KV) vout[b + idx] = v[j];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// block and tile classes: k_tile_sort's passes (kernels.hip) on one segment per workgroup.
+// The segment is striped over the waves in runs of S = 64 ceil(len / (64 W)) slots, so a
+// short segment of the class costs every wave the same few 64-key groups; groups that
+// start past the end are neither ranked nor read back.
+// ---------------------------------------------------------------------------------
+template <int BLOCK, int KPT, bool KV>
+__global__ __launch_bounds__(BLOCK, 4) void k_seg_block(const uint32_t *in, uint32_t *out, const uint32_t *vin,
+                                                         uint32_t *vout, const uint32_t *__restrict__ off,
+                                                         const uint32_t *__restrict__ hdr,
+                                                         const uint32_t *__restrict__ list, int cls, uint32_t flip) {
+    constexpr int R = 256, W = BLOCK / WAVE;
+    constexpr uint32_t TILE = (uint32_t)BLOCK * KPT;
+    static_assert(TILE <= 65536u, "16-bit LDS slots");
+    struct S {
+        uint32_t keys[TILE];
+        uint32_t vals[KV ? TILE : 1];
+        uint32_t whist[W * R];
+        uint32_t wsum[W];
+        uint32_t red_and[W];
+        uint32_t red_or[W];
+        uint32_t probe[WAVE];
+        uint32_t ordered;
+    };
+    __shared__ S sm;
+    if (ld_agent(hdr) != 0u) return;  // rejected offsets: touch nothing
+    const uint32_t cnt = hdr[SEG_HDR_CNT + cls];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t sentinel = ~flip;
+    if (blockIdx.x >= cnt) return;  // (an empty class costs its launch only; uniform over the workgroup)
+    if (wid == 0) {
+        const bool ord = lds_lane_ordered(sm.probe, lane);
+        if (lane == 0) sm.ordered = ord ? 1u : 0u;
+    }
+    __syncthreads();
+    const bool atomic_rank = __builtin_amdgcn_readfirstlane(sm.ordered) != 0u;
+    uint32_t *wh = sm.whist + wid * R;
+    // the list entry and the two offsets are three dependent loads: those of the next segment
+    // are issued before this one is sorted
+    uint32_t nb = 0u, ne = 0u;
+    if (blockIdx.x < cnt) {
+        const uint32_t seg = __builtin_amdgcn_readfirstlane(list[blockIdx.x]);
+        nb = __builtin_amdgcn_readfirstlane(off[seg]);
+        ne = __builtin_amdgcn_readfirstlane(off[seg + 1]);
+    }
+    for (uint32_t it = blockIdx.x; it < cnt; it += gridDim.x) {
+        const uint32_t b = nb, len = ne - nb;
+        if (it + gridDim.x < cnt) {
+            const uint32_t seg = __builtin_amdgcn_readfirstlane(list[it + gridDim.x]);
+            nb = __builtin_amdgcn_readfirstlane(off[seg]);
+            ne = __builtin_amdgcn_readfirstlane(off[seg + 1]);
+        }
+        if (len == 0u || len > TILE) continue;  // (uniform over the workgroup)
+        const uint32_t jn = (len + (uint32_t)(W * WAVE) - 1u) / (uint32_t)(W * WAVE);  // groups per wave, <= KPT
+        const uint32_t ws0 = wid * jn * WAVE;  // first slot of this wave's stripe
+        // this wave's keys: nf whole 64-key groups and a last group of `tail` keys (wave-uniform),
+        // so whole groups load and store under scalar branches and one lane mask serves the last
+        const uint32_t rem = ws0 < len ? len - ws0 : 0u;
+        const uint32_t nf = min(jn, rem / WAVE);
+        const uint32_t tail = nf < jn ? rem - nf * WAVE : 0u;  // < 64
+        const uint32_t ng = nf + (tail ? 1u : 0u);             // groups that hold keys
+        const bool tail_ok = lane < tail;
+        // scalar base + 32-bit lane offset per access: the lane offsets pass through empty asms so no
+        // 64-bit per-lane address of in / out is formed outside the segment loop and held across it
+        const size_t sb = (size_t)b + ws0;
+        uint32_t lin = lane;
+        asm volatile("" : "+v"(lin));
+        uint32_t k[KPT];
+        uint32_t v[KV ? KPT : 1];
+        uint32_t a = ~0u, o = 0u;
+        // every load first, so all of them are in flight together (a use inside the scalar
+        // branches would wait for each load in turn), then the bits the keys differ in
+        if (nf == (uint32_t)KPT) {  // a whole tile: straight-line loads, as k_tile_sort
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) k[j] = ld_stream<NT_TILE>(in + sb + ((uint32_t)(j * WAVE) + lin));
+            if constexpr (KV) {
+#pragma unroll
+                for (int j = 0; j < KPT; ++j) v[j] = vin[sb + ((uint32_t)(j * WAVE) + lin)];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                k[j] = sentinel;
+                if constexpr (KV) v[j] = 0u;
+                if ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) {
+                    k[j] = ld_stream<NT_TILE>(in + sb + ((uint32_t)(j * WAVE) + lin));
+                    if constexpr (KV) v[j] = vin[sb + ((uint32_t)(j * WAVE) + lin)];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const uint32_t x = k[j] ^ flip;  // padding: all ones
+            a &= x;
+            o |= ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) ? x : 0u;
+        }
+#pragma unroll
+        for (int offx = 32; offx > 0; offx >>= 1) {
+            a &= __shfl_xor(a, offx);
+            o |= __shfl_xor(o, offx);
+        }
+        if (lane == 0) {
+            sm.red_and[wid] = a;
+            sm.red_or[wid] = o;
+        }
+        __syncthreads();
+        uint32_t diff = 0;
+        {
+            uint32_t aa = ~0u, oo = 0u;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                aa &= sm.red_and[w];
+                oo |= sm.red_or[w];
+            }
+            diff = __builtin_amdgcn_readfirstlane(aa ^ oo);
+        }
+        for (int pass = 0; pass < 4; ++pass) {
+            const uint32_t shift = pass * 8;
+            if (((diff >> shift) & 0xFFu) == 0u) continue;  // uniform over the segment
+            for (uint32_t i = lane; i < (uint32_t)R; i += WAVE) wh[i] = 0u;
+            uint32_t rank[KPT / 2];  // two 16-bit ranks / slots per register, as k_tile_sort
+            // (the group count through an empty asm: the per-group compares are redone where they are
+            // used; hoisted out of the pass loop they were held in SGPRs across it and spilled)
+            uint32_t ngr = ng, ngs = ng, ngb = ng;
+            asm volatile("" : "+s"(ngr), "+s"(ngs), "+s"(ngb));
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                uint32_t r = 0u;
+                if ((uint32_t)j < ngr) {  // wave-uniform: the group holds keys
+                    const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
+                    if (atomic_rank) {
+                        r = wave_atomic_rank(wh, d, lane);
+                    } else {
+                        const uint64_t m = match8(d);
+                        const uint32_t pre = mbcnt64(m);
+                        const uint32_t old = wh[d];
+                        if (pre == 0) wh[d] = old + (uint32_t)__popcll(m);
+                        r = old + pre;
+                    }
+                }
+                rank[j / 2] = (j & 1) ? rank[j / 2] | (r << 16) : r;
+            }
+            __syncthreads();
+            uint32_t tot = 0;
+            if (tid < (uint32_t)R) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) tot += sm.whist[w * R + tid];
+            }
+            const uint32_t ds = block_excl_scan<BLOCK, R>(tot, sm.wsum);
+            if (tid < (uint32_t)R) {
+                uint32_t run = ds;
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    const uint32_t c = sm.whist[w * R + tid];
+                    sm.whist[w * R + tid] = run;
+                    run += c;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
+                const uint32_t dst = wh[d] + ((rank[j / 2] >> ((j & 1) * 16)) & 0xFFFFu);
+                rank[j / 2] = (j & 1) ? (rank[j / 2] & 0xFFFFu) | (dst << 16) : (rank[j / 2] & 0xFFFF0000u) | dst;
+            }
+            // ranked slots number the keys and the padding of the last group: dst < 64 ceil(len / 64) <= TILE
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < ngs) {
+                    const uint32_t dst = (rank[j / 2] >> ((j & 1) * 16)) & 0xFFFFu;
+                    sm.keys[dst] = k[j];
+                    if constexpr (KV) sm.vals[dst] = v[j];
+                }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < ngb) {
+                    k[j] = sm.keys[ws0 + (uint32_t)j * WAVE + lane];
+                    if constexpr (KV) v[j] = sm.vals[ws0 + (uint32_t)j * WAVE + lane];
+                }
+        }
+        uint32_t nfs = nf, lout = lane;
+        asm volatile("" : "+s"(nfs), "+v"(lout));
+        if (nfs == (uint32_t)KPT) {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) out[sb + ((uint32_t)(j * WAVE) + lout)] = k[j];
+            if constexpr (KV) {
+#pragma unroll
+                for (int j = 0; j < KPT; ++j) vout[sb + ((uint32_t)(j * WAVE) + lout)] = v[j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                if ((uint32_t)j < nfs || ((uint32_t)j == nfs && tail_ok)) {
+                    out[sb + ((uint32_t)(j * WAVE) + lout)] = k[j];
+                    if constexpr (KV) vout[sb + ((uint32_t)(j * WAVE) + lout)] = v[j];
+                }
+            }
+        }
+        __syncthreads();  // the next segment reuses red_and / red_or and the key slots
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// general path glue
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_seg_ids(const uint32_t *__restrict__ off, uint32_t nseg, uint32_t n,
+                                                 const uint32_t *__restrict__ idx, uint32_t *__restrict__ ids,
+                                                 uint32_t *__restrict__ iota, const uint32_t *__restrict__ hdr) {
+    if (ld_agent(hdr) != 0u) return;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (iota) iota[i] = (uint32_t)i;
+        if (!ids) continue;
+        uint32_t p = idx ? idx[i] : (uint32_t)i;
+        if (p >= n) p = n - 1u;
+        // first q in [1, nseg] with off[q] > p (off[nseg] = n > p): p lies in segment q - 1
+        uint32_t lo = 1u, hi = nseg;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            if (off[mid] > p) hi = mid;
+            else lo = mid + 1u;
+        }
+        ids[i] = lo - 1u;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_seg_gather(const uint32_t *__restrict__ src, const uint32_t *__restrict__ vsrc,
+                                                    const uint32_t *__restrict__ perm, uint32_t *__restrict__ out,
+                                                    uint32_t *__restrict__ vout, uint32_t n,
+                                                    const uint32_t *__restrict__ hdr) {
+    if (ld_agent(hdr) != 0u) return;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t p = perm ? perm[i] : (uint32_t)i;
+        if (p >= n) p = n - 1u;
+        out[i] = src[p];
+        if (vsrc) vout[i] = vsrc[p];
+    }
+}
+
+__global__ void k_seg_err_acc(uint32_t *hdr, uint32_t *inner) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        if (*inner) hdr[SEG_HDR_DEVERR] = 1u;
+        *inner = 0u;
+    }
+}
+
+int cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+    }
+    return cus;
+}
+
+unsigned stream_blocks(size_t n) {
+    size_t b = (n + 256 * 8 - 1) / (256 * 8);
+    return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
+}
+
+}  // namespace
+
+hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max_len, bool pairs, bool copy1,
+                          uint32_t *hdr, uint32_t *lists, size_t stride, hipStream_t s) {
+    const unsigned g = (unsigned)((nseg + BIN_BLOCK * BIN_SPT - 1) / (BIN_BLOCK * BIN_SPT));
+    (void)pairs;  // the class edges below the tile are the same for keys and pairs
+    const SegEdges e{{(uint32_t)SEG_WAVE_KEYS, (uint32_t)SEG_WAVE2_KEYS, (uint32_t)SEG_WAVE3_KEYS, (uint32_t)SEG_BLOCK_KEYS}};
+    k_seg_bin<<<g, BIN_BLOCK, 0, s>>>(off, (uint32_t)nseg, (uint32_t)n, (uint32_t)max_len, e, copy1 ? 1u : 0u, hdr, lists,
+                                      stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_sort(int c, const uint32_t *in, uint32_t *out, const uint32_t *vin, uint32_t *vout,
+                           const uint32_t *off, const uint32_t *hdr, const uint32_t *list, uint32_t flip,
+                           hipStream_t s) {
+    const bool kv = vin != nullptr;
+    const unsigned cus = (unsigned)cu_count();
+    // fixed grids, multiples of the CU count: what stays resident per CU by LDS
+    if (c == 0) {
+        if (kv) k_seg_wave<SEG_WAVE_KPT, true><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip);
+        else k_seg_wave<SEG_WAVE_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip);
+    } else if (c == 1) {
+        if (kv) k_seg_wave<SEG_WAVE2_KPT, true><<<cus * 6u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip);
+        else k_seg_wave<SEG_WAVE2_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip);
+    } else if (c == 2) {  // 110-127 VGPRs: four waves per SIMD
+        if (kv) k_seg_wave<SEG_WAVE3_KPT, true><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip);
+        else k_seg_wave<SEG_WAVE3_KPT, false><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip);
+    } else if (c == 3) {
+        if (kv) k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, true><<<cus * 4u, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip);
+        else k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, false><<<cus * 6u, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip);
+    } else if (c == 4) {
+        if (kv) k_seg_block<TS_BLOCK, TS_KPT_KV, true><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip);
+        else k_seg_block<TS_BLOCK, TS_KPT, false><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip);
+    } else {
+        return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_ids(const uint32_t *off, size_t nseg, size_t n, const uint32_t *idx, uint32_t *ids,
+                          uint32_t *iota, const uint32_t *hdr, hipStream_t s) {
+    k_seg_ids<<<stream_blocks(n), 256, 0, s>>>(off, (uint32_t)nseg, (uint32_t)n, idx, ids, iota, hdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_gather(const uint32_t *src, const uint32_t *vsrc, const uint32_t *perm, uint32_t *out,
+                             uint32_t *vout, size_t n, const uint32_t *hdr, hipStream_t s) {
+    k_seg_gather<<<stream_blocks(n), 256, 0, s>>>(src, vsrc, perm, out, vout, (uint32_t)n, hdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_err_acc(uint32_t *hdr, uint32_t *inner_err, hipStream_t s) {
+    k_seg_err_acc<<<1, 64, 0, s>>>(hdr, inner_err);
+    return hipGetLastError();
+}
+
+}  // namespace labsort

@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""Top-k selection measurements on an MI355X (output kept as
+profiles/topk_bench.txt).
+
+int32 keys, 2^28 in all, as rows x cols, smallest k with positions, on uniform keys and on
+keys % 1000:
+  topk      labsort_topk_device
+  fullsort  what a caller could do before it: one row, labsort_sort_pairs_device of (key, iota);
+            several rows, labsort_sort_segments_pairs_device with max_segment_keys = cols
+  copy      labsort_copy of the same keys (one read and one write: a read costs half of it)
+  torch     torch.topk(x, k, largest=False, sorted=True): an outside comparator, recorded only
+Every variant of a shape is timed in turn, repetition by repetition (device events around one
+call), after one warm-up each; median [min, max] ms over the repetitions.
+
+--sweep: the large-k threshold.  One row of 2^logn keys, k from 2^10 up to the whole row, with the
+path forced either way (LABSORT_TOPK_PATH=select / sort, read at every call), alternating."""
+import argparse
+import importlib
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+ls = importlib.import_module("radix-sort-merge-sort-cuda---lab-y-practicos-gpgpu-2023_amd")
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def alternate(variants, reps):
+    """variants: {name: fn}.  One warm-up each, then reps rounds over all of them."""
+    for fn in variants.values():
+        fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, fn in variants.items():
+            t[k].append(timed(fn))
+    return t
+
+
+def fmt(ts):
+    return f"{statistics.median(ts):8.3f} [{min(ts):7.3f}, {max(ts):7.3f}]"
+
+
+def med(ts):
+    return statistics.median(ts)
+
+
+def forced(path, fn):
+    def f():
+        os.environ["LABSORT_TOPK_PATH"] = path
+        try:
+            fn()
+        finally:
+            del os.environ["LABSORT_TOPK_PATH"]
+    return f
+
+
+def check(keys, rows, cols, k, ko, io):
+    """Keys against torch.sort; positions by gathering (torch's tie order is its own)."""
+    x = keys.view(rows, cols)
+    exp = torch.sort(x, dim=1, stable=True).values[:, :k]
+    assert torch.equal(ko.view(rows, k), exp), (rows, cols, k)
+    assert torch.equal(torch.gather(x, 1, io.view(rows, k).long()), exp), (rows, cols, k)
+    del exp
+
+
+def shapes_main(logn, reps, out, with_torch):
+    n = 1 << logn
+    keys = torch.empty(n, dtype=torch.int32, device="cuda")
+    iota = torch.arange(n, dtype=torch.int32, device="cuda")
+    so, sv = torch.empty_like(keys), torch.empty_like(keys)
+    print(f"# top-k, int32 keys, smallest k with positions, n = 2^{logn}, {reps} alternating repetitions, "
+          "ms: median [min, max]", file=out)
+    print(f"# device: {torch.cuda.get_device_name(0)}; {ls.version()}", file=out)
+    shapes = [(1, n, 1), (1, n, 1024), (1, n, min(1 << 20, n)), (n >> 16, 1 << 16, 64), (n >> 12, 4096, 8)]
+    for dist in ("u32", "mod1000"):
+        ls.fill(keys, n, seed=0x70C0EED, dist=dist)
+        torch.cuda.synchronize()
+        for rows, cols, k in shapes:
+            ko = torch.empty(rows * k, dtype=torch.int32, device="cuda")
+            io = torch.empty(rows * k, dtype=torch.int32, device="cuda")
+            ws = torch.full((ls.topk_workspace_bytes(rows, cols, k),), 0xFF, dtype=torch.uint8, device="cuda")
+            v = {"topk": lambda: ls.topk_device(keys, rows, cols, k, ko, io, key="i32", workspace=ws)}
+            if rows == 1:
+                ws_f = torch.empty(ls.pairs_workspace_bytes(n, "auto"), dtype=torch.uint8, device="cuda")
+                v["fullsort"] = lambda: ls.sort_pairs_device(keys, iota, so, sv, n, key="i32", algo="auto", workspace=ws_f)
+            else:
+                offs = ls.row_offsets(rows, cols)
+                ws_f = torch.empty(ls.segments_workspace_bytes(n, rows, cols, True), dtype=torch.uint8, device="cuda")
+                v["fullsort"] = lambda: ls.sort_segments_pairs_device(keys, iota, so, sv, n, offs, rows, cols, key="i32",
+                                                                      workspace=ws_f)
+            v["copy"] = lambda: ls.copy(keys, so, n)
+            if with_torch:
+                v["torch"] = lambda: torch.topk(keys.view(rows, cols), k, dim=1, largest=False, sorted=True)
+            t = alternate(v, reps)
+            ko.zero_()
+            v["topk"]()
+            ls.topk_workspace_status(ws)
+            check(keys, rows, cols, k, ko, io)
+            path = "short" if cols <= ls.segment_pair_tile_keys() else ("sort" if k * ls.TOPK_SORT_DIV > cols else "select")
+            print(f"{dist:<8}{rows:>6} x {cols:<10} k {k:<8} {path:<7}" +
+                  "  ".join(f"{name} {fmt(ts)}" for name, ts in t.items()) +
+                  f"  topk/fullsort {med(t['topk']) / med(t['fullsort']):.3f}  topk/copy {med(t['topk']) / med(t['copy']):.2f}",
+                  file=out)
+            out.flush()
+            del ws, ws_f, ko, io
+
+
+def sweep_main(logn, reps, out):
+    n = 1 << logn
+    keys = torch.empty(n, dtype=torch.int32, device="cuda")
+    print(f"# large-k sweep, one row of 2^{logn} int32 keys, path forced, {reps} alternating repetitions, "
+          "ms: median [min, max]", file=out)
+    for dist in ("u32", "mod1000"):
+        ls.fill(keys, n, seed=0x70C0EED, dist=dist)
+        torch.cuda.synchronize()
+        for k in [1 << lk for lk in range(10, logn - 2, 2)] + [n // 8, n // 4, 3 * (n // 8), n // 2, 3 * (n // 4), n]:
+            ko = torch.empty(k, dtype=torch.int32, device="cuda")
+            io = torch.empty(k, dtype=torch.int32, device="cuda")
+            v, wss = {}, {}
+            for path in ("select", "sort"):
+                os.environ["LABSORT_TOPK_PATH"] = path
+                wss[path] = torch.empty(ls.topk_workspace_bytes(1, n, k), dtype=torch.uint8, device="cuda")
+                del os.environ["LABSORT_TOPK_PATH"]
+                v[path] = forced(path, lambda w=wss[path]: ls.topk_device(keys, 1, n, k, ko, io, key="i32", workspace=w))
+            t = alternate(v, reps)
+            print(f"{dist:<8}k {k:<10} k/cols {k / n:<10.6f}" + "  ".join(f"{name} {fmt(ts)}" for name, ts in t.items()) +
+                  f"  select/sort {med(t['select']) / med(t['sort']):.3f}", file=out)
+            out.flush()
+            del wss, ko, io
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--logn", type=int, default=28)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("topk_bench: no GPU (no CPU fallback)")
+    out = open(a.out, "a") if a.out else sys.stdout
+    if a.sweep:
+        sweep_main(a.logn, a.reps, out)
+    else:
+        shapes_main(a.logn, a.reps, out, not a.no_torch)

@@ -83,7 +83,8 @@ extern "C" {
 #define LABSORT_K_COPY 7         /* the streaming copy (labsort_copy: the bench's copy ceiling) */
 #define LABSORT_K_MERGE4 8       /* four-way merge pass of the merge sort (k_m4_rank + k_m4_merge) */
 #define LABSORT_K_SEGSORT 9      /* segmented sort: classification, the LDS class kernels, the general path's glue */
-#define LABSORT_K_COUNT 10
+#define LABSORT_K_TOPK 10        /* top-k selection: the select's own kernels and the glue around the inner sorts */
+#define LABSORT_K_COUNT 11
 
 /* ---- library info ---- */
 const char *labsort_version(void);
@@ -283,6 +284,39 @@ int labsort_sort_segments_pairs_device(const void *d_keys_in, const void *d_vals
                                        size_t max_segment_keys, int key_type, void *d_workspace,
                                        size_t workspace_bytes, void *stream);
 int labsort_segments_workspace_status(const void *d_workspace, void *stream);
+
+/* ---- top-k selection: the k smallest or largest keys of every row, sorted, with their
+ * positions (torch.topk on a matrix; no lab.cu counterpart) ----
+ * d_keys is a dense rows x cols matrix of 32-bit keys, never written; d_keys_out is rows x k;
+ * d_idx_out is rows x k positions within the row, or NULL (keys only).  With
+ * u(x) = x ^ flip_of(key_type) ^ (largest ? 0xFFFFFFFF : 0), row r of the output is the first
+ * k entries of the stable ascending sort of the row's (u(key), position) pairs, keys written
+ * back untransformed: best first, equal keys in order of position, and of the ties of the k-th
+ * key those with the lowest positions.  The output, indices included, is a deterministic
+ * function of the input (torch.topk leaves the tie order open).
+ * 1 <= k <= cols, rows * cols <= 2^31 - 1; rows == 0 or k == 0 launches nothing.
+ * LABSORT_ERR_ARG before any launch: NULL d_keys / d_keys_out, a bad key type, k > cols, a
+ * missing or short workspace, an output that overlaps the input, d_idx_out == d_keys_out, and
+ * rows > 1 with rows * k > labsort_max_keys(LABSORT_ALGO_RADIX) and
+ * k > labsort_segment_pair_tile_keys() (the survivors are ordered by the segmented sort's
+ * general path).
+ * cols <= labsort_segment_pair_tile_keys(): whole rows are sorted in LDS by the segmented
+ * sort's class kernels.  Longer rows: an MSD radix select with 8-bit digits (at most one
+ * histogram read per digit, no scatter; a row whose surviving bucket fits cols / 8 pairs is
+ * narrowed to it), then a stable sort of the k survivors.  k > cols / LABSORT_TOPK_SORT_DIV:
+ * whole rows are pair-sorted and the first k copied; the results are identical.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on
+ * the host arguments only, so a captured call may be replayed on new keys in the same buffers.
+ * The call clears the part of the workspace it relies on (garbage or a reused workspace is fine).
+ * labsort_topk_workspace_bytes never shrinks as k grows at fixed rows and cols.
+ * labsort_topk_workspace_status synchronises `stream` and returns LABSORT_ERR_DEVICE if an
+ * inner sort reported an error (word 0 of the workspace's 256-byte header), else LABSORT_OK. */
+#define LABSORT_TOPK_SORT_DIV 4
+size_t labsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k);
+int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, int largest, int key_type,
+                        void *d_keys_out, uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes,
+                        void *stream);
+int labsort_topk_workspace_status(const void *d_workspace, void *stream);
 
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +

@@ -31,7 +31,9 @@ ALGO = {"radix": 0, "merge": 1, "radix1": 2, "auto": 3}
 KEY = {"u32": 0, "i32": 1}
 DIST = {"u32": 0, "u31": 1, "mod100": 2, "mod1000": 3, "sorted": 4, "reversed": 5, "const": 6, "lowbits": 7}
 KCLASS = {"histogram": 0, "onesweep": 1, "tile_sort": 2, "merge": 3, "partition": 4, "gsweep": 5, "gcopy": 6,
-          "copy": 7, "merge4": 8, "segsort": 9}
+          "copy": 7, "merge4": 8, "segsort": 9, "topk": 10}
+# topk_device sorts whole rows from k > cols // TOPK_SORT_DIV (LABSORT_TOPK_SORT_DIV in labsort.h)
+TOPK_SORT_DIV = 4
 
 # exported symbols of include/labsort.h + lab.h (checked by tests/test_abi.py)
 C_SYMBOLS = [
@@ -52,6 +54,7 @@ C_SYMBOLS = [
     "labsort_segment_tile_keys", "labsort_segment_pair_tile_keys", "labsort_segment_class_edges",
     "labsort_segments_workspace_bytes", "labsort_sort_segments_device", "labsort_sort_segments_pairs_device",
     "labsort_segments_workspace_status",
+    "labsort_topk_workspace_bytes", "labsort_topk_device", "labsort_topk_workspace_status",
 ]
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
 MULTI_PHASES = ["h2d", "local_sort", "plan", "exchange", "merge", "d2h", "total", "plan_work", "plan_wait"]
@@ -179,6 +182,10 @@ def _load() -> ctypes.CDLL:
     L.labsort_sort_segments_device.argtypes = [p, p, sz, p, sz, sz, i, p, sz, p]
     L.labsort_sort_segments_pairs_device.argtypes = [p, p, p, p, sz, p, sz, sz, i, p, sz, p]
     L.labsort_segments_workspace_status.argtypes = [p, p]
+    L.labsort_topk_workspace_bytes.restype = sz
+    L.labsort_topk_workspace_bytes.argtypes = [sz, sz, sz]
+    L.labsort_topk_device.argtypes = [p, sz, sz, sz, i, i, p, p, p, sz, p]
+    L.labsort_topk_workspace_status.argtypes = [p, p]
     L.labsort_histogram.argtypes = [p, sz, i, i, p, p]
     L.labsort_fill.argtypes = [p, sz, u64, i, u64, u64, p]
     L.labsort_count_descents.argtypes = [p, sz, i, p, p]
@@ -631,6 +638,36 @@ def segments_workspace_status(workspace, stream=None) -> None:
     """Synchronise `stream`; raise LabsortError with ERR_ARG if the last segmented sort on
     `workspace` rejected its offsets, ERR_DEVICE if an inner sort reported a failure."""
     _check(lib.labsort_segments_workspace_status(_ptr(workspace), _stream(stream)), "sort_segments (status)")
+
+
+def topk_workspace_bytes(rows: int, cols: int, k: int) -> int:
+    return int(lib.labsort_topk_workspace_bytes(rows, cols, k))
+
+
+def topk_device(d_keys, rows: int, cols: int, k: int, d_keys_out, d_idx_out=None, largest: bool = False,
+                key: str = "u32", workspace=None, stream=None) -> None:
+    """The k smallest (largest) keys of every row of the dense rows x cols matrix d_keys, best
+    first, into d_keys_out (rows x k), and their positions within the row into d_idx_out (rows x k
+    int32 / uint32 words, or None): torch.topk(x, k, largest=..., sorted=True) with the tie order
+    fixed (equal keys in order of position; of the k-th key's ties the lowest positions).  With a
+    caller-owned `workspace` the call stays asynchronous (check topk_workspace_status when the
+    result is needed); without one it allocates, synchronises and checks."""
+    own = workspace is None
+    if own:
+        import torch
+        workspace = torch.empty(max(topk_workspace_bytes(rows, cols, k), 1), dtype=torch.uint8, device="cuda")
+    wsb = workspace.numel() * workspace.element_size()
+    _check(lib.labsort_topk_device(_ptr(d_keys), rows, cols, k, 1 if largest else 0, KEY[key], _ptr(d_keys_out),
+                                   None if d_idx_out is None else _ptr(d_idx_out), _ptr(workspace), wsb,
+                                   _stream(stream)), "topk_device")
+    if own:
+        topk_workspace_status(workspace, stream)
+
+
+def topk_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_DEVICE if an inner sort of the last
+    topk_device call on `workspace` reported a failure."""
+    _check(lib.labsort_topk_workspace_status(_ptr(workspace), _stream(stream)), "topk (status)")
 
 
 def histogram(d_keys, n: int, d_hist, bits: int = 8, key: str = "u32", stream=None) -> None:

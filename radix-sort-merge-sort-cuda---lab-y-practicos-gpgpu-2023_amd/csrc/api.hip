@@ -20,6 +20,7 @@
 #include "../../include/labsort.h"
 #include "common.h"
 #include "segsort.h"
+#include "topk.h"
 
 using namespace labsort;
 
@@ -1059,6 +1060,205 @@ int labsort_segments_workspace_status(const void *d_ws, void *stream) {
     HIP_TRY(hipMemcpyAsync(w, d_ws, sizeof w, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return w[0] ? LABSORT_ERR_ARG : w[SEG_HDR_DEVERR] ? LABSORT_ERR_DEVICE : LABSORT_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// top-k selection (topk.hip): the k best keys of every row, sorted, with their positions
+// ---------------------------------------------------------------------------------
+namespace {
+static_assert(TK_SORT_DIV == LABSORT_TOPK_SORT_DIV, "labsort.h states the large-k threshold");
+static_assert(SEG_HDR_CNT * 4 + SEG_CLASSES * 4 <= TK_HDR_BYTES && TK_HDR_BYTES == SEG_HDR_BYTES,
+              "the short path hands its header to the segmented sort's kernels");
+enum { TK_PATH_SHORT, TK_PATH_SELECT, TK_PATH_SORT };
+
+// Which path runs: host arguments only.  Whole-row sorting needs the inner sort's limits (one row:
+// any length; several: the segmented sort's general path), else the select serves every k.
+int topk_path(size_t rows, size_t cols, size_t k) {
+    if (cols <= (size_t)SEG_TILE_PAIRS) return TK_PATH_SHORT;
+    const bool sort_ok = rows == 1 || rows * cols <= RADIX_MAX_N;
+    bool want_sort = k * (size_t)TK_SORT_DIV > cols;
+    // LABSORT_TOPK_PATH=select / sort forces the long rows' path (harness/topk_bench.py --sweep)
+    if (const char *e = std::getenv("LABSORT_TOPK_PATH")) {
+        if (!std::strcmp(e, "select")) want_sort = false;
+        else if (!std::strcmp(e, "sort")) want_sort = true;
+    }
+    return (want_sort && sort_ok) ? TK_PATH_SORT : TK_PATH_SELECT;
+}
+
+// header | (select: hist, state, per-chunk tables, candidate buffers) | A, B: the m (u, position)
+// pairs per row to be ordered | SU, SP: the same, ordered | uniform offsets | the inner sort's
+// workspace.  m = k after a select, cols where whole rows are sorted.  The short path keeps the
+// segmented sort's class lists where the others keep the inner workspace, and has no A.
+struct TopkLayout {
+    int path;
+    size_t m, nch, cap, capa;
+    size_t off_hist, zero_bytes, off_st, off_cnt, off_low, off_eq, off_lowbase, off_eqbase, off_cand_u, off_cand_p;
+    size_t off_a, off_b, off_su, off_sp, off_offs, off_lists, list_stride, off_inner, inner_bytes, total;
+};
+TopkLayout topk_layout_path(size_t rows, size_t cols, size_t k, int path) {
+    TopkLayout L{};
+    L.path = path;
+    L.m = path == TK_PATH_SELECT ? k : cols;
+    size_t o = TK_HDR_BYTES;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o = align_up(o + bytes, 256);
+        return at;
+    };
+    if (path == TK_PATH_SELECT) {
+        L.nch = (cols + TK_CHUNK - 1) / TK_CHUNK;
+        L.cap = cols / TK_CAND_DIV;
+        L.capa = align_up(L.cap, 64);
+        L.off_hist = take(rows * TK_LEVELS * 256 * 4);
+        L.zero_bytes = o;  // header and histograms: the only words a call relies on being clear
+        L.off_st = take(rows * (TK_LEVELS + 1) * sizeof(TkState));
+        L.off_cnt = take(rows * L.nch * 256 * 4);
+        L.off_low = take(rows * L.nch * 4);
+        L.off_eq = take(rows * L.nch * 4);
+        L.off_lowbase = take(rows * L.nch * 4);
+        L.off_eqbase = take(rows * L.nch * 4);
+        L.off_cand_u = take(rows * L.capa * 4);
+        L.off_cand_p = take(rows * L.capa * 4);
+    } else {
+        L.zero_bytes = o;
+    }
+    const size_t n = rows * L.m;
+    if (path != TK_PATH_SHORT) L.off_a = take(n * 4);
+    L.off_b = take(n * 4);
+    L.off_su = take(n * 4);
+    L.off_sp = take(n * 4);
+    L.off_offs = take((rows + 1) * 4);
+    if (path == TK_PATH_SHORT) {
+        L.list_stride = align_up(rows * 4, 256) / 4;
+        L.off_lists = take((size_t)SEG_CLASSES * L.list_stride * 4);
+    } else {
+        L.inner_bytes = rows == 1 ? seg_inner_bytes(n) : labsort_segments_workspace_bytes(n, rows, L.m, 1);
+        L.off_inner = take(L.inner_bytes);
+    }
+    L.total = o;
+    return L;
+}
+TopkLayout topk_layout(size_t rows, size_t cols, size_t k) {
+    const int path = topk_path(rows, cols, k);
+    TopkLayout L = topk_layout_path(rows, cols, k, path);
+    // never less than the largest select below the threshold: the size does not shrink as k grows
+    if (path == TK_PATH_SORT && cols / TK_SORT_DIV >= 1)
+        L.total = std::max(L.total, topk_layout_path(rows, cols, cols / TK_SORT_DIV, TK_PATH_SELECT).total);
+    return L;
+}
+bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+}  // namespace
+
+size_t labsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k) {
+    if (rows == 0 || k == 0 || k > cols || rows > (size_t)0x7FFFFFFFu / cols) return TK_HDR_BYTES;
+    return topk_layout(rows, cols, k).total;
+}
+
+int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, int largest, int key_type,
+                        void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
+    if (rows == 0 || k == 0) return LABSORT_OK;
+    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
+    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
+    if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
+    if (ranges_overlap(d_keys, rows * cols * 4, d_keys_out, rows * k * 4)) return LABSORT_ERR_ARG;
+    if (d_idx_out && ranges_overlap(d_keys, rows * cols * 4, d_idx_out, rows * k * 4)) return LABSORT_ERR_ARG;
+    const int path = topk_path(rows, cols, k);
+    // the survivors of several long rows are ordered by the segmented sort: past its LDS tile, its general path
+    if (path == TK_PATH_SELECT && rows > 1 && k > (size_t)SEG_TILE_PAIRS && rows * k > RADIX_MAX_N) return LABSORT_ERR_ARG;
+    if (!d_ws || ws_bytes < labsort_topk_workspace_bytes(rows, cols, k)) return LABSORT_ERR_ARG;
+    const TopkLayout L = topk_layout_path(rows, cols, k, path);
+    const uint32_t xr = flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t *>(ws + off); };
+    const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
+    uint32_t *hdr = W(0), *A = W(L.off_a), *B = W(L.off_b), *SU = W(L.off_su), *SP = W(L.off_sp), *offs = W(L.off_offs);
+    uint32_t *ko = static_cast<uint32_t *>(d_keys_out);
+    const size_t n = rows * L.m;
+    HIP_TRY(launch_zero(ws, L.zero_bytes, s));  // (a kernel: graph-replayable)
+    if (path == TK_PATH_SHORT) {
+        // whole rows through the segmented sort's LDS classes, on (key, position) with xr as the flip
+        TimingScope ts(LABSORT_K_TOPK, s);
+        uint32_t *lists = W(L.off_lists);
+        HIP_TRY(launch_topk_offsets(offs, rows, cols, s));
+        HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, s));
+        HIP_TRY(launch_seg_bin(offs, rows, n, cols, true, true, hdr, lists, L.list_stride, s));
+        size_t edges[SEG_CLASSES];
+        labsort_segment_class_edges(1, edges, SEG_CLASSES);
+        int ncls = 1;
+        while (ncls < SEG_CLASSES && cols > edges[ncls - 1]) ++ncls;
+        for (int c = 0; c < ncls; ++c)
+            HIP_TRY(launch_seg_sort(c, keys, SU, B, SP, offs, hdr, lists + (size_t)c * L.list_stride, xr, s));
+        HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, cols, k, 0u, s));  // (the class kernels wrote keys, not u)
+        return LABSORT_OK;
+    }
+    if (path == TK_PATH_SELECT) {
+        TimingScope ts(LABSORT_K_TOPK, s);
+        TkArgs a{};
+        a.keys = keys;
+        a.hist = W(L.off_hist);
+        a.cnt = W(L.off_cnt);
+        a.low = W(L.off_low);
+        a.eq = W(L.off_eq);
+        a.lowbase = W(L.off_lowbase);
+        a.eqbase = W(L.off_eqbase);
+        a.st = reinterpret_cast<TkState *>(ws + L.off_st);
+        a.cand_u = W(L.off_cand_u);
+        a.cand_p = W(L.off_cand_p);
+        a.surv_u = A;
+        a.surv_p = B;
+        a.cols = (uint32_t)cols;
+        a.k = (uint32_t)k;
+        a.nch = (uint32_t)L.nch;
+        a.capa = (uint32_t)L.capa;
+        a.cap = (uint32_t)L.cap;
+        a.xr = xr;
+        for (int level = 0; level < TK_LEVELS; ++level) {
+            HIP_TRY(launch_topk_hist(a, rows, level, s));
+            HIP_TRY(launch_topk_reduce(a, rows, level, s));
+            HIP_TRY(launch_topk_scan(a, rows, level, s));
+            if (level < TK_LEVELS - 1 && L.cap > 0) HIP_TRY(launch_topk_narrow(a, rows, level, s));
+        }
+        HIP_TRY(launch_topk_final(a, rows, s));
+    } else {
+        TimingScope ts(LABSORT_K_TOPK, s);
+        HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, s));
+    }
+    // order the m pairs of every row on u (stable): one pair sort, or the segmented pair sort
+    char *iws = ws + L.off_inner;
+    uint32_t *ierr = reinterpret_cast<uint32_t *>(iws);
+    HIP_TRY(launch_zero(ierr, 16, s));  // (a one-tile inner sort has no error word of its own)
+    int st;
+    if (rows == 1) {
+        if ((st = labsort_sort_pairs_device(A, B, SU, SP, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
+            return st;
+    } else {
+        {
+            TimingScope ts(LABSORT_K_TOPK, s);
+            HIP_TRY(launch_topk_offsets(offs, rows, L.m, s));
+        }
+        if ((st = labsort_sort_segments_pairs_device(A, B, SU, SP, n, offs, rows, L.m, LABSORT_KEY_U32, iws, L.inner_bytes,
+                                                     stream)))
+            return st;
+    }
+    TimingScope ts(LABSORT_K_TOPK, s);
+    HIP_TRY(launch_topk_err_acc(hdr, ierr, 2, s));
+    HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, L.m, k, xr, s));
+    return LABSORT_OK;
+}
+
+int labsort_topk_workspace_status(const void *d_ws, void *stream) {
+    hipStream_t s = as_stream(stream);
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!d_ws) return LABSORT_ERR_ARG;
+    uint32_t w = 0;
+    HIP_TRY(hipMemcpyAsync(&w, d_ws, sizeof w, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return w ? LABSORT_ERR_DEVICE : LABSORT_OK;
 }
 
 int labsort_histogram(const void *d_keys, size_t n, int key_type, int bits, uint32_t *d_hist, void *stream) {

@@ -1,0 +1,419 @@
+// topk.hip -- top-k selection: the k smallest or largest keys of every row, with their positions
+// (labsort_topk_device).  All kernels work on u = key ^ xr, where plain uint32 order is the
+// order asked for.
+//
+// Rows longer than the segmented sort's pair tile are selected by an MSD radix select with 8-bit
+// digits.  A row is cut into chunks of TK_CHUNK keys; per level:
+//   k_tk_hist     counts the level's digit of the keys that match the prefix chosen so far: per
+//                 chunk (cnt) and per row (hist)
+//   k_tk_reduce   one wave per chunk: picks the digit d at which the row's running count reaches
+//                 the remaining k, and sums the chunk's counts below d (low, accumulated over the
+//                 levels) and at d (eq)
+//   k_tk_scan     one workgroup per row: exclusive scans of low and eq over the chunks, the next
+//                 level's state, and whether the row narrows
+//   k_tk_compact  <false>, levels 0-2, rows that narrow: one ordered pass over the input writes
+//                 the keys below the bucket to the survivor list and the bucket to the candidate
+//                 buffer; <true>, after level 3: the keys below the threshold and the first krem
+//                 keys equal to it go to the survivor list
+// Chunks are contiguous and every compaction places a chunk's keys at the chunk's scanned base in
+// thread order, so keys of one value reach the survivor list in position order: the stable sort
+// of the survivors that follows gives the tie rule for nothing.
+// Every dependency is a kernel boundary; a workgroup beyond a row's current source returns at once.
+#include "topk.h"
+
+#include "devutil.h"
+
+namespace labsort {
+
+namespace {
+
+struct TkSrc {
+    const uint32_t *u, *p;  // p == nullptr: the input (position = index, u = word ^ xr)
+    uint32_t count, xr;
+};
+
+__device__ __forceinline__ TkState tk_state(const TkArgs &a, uint32_t row, int level) {
+    if (level == 0) return TkState{0u, a.k, 0u, 0u, 0u, 0u, 0u, 0u};
+    return a.st[(size_t)row * (TK_LEVELS + 1) + level];
+}
+
+__device__ __forceinline__ TkSrc tk_src(const TkArgs &a, uint32_t row, const TkState &st) {
+    if (st.narrowed) {
+        const uint32_t c = st.ccount < a.cap ? st.ccount : a.cap;
+        return TkSrc{a.cand_u + (size_t)row * a.capa, a.cand_p + (size_t)row * a.capa, c, 0u};
+    }
+    return TkSrc{a.keys + (size_t)row * a.cols, nullptr, a.cols, a.xr};
+}
+
+// Elements [beg, end) of a source are read in quads that start 16-byte aligned: quad q holds the
+// elements i0 .. i0 + 3, i0 = beg - mis + 4 q, where mis is how far beg lies into its 16 bytes
+// (a row of odd length starts anywhere).  A quad inside the range is one 16-byte load; the head
+// and the tail are read word by word.  Returns the mask of the elements that exist.
+__device__ __forceinline__ uint32_t tk_mis(const uint32_t *base, uint32_t beg) {
+    return (uint32_t)(((uintptr_t)(base + beg) >> 2) & 3u);
+}
+__device__ __forceinline__ uint32_t tk_quads(uint32_t beg, uint32_t end, uint32_t mis) { return (end - beg + mis + 3u) / 4u; }
+
+__device__ __forceinline__ uint32_t tk_load_quad(const uint32_t *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
+                                                 uint32_t xr, uint32_t (&u)[4], int64_t &i0) {
+    i0 = (int64_t)beg - (int64_t)mis + 4 * (int64_t)q;
+    if (i0 >= (int64_t)beg && i0 + 4 <= (int64_t)end) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(base + i0);
+        u[0] = v.x ^ xr; u[1] = v.y ^ xr; u[2] = v.z ^ xr; u[3] = v.w ^ xr;
+        return 15u;
+    }
+    uint32_t vm = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = i0 + j;
+        u[j] = 0u;
+        if (i >= (int64_t)beg && i < (int64_t)end) {
+            u[j] = base[i] ^ xr;
+            vm |= 1u << j;
+        }
+    }
+    return vm;
+}
+
+// The digit at which the running count of a row's level histogram reaches krem: the d with
+// count(< d) < krem <= count(<= d).  Called by a whole wave; the result is wave-uniform.
+struct TkPick {
+    uint32_t d, below, bucket;
+};
+__device__ __forceinline__ TkPick tk_pick(const uint32_t *hrow, uint32_t krem, uint32_t lane) {
+    const uint4 v = reinterpret_cast<const uint4 *>(hrow)[lane];  // digits 4 lane .. 4 lane + 3
+    const uint32_t c[4] = {v.x, v.y, v.z, v.w};
+    const uint32_t s = v.x + v.y + v.z + v.w;
+    uint32_t x = s;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(x, off);
+        if (lane >= (uint32_t)off) x += t;
+    }
+    uint32_t run = x - s, d = 255u, below = x - c[3], bucket = c[3];  // (lane 63's default: the last digit)
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!found && run < krem && krem <= run + c[j]) {
+            found = true;
+            d = 4u * lane + (uint32_t)j;
+            below = run;
+            bucket = c[j];
+        }
+        run += c[j];
+    }
+    const uint64_t m = __ballot(found);
+    const int srcl = m ? __ffsll((long long)m) - 1 : 63;  // (no lane: krem exceeds the row's count, which cannot happen)
+    TkPick p;
+    p.d = __shfl(d, srcl);
+    p.below = __shfl(below, srcl);
+    p.bucket = __shfl(bucket, srcl);
+    if (p.below >= krem) p.below = krem - 1u;  // keeps krem >= 1 whatever the histogram held
+    return p;
+}
+
+__global__ __launch_bounds__(TK_BLOCK) void k_tk_hist(TkArgs a, int level, uint32_t nx, uint32_t g) {
+    __shared__ uint32_t h[256 * TK_SLOTS];
+    const uint32_t tid = threadIdx.x, slot = tid & (TK_SLOTS - 1u);
+    const uint32_t row = blockIdx.x / nx, bx = blockIdx.x - row * nx;
+    const TkState st = tk_state(a, row, level);
+    const TkSrc s = tk_src(a, row, st);
+    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
+    const uint32_t c0 = bx * g;
+    if (c0 >= nact) return;
+    const uint32_t c1 = c0 + g < nact ? c0 + g : nact;
+    const uint32_t shift = 24u - 8u * (uint32_t)level;
+    const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+    uint32_t acc = 0u;
+    for (uint32_t c = c0; c < c1; ++c) {
+        for (uint32_t i = tid; i < 256u * TK_SLOTS; i += TK_BLOCK) h[i] = 0u;
+        __syncthreads();
+        const uint32_t beg = c * TK_CHUNK, end = beg + TK_CHUNK < s.count ? beg + TK_CHUNK : s.count;
+        const uint32_t mis = tk_mis(s.u, beg), nq = tk_quads(beg, end, mis);
+        for (uint32_t q0 = 0; q0 < nq; q0 += 4u * TK_BLOCK) {
+            uint32_t u[4][4], vm[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const uint32_t q = q0 + (uint32_t)t * TK_BLOCK + tid;
+                int64_t i0;
+                vm[t] = q < nq ? tk_load_quad(s.u, beg, end, mis, q, s.xr, u[t], i0) : 0u;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (((vm[t] >> j) & 1u) && ((u[t][j] ^ st.prefix) & mask) == 0u)
+                        atomicAdd(&h[((u[t][j] >> shift) & 255u) * TK_SLOTS + slot], 1u);
+        }
+        __syncthreads();
+        if (tid < 256u) {
+            uint32_t sum = 0u;
+#pragma unroll 8
+            for (uint32_t q = 0; q < (uint32_t)TK_SLOTS; ++q) sum += h[tid * TK_SLOTS + ((q + tid) & (TK_SLOTS - 1u))];
+            a.cnt[((size_t)row * a.nch + c) * 256u + tid] = sum;
+            acc += sum;
+        }
+        __syncthreads();
+    }
+    if (tid < 256u && acc) atomicAdd(&a.hist[((size_t)row * TK_LEVELS + level) * 256u + tid], acc);
+}
+
+constexpr int TK_RED_WAVES = 4;
+
+__global__ __launch_bounds__(TK_RED_WAVES * WAVE) void k_tk_reduce(TkArgs a, int level, uint32_t nx) {
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    const uint32_t row = blockIdx.x / nx, bx = blockIdx.x - row * nx;
+    const uint32_t chunk = bx * TK_RED_WAVES + wid;
+    const TkState st = tk_state(a, row, level);
+    const TkSrc s = tk_src(a, row, st);
+    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
+    if (chunk >= nact) return;  // (wave-uniform)
+    const TkPick p = tk_pick(a.hist + ((size_t)row * TK_LEVELS + level) * 256u, st.krem, lane);
+    const size_t idx = (size_t)row * a.nch + chunk;
+    const uint4 v = reinterpret_cast<const uint4 *>(a.cnt + idx * 256u)[lane];
+    const uint32_t c[4] = {v.x, v.y, v.z, v.w};
+    uint32_t lo = 0u, e = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t dg = 4u * lane + (uint32_t)j;
+        lo += dg < p.d ? c[j] : 0u;
+        e += dg == p.d ? c[j] : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lo += __shfl_xor(lo, off);
+        e += __shfl_xor(e, off);
+    }
+    if (lane == 0u) {
+        a.low[idx] = (level == 0 || st.jn) ? lo : a.low[idx] + lo;
+        a.eq[idx] = e;
+    }
+}
+
+__global__ __launch_bounds__(TK_BLOCK) void k_tk_scan(TkArgs a, int level) {
+    __shared__ uint32_t wsum[TK_BLOCK / WAVE], tot[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
+    const TkState st = tk_state(a, row, level);
+    const TkSrc s = tk_src(a, row, st);
+    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
+    const TkPick p = tk_pick(a.hist + ((size_t)row * TK_LEVELS + level) * 256u, st.krem, lane);
+    uint32_t carry_lo = 0u, carry_eq = 0u;
+    for (uint32_t b = 0; b < nact; b += TK_BLOCK) {
+        const uint32_t c = b + tid;
+        const size_t idx = (size_t)row * a.nch + c;
+        const uint32_t lo = c < nact ? a.low[idx] : 0u, e = c < nact ? a.eq[idx] : 0u;
+        const uint32_t xl = block_excl_scan<TK_BLOCK, TK_BLOCK>(lo, wsum);
+        __syncthreads();
+        const uint32_t xe = block_excl_scan<TK_BLOCK, TK_BLOCK>(e, wsum);
+        if (c < nact) {
+            a.lowbase[idx] = carry_lo + xl;
+            a.eqbase[idx] = carry_eq + xe;
+        }
+        if (tid == TK_BLOCK - 1u) {
+            tot[0] = xl + lo;
+            tot[1] = xe + e;
+        }
+        __syncthreads();
+        carry_lo += tot[0];
+        carry_eq += tot[1];
+        __syncthreads();
+    }
+    if (tid == 0u) {
+        const bool narrow = !st.narrowed && level < TK_LEVELS - 1 && p.bucket <= a.cap;
+        TkState ns;
+        ns.prefix = st.prefix | (p.d << (24u - 8u * (uint32_t)level));
+        ns.krem = st.krem - p.below;
+        ns.narrowed = (st.narrowed || narrow) ? 1u : 0u;
+        ns.ccount = narrow ? p.bucket : st.ccount;
+        ns.sbase = narrow ? carry_lo : st.sbase;
+        ns.jn = narrow ? 1u : 0u;
+        ns.tlow = carry_lo;
+        ns.pad = 0u;
+        a.st[(size_t)row * (TK_LEVELS + 1) + level + 1] = ns;
+    }
+}
+
+// One ordered pass over a chunk.  FINAL = false (after level `level`, rows with jn set): the keys
+// whose top digits lie below the new prefix go to the survivor list, those that match it to the
+// candidate buffer.  FINAL = true: the keys below the threshold and the first krem keys equal to
+// it go to the survivor list.  Every store is bounds-checked against its list.
+template <bool FINAL>
+__global__ __launch_bounds__(TK_BLOCK) void k_tk_compact(TkArgs a, int level) {
+    __shared__ uint32_t wsum[TK_BLOCK / WAVE], tot;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = blockIdx.x / a.nch, chunk = blockIdx.x - row * a.nch;
+    const TkState ns = a.st[(size_t)row * (TK_LEVELS + 1) + level + 1];
+    if (!FINAL && !ns.jn) return;
+    TkState from = ns;
+    if (!FINAL) from.narrowed = 0u;  // a row narrows once, from the input
+    const TkSrc s = tk_src(a, row, from);
+    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
+    if (chunk >= nact) return;
+    const size_t idx = (size_t)row * a.nch + chunk;
+    const uint32_t eqb = a.eqbase[idx];
+    // (FINAL: nothing of this chunk is taken: no key below the threshold, its equals past the last one taken)
+    if (FINAL && a.low[idx] == 0u && eqb >= ns.krem) return;
+    const uint32_t lob = a.lowbase[idx] + (FINAL ? ns.sbase : 0u);
+    const uint32_t mask = FINAL ? 0xFFFFFFFFu : 0xFFFFFFFFu << (24u - 8u * (uint32_t)level);
+    const uint32_t P = ns.prefix;
+    uint32_t *su = a.surv_u + (size_t)row * a.k, *sp = a.surv_p + (size_t)row * a.k;
+    uint32_t *cu = a.cand_u + (size_t)row * a.capa, *cp = a.cand_p + (size_t)row * a.capa;
+    const uint32_t beg = chunk * TK_CHUNK, end = beg + TK_CHUNK < s.count ? beg + TK_CHUNK : s.count;
+    const uint32_t mis = tk_mis(s.u, beg), nq = tk_quads(beg, end, mis);
+    uint32_t carry_l = 0u, carry_e = 0u;
+    for (uint32_t q0 = 0; q0 < nq; q0 += TK_BLOCK) {
+        const uint32_t q = q0 + tid;
+        uint32_t u[4], pos[4], vm = 0u;
+        int64_t i0 = 0;
+        if (q < nq) vm = tk_load_quad(s.u, beg, end, mis, q, s.xr, u, i0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pos[j] = (uint32_t)(i0 + j);
+        if (s.p) {
+            if (vm == 15u) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(s.p + i0);
+                pos[0] = v.x; pos[1] = v.y; pos[2] = v.z; pos[3] = v.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((vm >> j) & 1u) pos[j] = s.p[i0 + j];
+            }
+        }
+        uint32_t lm = 0u, em = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if ((vm >> j) & 1u) {
+                const uint32_t t = u[j] & mask;
+                lm |= (t < P ? 1u : 0u) << j;
+                em |= (t == P ? 1u : 0u) << j;
+            }
+        // one scan for both counts: a batch holds at most 4096 keys
+        const uint32_t packed = (uint32_t)__popc(lm) | ((uint32_t)__popc(em) << 16);
+        const uint32_t ex = block_excl_scan<TK_BLOCK, TK_BLOCK>(packed, wsum);
+        if (tid == TK_BLOCK - 1u) tot = ex + packed;
+        __syncthreads();
+        uint32_t l = lob + carry_l + (ex & 0xFFFFu), e = eqb + carry_e + (ex >> 16);
+        carry_l += tot & 0xFFFFu;
+        carry_e += tot >> 16;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if ((lm >> j) & 1u) {
+                if (l < a.k) {
+                    su[l] = u[j];
+                    sp[l] = pos[j];
+                }
+                ++l;
+            }
+            if ((em >> j) & 1u) {
+                if (FINAL) {
+                    const uint32_t t = ns.sbase + ns.tlow + e;
+                    if (e < ns.krem && t < a.k) {
+                        su[t] = u[j];
+                        sp[t] = pos[j];
+                    }
+                } else if (e < a.cap) {
+                    cu[e] = u[j];
+                    cp[e] = pos[j];
+                }
+                ++e;
+            }
+        }
+        __syncthreads();  // wsum and tot are reused by the next batch
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tk_prep(const uint32_t *__restrict__ keys, uint32_t *__restrict__ u,
+                                                 uint32_t *__restrict__ pos, size_t n, uint32_t cols, uint32_t xr) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (u) u[i] = keys[i] ^ xr;
+        pos[i] = (uint32_t)i % cols;  // (n <= 2^31 - 1)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tk_offsets(uint32_t *__restrict__ off, uint32_t rows, uint32_t m) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i <= rows; i += stride) off[i] = (uint32_t)i * m;
+}
+
+__global__ void k_tk_err_acc(uint32_t *hdr, const uint32_t *inner, int nw) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        uint32_t e = 0u;
+        for (int i = 0; i < nw; ++i) e |= inner[i];
+        if (e) hdr[0] = 1u;
+    }
+}
+
+// grid: x over the k outputs of a row, rows folded into x as well (row = block / bpr)
+__global__ __launch_bounds__(256) void k_tk_write(const uint32_t *__restrict__ su, const uint32_t *__restrict__ sp,
+                                                  uint32_t *__restrict__ ko, uint32_t *__restrict__ io, uint32_t m,
+                                                  uint32_t k, uint32_t bpr, uint32_t xr) {
+    const uint32_t row = blockIdx.x / bpr, bx = blockIdx.x - row * bpr;
+    const size_t src = (size_t)row * m, dst = (size_t)row * k;
+    for (uint32_t j = bx * 256u + threadIdx.x; j < k; j += bpr * 256u) {
+        ko[dst + j] = su[src + j] ^ xr;
+        if (io) io[dst + j] = sp[src + j];
+    }
+}
+
+unsigned tk_stream_blocks(size_t n) {
+    const size_t b = (n + 256 * 8 - 1) / (256 * 8);
+    return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
+}
+
+}  // namespace
+
+hipError_t launch_topk_hist(const TkArgs &a, size_t rows, int level, hipStream_t s) {
+    const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
+    const uint32_t nx = (a.nch + g - 1u) / g;
+    k_tk_hist<<<(unsigned)(rows * nx), TK_BLOCK, 0, s>>>(a, level, nx, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_reduce(const TkArgs &a, size_t rows, int level, hipStream_t s) {
+    const uint32_t nx = (a.nch + TK_RED_WAVES - 1u) / TK_RED_WAVES;
+    k_tk_reduce<<<(unsigned)(rows * nx), TK_RED_WAVES * WAVE, 0, s>>>(a, level, nx);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_scan(const TkArgs &a, size_t rows, int level, hipStream_t s) {
+    k_tk_scan<<<(unsigned)rows, TK_BLOCK, 0, s>>>(a, level);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_narrow(const TkArgs &a, size_t rows, int level, hipStream_t s) {
+    k_tk_compact<false><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, level);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_final(const TkArgs &a, size_t rows, hipStream_t s) {
+    k_tk_compact<true><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, TK_LEVELS - 1);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_prep(const uint32_t *keys, uint32_t *u, uint32_t *pos, size_t n, size_t cols, uint32_t xr,
+                            hipStream_t s) {
+    k_tk_prep<<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_offsets(uint32_t *off, size_t rows, size_t m, hipStream_t s) {
+    k_tk_offsets<<<tk_stream_blocks(rows + 1), 256, 0, s>>>(off, (uint32_t)rows, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_err_acc(uint32_t *hdr, const uint32_t *inner, int nw, hipStream_t s) {
+    k_tk_err_acc<<<1, 64, 0, s>>>(hdr, inner, nw);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_write(const uint32_t *su, const uint32_t *sp, uint32_t *keys_out, uint32_t *idx_out, size_t rows,
+                             size_t m, size_t k, uint32_t xr, hipStream_t s) {
+    // blocks per row: enough for one key per thread, fewer when there are many rows
+    size_t bpr = (k + 255) / 256;
+    const size_t room = ((size_t)1 << 20) / rows;
+    if (bpr > room) bpr = room ? room : 1;
+    k_tk_write<<<(unsigned)(rows * bpr), 256, 0, s>>>(su, sp, keys_out, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    return hipGetLastError();
+}
+
+}  // namespace labsort

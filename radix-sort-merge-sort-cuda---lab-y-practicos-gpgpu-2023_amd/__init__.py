@@ -480,6 +480,18 @@ def merge_parts(n: int) -> int:
     return int(lib.labsort_merge_parts(n))
 
 
+def _workspace(workspace, nbytes):
+    """(workspace, its size in bytes, own) for a device call.  Without a caller-owned workspace
+    (own), max(nbytes(), 1) bytes are allocated, and the caller synchronises and checks the
+    status itself.  A raw device address counts as nbytes() long."""
+    own = workspace is None
+    if own:
+        import torch
+        workspace = torch.empty(max(nbytes(), 1), dtype=torch.uint8, device="cuda")
+    wsb = workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else nbytes()
+    return workspace, wsb, own
+
+
 def sort_device(d_in, d_out, n: int, key: str = "u32", algo: str = "radix", workspace=None,
                 workspace_bytes_: int | None = None, stream=None) -> None:
     """Sort n keys d_in -> d_out (may alias) asynchronously on `stream`.
@@ -487,12 +499,9 @@ def sort_device(d_in, d_out, n: int, key: str = "u32", algo: str = "radix", work
     With a caller-owned `workspace` the call stays asynchronous; check the kernels'
     own error report with workspace_status() once the result is needed.  Without
     one, the call allocates a workspace, synchronises and checks it itself."""
-    own = workspace is None
-    if own:
-        import torch
-        workspace = torch.empty(max(workspace_bytes(n, algo), 1), dtype=torch.uint8, device="cuda")
-    wsb = workspace_bytes_ if workspace_bytes_ is not None else (
-        workspace.numel() * workspace.element_size() if hasattr(workspace, "numel") else workspace_bytes(n, algo))
+    workspace, wsb, own = _workspace(workspace, lambda: workspace_bytes(n, algo))
+    if workspace_bytes_ is not None:
+        wsb = workspace_bytes_
     _check(lib.labsort_sort_device(_ptr(d_in), _ptr(d_out), n, KEY[key], ALGO[algo], _ptr(workspace), wsb,
                                    _stream(stream)), "sort_device")
     if own:
@@ -558,11 +567,7 @@ def sort_pairs_device(d_keys_in, d_vals_in, d_keys_out, d_vals_out, n: int, key:
                       workspace=None, stream=None) -> None:
     """Stable sort of n (key, 4-byte payload) pairs (sort_by_key); equal keys keep
     their input order.  algo: "radix", "merge" or "auto".  Asynchronous on `stream`."""
-    own = workspace is None
-    if own:
-        import torch
-        workspace = torch.empty(max(pairs_workspace_bytes(n, algo), 1), dtype=torch.uint8, device="cuda")
-    wsb = workspace.numel() * workspace.element_size()
+    workspace, wsb, own = _workspace(workspace, lambda: pairs_workspace_bytes(n, algo))
     _check(lib.labsort_sort_pairs_device(_ptr(d_keys_in), _ptr(d_vals_in), _ptr(d_keys_out), _ptr(d_vals_out), n,
                                          KEY[key], ALGO[algo], _ptr(workspace), wsb, _stream(stream)),
            "sort_pairs_device")
@@ -606,12 +611,7 @@ def sort_segments_device(d_in, d_out, n: int, d_offsets, nseg: int, max_segment_
     the general path).  With a caller-owned `workspace` the call stays asynchronous (check
     segments_workspace_status when the result is needed); without one it allocates, synchronises
     and checks."""
-    own = workspace is None
-    if own:
-        import torch
-        workspace = torch.empty(max(segments_workspace_bytes(n, nseg, max_segment_keys), 1), dtype=torch.uint8,
-                                device="cuda")
-    wsb = workspace.numel() * workspace.element_size()
+    workspace, wsb, own = _workspace(workspace, lambda: segments_workspace_bytes(n, nseg, max_segment_keys))
     _check(lib.labsort_sort_segments_device(_ptr(d_in), _ptr(d_out), n, _ptr(d_offsets), nseg, max_segment_keys,
                                             KEY[key], _ptr(workspace), wsb, _stream(stream)), "sort_segments_device")
     if own:
@@ -621,12 +621,7 @@ def sort_segments_device(d_in, d_out, n: int, d_offsets, nseg: int, max_segment_
 def sort_segments_pairs_device(d_keys_in, d_vals_in, d_keys_out, d_vals_out, n: int, d_offsets, nseg: int,
                                max_segment_keys: int = 0, key: str = "u32", workspace=None, stream=None) -> None:
     """As sort_segments_device for (key, 4-byte payload) pairs; stable within each segment."""
-    own = workspace is None
-    if own:
-        import torch
-        workspace = torch.empty(max(segments_workspace_bytes(n, nseg, max_segment_keys, True), 1), dtype=torch.uint8,
-                                device="cuda")
-    wsb = workspace.numel() * workspace.element_size()
+    workspace, wsb, own = _workspace(workspace, lambda: segments_workspace_bytes(n, nseg, max_segment_keys, True))
     _check(lib.labsort_sort_segments_pairs_device(_ptr(d_keys_in), _ptr(d_vals_in), _ptr(d_keys_out), _ptr(d_vals_out),
                                                   n, _ptr(d_offsets), nseg, max_segment_keys, KEY[key], _ptr(workspace),
                                                   wsb, _stream(stream)), "sort_segments_pairs_device")
@@ -652,11 +647,7 @@ def topk_device(d_keys, rows: int, cols: int, k: int, d_keys_out, d_idx_out=None
     fixed (equal keys in order of position; of the k-th key's ties the lowest positions).  With a
     caller-owned `workspace` the call stays asynchronous (check topk_workspace_status when the
     result is needed); without one it allocates, synchronises and checks."""
-    own = workspace is None
-    if own:
-        import torch
-        workspace = torch.empty(max(topk_workspace_bytes(rows, cols, k), 1), dtype=torch.uint8, device="cuda")
-    wsb = workspace.numel() * workspace.element_size()
+    workspace, wsb, own = _workspace(workspace, lambda: topk_workspace_bytes(rows, cols, k))
     _check(lib.labsort_topk_device(_ptr(d_keys), rows, cols, k, 1 if largest else 0, KEY[key], _ptr(d_keys_out),
                                    None if d_idx_out is None else _ptr(d_idx_out), _ptr(workspace), wsb,
                                    _stream(stream)), "topk_device")

@@ -17,30 +17,13 @@
 #include <mutex>
 #include <vector>
 
-#include "../../include/labsort.h"
-#include "common.h"
-#include "segsort.h"
-#include "topk.h"
+#include "host.h"
 
 using namespace labsort;
 
 namespace {
 
 thread_local int g_last_hip = 0;
-
-int fail_hip(hipError_t e) {
-    g_last_hip = (int)e;
-    return LABSORT_ERR_HIP;
-}
-#define HIP_TRY(x)                                   \
-    do {                                             \
-        hipError_t _e = (x);                         \
-        if (_e != hipSuccess) return fail_hip(_e);   \
-    } while (0)
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline uint32_t flip_of(int key_type) { return key_type == LABSORT_KEY_I32 ? 0x80000000u : 0u; }
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---------------------------------------------------------------------------------
 // timing hooks
@@ -55,22 +38,26 @@ std::vector<TimedLaunch> g_pending;
 double g_total_ms[LABSORT_K_COUNT];
 long long g_launches[LABSORT_K_COUNT];
 
-struct TimingScope {
-    int cls;
-    hipStream_t s;
-    hipEvent_t a = nullptr, b = nullptr;
-    TimingScope(int c, hipStream_t st) : cls(c), s(st) {
-        if (!g_timing_on) return;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
-        (void)hipEventRecord(a, s);
-    }
-    ~TimingScope() {
-        if (!a) return;
-        (void)hipEventRecord(b, s);
-        std::lock_guard<std::mutex> lk(g_timing_mu);
-        g_pending.push_back({cls, a, b});
-    }
-};
+}  // namespace
+
+int labsort::fail_hip(hipError_t e) {
+    g_last_hip = (int)e;
+    return LABSORT_ERR_HIP;
+}
+
+TimingScope::TimingScope(int c, hipStream_t st) : cls(c), s(st) {
+    if (!g_timing_on) return;
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
+    (void)hipEventRecord(a, s);
+}
+TimingScope::~TimingScope() {
+    if (!a) return;
+    (void)hipEventRecord(b, s);
+    std::lock_guard<std::mutex> lk(g_timing_mu);
+    g_pending.push_back({cls, a, b});
+}
+
+namespace {
 
 void timing_collect() {
     std::lock_guard<std::mutex> lk(g_timing_mu);
@@ -106,68 +93,58 @@ RadixLayout radix_layout(size_t n, int bits, size_t tile) {
     L.ntiles = (n + tile - 1) / tile + (bits == 8 ? NSEG : 0);
     // zeroed block: err | hist | segment histograms | counters | lookback.  The device
     // error word is the workspace's first word (labsort_workspace_status reads it).
-    size_t o = 0;
-    L.off_err = o;
-    o += 256;
-    L.off_hist = o;
-    o += (size_t)L.P * L.R * 4;
-    L.off_hps = o;
-    if (bits == 8) o += (size_t)NSEG * 256 * 4;
-    L.off_joint = o;
-    if (bits == 8) o += (size_t)4 * NSEG * 256 * 4;
-    L.off_counter = o;
-    o += (size_t)L.P * OSP_NCTR * 4;
-    o = align_up(o, 256);
-    L.off_lookback = o;
-    o += (size_t)L.P * L.ntiles * L.R * 4;
-    o = align_up(o, 256);
-    L.zero_bytes = o;
-    L.off_plan = o;
-    o = align_up(o + sizeof(Plan), 256);
-    L.off_segplan = o;
-    if (bits == 8) o = align_up(o + 4 * sizeof(SegPlan), 256);
+    // (every region of the zeroed block but the counters is a multiple of 256 bytes)
+    Carver c;
+    L.off_err = c.take(256);
+    L.off_hist = c.take((size_t)L.P * L.R * 4);
+    L.off_hps = c.take(bits == 8 ? (size_t)NSEG * 256 * 4 : 0);
+    L.off_joint = c.take(bits == 8 ? (size_t)4 * NSEG * 256 * 4 : 0);
+    L.off_counter = c.take((size_t)L.P * OSP_NCTR * 4);
+    L.off_lookback = c.take((size_t)L.P * L.ntiles * L.R * 4);
+    L.zero_bytes = c.o;
+    L.off_plan = c.take(sizeof(Plan));
+    L.off_segplan = c.take(bits == 8 ? 4 * sizeof(SegPlan) : 0);
     // the ping-pong key buffer last, 64 KiB aligned (tiles are 64 KiB of keys)
-    L.off_tmp = align_up(o, 65536);
+    L.off_tmp = align_up(c.o, 65536);
     L.total = align_up(L.off_tmp + n * 4, 256);
     return L;
 }
 
-// Merge sort levels after the tile sort: runs of TS_TILE keys doubled until one run.
+// Merge sort levels after the tile sort: runs of `tile` keys (TS_TILE, or TS_TILE_KV pairs)
+// doubled until one run.
 // LABSORT_MERGE4 (build knob, default 1): two levels per four-way pass (merge4.hip), the odd
 // level first as a pairwise pass; 0: pairwise passes only.
 #ifndef LABSORT_MERGE4
 #define LABSORT_MERGE4 1
 #endif
-int merge_levels(size_t n) {
+int merge_levels(size_t n, size_t tile) {
     int m = 0;
-    for (size_t run = TS_TILE; run < n; run *= 2) ++m;
+    for (size_t run = tile; run < n; run *= 2) ++m;
     return m;
 }
+inline size_t merge_tile(bool pairs) { return pairs ? (size_t)TS_TILE_KV : (size_t)TS_TILE; }
 
-// the error word first (labsort_workspace_status reads the workspace's first word, as for
-// the radix layout), then the ping-pong keys, ...
+// The merge sorts' workspace, keys only or key/value.  The error word first (the status
+// functions read the workspace's first word, as for the radix layout), the keys' ping-pong
+// buffer, the payloads' (pairs), then the four-way passes' boundary tables (one at a time)
+// and their two sample buffers, written by the pass before (ping-pong).
 struct MergeLayout {
-    size_t off_err, off_tmp, off_part, off_bnd, off_samp[2], total;
+    size_t off_err, off_tk, off_tv, off_bnd, off_samp[2], total;
 };
-MergeLayout merge_layout(size_t n) {
+MergeLayout merge_layout(size_t n, bool pairs) {
     MergeLayout L{};
-    size_t o = 0;
-    L.off_err = o;
-    o += 256;
-    L.off_tmp = o;
-    o = align_up(o + n * 4, 256);
-    L.off_part = o;
-    o = align_up(o + (labsort_merge_parts(n)) * 4, 256);
-    L.off_bnd = o;
-    size_t bw = 0;  // the four-way passes' boundary tables (one at a time)
+    Carver c;
+    L.off_err = c.take(256);
+    L.off_tk = c.take(n * 4);
+    // keys only: the partition table of earlier merge passes; no kernel reads it, it stays in the public size
+    L.off_tv = c.take((pairs ? n : labsort_merge_parts(n)) * 4);
+    size_t bw = 0;
     if (LABSORT_MERGE4)
-        for (size_t r = (merge_levels(n) % 2 ? 2 : 1) * (size_t)TS_TILE; r < n; r *= 4) bw = std::max(bw, merge4_bnd_words(n, r));
-    o = align_up(o + bw * 4, 256);
-    for (int i = 0; i < 2; ++i) {  // the four-way passes' samples, written by the pass before (ping-pong)
-        L.off_samp[i] = o;
-        if (bw) o = align_up(o + merge4_samp_words(n) * 4, 256);
-    }
-    L.total = o;
+        for (size_t r = (merge_levels(n, merge_tile(pairs)) % 2 ? 2 : 1) * merge_tile(pairs); r < n; r *= 4)
+            bw = std::max(bw, merge4_bnd_words(n, r));
+    L.off_bnd = c.take(bw * 4);
+    for (int i = 0; i < 2; ++i) L.off_samp[i] = c.take(bw ? merge4_samp_words(n) * 4 : 0);
+    L.total = c.o;
     return L;
 }
 
@@ -181,34 +158,57 @@ bool use_gather(size_t n) {
     return !(e && !std::strcmp(e, "onesweep"));
 }
 
-// GsHooks callbacks: the same event pairs as TimingScope
-struct HookCtx {
-    hipEvent_t a = nullptr, b = nullptr;
-};
-void hook_begin(void *ctx, int cls, hipStream_t s) {
-    (void)cls;
-    HookCtx *h = static_cast<HookCtx *>(ctx);
-    h->a = h->b = nullptr;
-    if (!g_timing_on) return;
-    if (hipEventCreate(&h->a) != hipSuccess || hipEventCreate(&h->b) != hipSuccess) {
-        h->a = h->b = nullptr;
-        return;
-    }
-    (void)hipEventRecord(h->a, s);
-}
-void hook_end(void *ctx, int cls, hipStream_t s) {
-    HookCtx *h = static_cast<HookCtx *>(ctx);
-    if (!h->a) return;
-    (void)hipEventRecord(h->b, s);
-    std::lock_guard<std::mutex> lk(g_timing_mu);
-    g_pending.push_back({cls, h->a, h->b});
-    h->a = h->b = nullptr;
-}
-
 bool small_path(size_t n, int algo) { return algo != LABSORT_ALGO_RADIX1 && n <= (size_t)TS_TILE; }
 
-int sort_radix(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, int bits, char *ws, hipStream_t s) {
-    const RadixLayout L = radix_layout(n, bits, bits == 8 ? OSP_TILE : OS_TILE);
+// 8-bit LSD radix of keys (vi == vo == nullptr) or (key, payload) pairs: the keys' segmented
+// histogram and plans, then the persistent onesweep passes, each payload carried with its
+// key (k_onesweep_p<true>), and the final copy under the keys' buffer plan.  The payloads'
+// ping-pong buffer lies behind the radix layout.
+int sort_radix8(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, size_t n, uint32_t flip, char *ws,
+                hipStream_t s) {
+    const RadixLayout L = radix_layout(n, 8, OSP_TILE);
+    Bufs b, vb;
+    b.p[SEL_IN] = const_cast<uint32_t *>(ki);
+    b.p[SEL_OUT] = ko;
+    b.p[SEL_TMP] = reinterpret_cast<uint32_t *>(ws + L.off_tmp);
+    vb.p[SEL_IN] = const_cast<uint32_t *>(vi);
+    vb.p[SEL_OUT] = vo;
+    vb.p[SEL_TMP] = vi ? reinterpret_cast<uint32_t *>(ws + align_up(L.total, 256)) : nullptr;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(ws + L.off_hist);
+    uint32_t *counters = reinterpret_cast<uint32_t *>(ws + L.off_counter);
+    uint32_t *err = reinterpret_cast<uint32_t *>(ws + L.off_err);
+    uint32_t *lookback = reinterpret_cast<uint32_t *>(ws + L.off_lookback);
+    Plan *plan = reinterpret_cast<Plan *>(ws + L.off_plan);
+    // histograms first; the look-back words (tens of MB) are cleared after the
+    // histogram so their dirty lines do not compete with its read of the keys
+    HIP_TRY(launch_zero(ws, L.off_lookback, s));
+    uint32_t *hps = reinterpret_cast<uint32_t *>(ws + L.off_hps);
+    uint32_t *joint = reinterpret_cast<uint32_t *>(ws + L.off_joint);
+    SegPlan *sps = reinterpret_cast<SegPlan *>(ws + L.off_segplan);
+    {
+        TimingScope ts(LABSORT_K_HISTOGRAM, s);
+        HIP_TRY(launch_hist_seg(ki, n, flip, hps, joint, s));
+    }
+    // the look-back clear rides in the plan launch (k_plan8's workgroups 1..)
+    HIP_TRY(launch_plan8(hps, joint, n, ki == ko ? 1 : 0, plan, sps, hist, ws + L.off_lookback,
+                         L.zero_bytes - L.off_lookback, s));
+    for (int p = 0; p < L.P; ++p) {
+        TimingScope ts(LABSORT_K_ONESWEEP, s);
+        HIP_TRY(launch_onesweep_p(b, plan, p, n, flip, sps + p, lookback + (size_t)p * L.ntiles * L.R,
+                                  counters + (size_t)p * OSP_NCTR, err, s, vi ? &vb : nullptr));
+    }
+    // pass 0's launch copies an input whose every digit is constant (IN -> OUT), so only an
+    // in-place sort (its odd pass count ends in TMP) needs the final copy launches
+    if (ki == ko) {
+        HIP_TRY(launch_final_copy(b, plan, n, s));
+        if (vi) HIP_TRY(launch_final_copy(vb, plan, n, s));
+    }
+    return LABSORT_OK;
+}
+
+// LABSORT_ALGO_RADIX1: the reference's 1-bit passes (non-persistent k_onesweep)
+int sort_radix1(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, char *ws, hipStream_t s) {
+    const RadixLayout L = radix_layout(n, 1, OS_TILE);
     Bufs b;
     b.p[SEL_IN] = const_cast<uint32_t *>(in);
     b.p[SEL_OUT] = out;
@@ -218,85 +218,68 @@ int sort_radix(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, int b
     uint32_t *err = reinterpret_cast<uint32_t *>(ws + L.off_err);
     uint32_t *lookback = reinterpret_cast<uint32_t *>(ws + L.off_lookback);
     Plan *plan = reinterpret_cast<Plan *>(ws + L.off_plan);
-    if (bits == 8) {
-        // histograms first; the look-back words (tens of MB) are cleared after the
-        // histogram so their dirty lines do not compete with its read of the keys
-        HIP_TRY(launch_zero(ws, L.off_lookback, s));
-        uint32_t *hps = reinterpret_cast<uint32_t *>(ws + L.off_hps);
-        uint32_t *joint = reinterpret_cast<uint32_t *>(ws + L.off_joint);
-        SegPlan *sps = reinterpret_cast<SegPlan *>(ws + L.off_segplan);
-        {
-            TimingScope ts(LABSORT_K_HISTOGRAM, s);
-            HIP_TRY(launch_hist_seg(in, n, flip, hps, joint, s));
-        }
-        // the look-back clear rides in the plan launch (k_plan8's workgroups 1..)
-        HIP_TRY(launch_plan8(hps, joint, n, in == out ? 1 : 0, plan, sps, hist, ws + L.off_lookback,
-                             L.zero_bytes - L.off_lookback, s));
-        for (int p = 0; p < L.P; ++p) {
-            TimingScope ts(LABSORT_K_ONESWEEP, s);
-            HIP_TRY(launch_onesweep_p(b, plan, p, n, flip, sps + p, lookback + (size_t)p * L.ntiles * L.R,
-                                      counters + (size_t)p * OSP_NCTR, err, s));
-        }
-    } else {
-        HIP_TRY(launch_zero(ws, L.zero_bytes, s));
-        {
-            TimingScope ts(LABSORT_K_HISTOGRAM, s);
-            HIP_TRY(launch_histogram(in, n, flip, bits, hist, s));
-        }
-        HIP_TRY(launch_plan(hist, n, bits, in == out ? 1 : 0, plan, s));
-        for (int p = 0; p < L.P; ++p) {
-            TimingScope ts(LABSORT_K_ONESWEEP, s);
-            HIP_TRY(launch_onesweep(b, plan, p, bits, n, flip, hist, lookback + (size_t)p * L.ntiles * L.R,
-                                    counters + (size_t)p * OSP_NCTR, err, s));
-        }
+    HIP_TRY(launch_zero(ws, L.zero_bytes, s));
+    {
+        TimingScope ts(LABSORT_K_HISTOGRAM, s);
+        HIP_TRY(launch_histogram(in, n, flip, 1, hist, s));
     }
-    // 8-bit: pass 0's launch copies an input whose every digit is constant (IN -> OUT), so
-    // only an in-place sort (its odd pass count ends in TMP) needs the final copy launch
-    if (bits != 8 || in == out) HIP_TRY(launch_final_copy(b, plan, n, s));
+    HIP_TRY(launch_plan(hist, n, 1, in == out ? 1 : 0, plan, s));
+    for (int p = 0; p < L.P; ++p) {
+        TimingScope ts(LABSORT_K_ONESWEEP, s);
+        HIP_TRY(launch_onesweep(b, plan, p, 1, n, flip, hist, lookback + (size_t)p * L.ntiles * L.R,
+                                counters + (size_t)p * OSP_NCTR, err, s));
+    }
+    HIP_TRY(launch_final_copy(b, plan, n, s));
     return LABSORT_OK;
 }
 
-// Merge passes after the tile sort (runs of TS_TILE keys): four-way passes (two levels per
-// HBM read and write, merge4.hip) and, for an odd level count, one pairwise merge-path pass
-// first.  (An earlier K-way pass, LDS merges with binary searches per key, measured slower
-// than pairwise passes: 9.7-14 vs 7.9 ms)
-int sort_merge(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, char *ws, hipStream_t s) {
-    const MergeLayout L = merge_layout(n);
+// Merge sort of keys (vi == vo == nullptr) or (key, payload) pairs.  The tile sort leaves
+// runs of TS_TILE keys (TS_TILE_KV pairs); then four-way passes (two levels per HBM read and
+// write, merge4.hip) and, for an odd level count, one pairwise merge-path pass first,
+// ping-pong between out and the workspace: the tile sort writes where the pass count makes
+// the last pass land in out.  (An earlier K-way pass, LDS merges with binary searches per
+// key, measured slower than pairwise passes: 9.7-14 vs 7.9 ms)
+int sort_merge(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, size_t n, uint32_t flip, char *ws,
+               hipStream_t s) {
+    const bool pairs = vi != nullptr;
+    const MergeLayout L = merge_layout(n, pairs);
     uint32_t *err = reinterpret_cast<uint32_t *>(ws + L.off_err);
     HIP_TRY(launch_zero(err, 16, s));  // (a kernel: graph-replayable)
-    uint32_t *tmp = reinterpret_cast<uint32_t *>(ws + L.off_tmp);
-    uint32_t *part = reinterpret_cast<uint32_t *>(ws + L.off_part);
+    uint32_t *tk = reinterpret_cast<uint32_t *>(ws + L.off_tk);
+    uint32_t *tv = pairs ? reinterpret_cast<uint32_t *>(ws + L.off_tv) : nullptr;
     uint32_t *bnd = reinterpret_cast<uint32_t *>(ws + L.off_bnd);
-    const int m = merge_levels(n);
-    const bool four = LABSORT_MERGE4 && (((uintptr_t)out | (uintptr_t)tmp) & 15u) == 0;
+    const int m = merge_levels(n, merge_tile(pairs));
+    const bool four = LABSORT_MERGE4 && (((uintptr_t)ko | (uintptr_t)vo | (uintptr_t)tk | (uintptr_t)tv) & 15u) == 0;
     const int npass = four ? m / 2 + m % 2 : m;
-    uint32_t *cur = (npass % 2 == 0) ? out : tmp;
+    uint32_t *ck = (npass % 2 == 0) ? ko : tk, *cv = (npass % 2 == 0) ? vo : tv;
     // samples for a four-way pass are written by the pass before it (samp[0], samp[1] in turn)
     uint32_t *samp[2] = {reinterpret_cast<uint32_t *>(ws + L.off_samp[0]), reinterpret_cast<uint32_t *>(ws + L.off_samp[1])};
     int sb = 0;
     auto next_is_four = [&](int lv) { return four && lv < m && (m - lv) % 2 == 0; };
     {
         TimingScope ts(LABSORT_K_TILE_SORT, s);
-        HIP_TRY(launch_tile_sort(in, cur, n, flip, s, next_is_four(0) ? samp[sb] : nullptr));
+        uint32_t *so = next_is_four(0) ? samp[sb] : nullptr;
+        HIP_TRY(pairs ? launch_tile_sort_kv(ki, ck, vi, cv, n, flip, s, so) : launch_tile_sort(ki, ck, n, flip, s, so));
     }
-    size_t run = TS_TILE;
+    size_t run = merge_tile(pairs);
     for (int lv = 0; lv < m;) {
-        uint32_t *nxt = (cur == out) ? tmp : out;
+        uint32_t *nk = (ck == ko) ? tk : ko, *nv = (ck == ko) ? tv : vo;
         if (next_is_four(lv)) {
             TimingScope ts(LABSORT_K_MERGE4, s);
-            HIP_TRY(launch_merge4_pass(cur, nxt, n, run, flip, bnd, samp[sb], next_is_four(lv + 2) ? samp[sb ^ 1] : nullptr,
-                                       s, nullptr, nullptr, err));
+            HIP_TRY(launch_merge4_pass(ck, nk, n, run, flip, bnd, samp[sb], next_is_four(lv + 2) ? samp[sb ^ 1] : nullptr,
+                                       s, cv, nv, err));
             sb ^= 1;
             run *= 4;
             lv += 2;
         } else {
             TimingScope ts(LABSORT_K_MERGE, s);
-            HIP_TRY(launch_merge_pass(cur, nxt, n, run, flip, part, s, nullptr, nullptr, nullptr,
+            HIP_TRY(launch_merge_pass(ck, nk, n, run, flip, nullptr, s, cv, nv, nullptr,
                                       next_is_four(lv + 1) ? samp[sb] : nullptr));
             run *= 2;
             lv += 1;
         }
-        cur = nxt;
+        ck = nk;
+        cv = nv;
     }
     return LABSORT_OK;
 }
@@ -472,7 +455,7 @@ size_t labsort_workspace_bytes(size_t n, int algo) {
     // caller's workspace was sized for the other one)
     case LABSORT_ALGO_RADIX: return radix_ws_bytes(n);
     case LABSORT_ALGO_RADIX1: return radix_layout(n, 1, OS_TILE).total;
-    case LABSORT_ALGO_MERGE: return merge_layout(n).total;
+    case LABSORT_ALGO_MERGE: return merge_layout(n, false).total;
     default: return 0;
     }
 }
@@ -481,7 +464,7 @@ int labsort_sort_device(const void *d_in, void *d_out, size_t n, int key_type, i
                         size_t ws_bytes, void *stream) {
     if (n == 0) return LABSORT_OK;
     if (!d_in || !d_out) return LABSORT_ERR_ARG;
-    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
+    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (algo != LABSORT_ALGO_RADIX && algo != LABSORT_ALGO_MERGE && algo != LABSORT_ALGO_RADIX1 &&
         algo != LABSORT_ALGO_AUTO)
         return LABSORT_ERR_ARG;
@@ -498,37 +481,35 @@ int labsort_sort_device(const void *d_in, void *d_out, size_t n, int key_type, i
         return LABSORT_OK;
     }
     char *ws = static_cast<char *>(d_ws);
-    if (algo == LABSORT_ALGO_MERGE) return sort_merge(in, out, n, flip, ws, s);
-    if (algo == LABSORT_ALGO_RADIX && use_gather(n)) {
-        HookCtx hc;
-        HIP_TRY(launch_gsweep_sort(in, out, n, flip, ws, s, GsHooks{&hc, hook_begin, hook_end}));
+    if (algo == LABSORT_ALGO_MERGE) return sort_merge(in, nullptr, out, nullptr, n, flip, ws, s);
+    if (algo == LABSORT_ALGO_RADIX1) return sort_radix1(in, out, n, flip, ws, s);
+    if (use_gather(n)) {
+        HIP_TRY(launch_gsweep_sort(in, out, n, flip, ws, s));
         return LABSORT_OK;
     }
-    return sort_radix(in, out, n, flip, algo == LABSORT_ALGO_RADIX1 ? 1 : 8, ws, s);
+    return sort_radix8(in, nullptr, out, nullptr, n, flip, ws, s);
 }
 
 namespace {
 // Synchronise the stream, then read the device error word (the workspace's first
 // word) when the sort that used the workspace had one (radix and merge layouts beyond one tile).
 int read_status(const void *d_ws, bool has_err_word, hipStream_t s) {
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!has_err_word) return LABSORT_OK;
-    if (!d_ws) return LABSORT_ERR_ARG;
+    if (!has_err_word) {
+        HIP_TRY(hipStreamSynchronize(s));
+        return LABSORT_OK;
+    }
     uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, d_ws, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (const int st = read_ws_words(d_ws, &err, 1, s)) return st;
     return err ? LABSORT_ERR_DEVICE : LABSORT_OK;
 }
 }  // namespace
 
 int labsort_workspace_status(const void *d_ws, size_t n, int algo, void *stream) {
-    if (n == 0) return read_status(d_ws, false, as_stream(stream));
-    algo = resolve_algo(algo, n);
-    return read_status(d_ws, !small_path(n, algo), as_stream(stream));
+    return read_status(d_ws, n != 0 && !small_path(n, resolve_algo(algo, n)), as_stream(stream));
 }
 
 int labsort_pairs_workspace_status(const void *d_ws, size_t n, int algo, void *stream) {
-    algo = resolve_pairs_algo(algo, n);
+    (void)algo;  // every key/value layout beyond one tile keeps the error word first
     return read_status(d_ws, n > (size_t)TS_TILE_KV, as_stream(stream));
 }
 
@@ -630,7 +611,7 @@ int labsort_sort_host(void *h_keys, size_t n, int key_type, int algo) {
     if (n == 0) return LABSORT_OK;
     if (!h_keys) return LABSORT_ERR_ARG;
     if (n > labsort_max_keys(algo)) return LABSORT_ERR_ARG;
-    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
+    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
     const int requested = algo;  // AUTO is resolved again per chunk by the pipeline
     algo = resolve_algo(algo, n);
     std::lock_guard<std::mutex> lk(g_host_mu);
@@ -699,7 +680,7 @@ int labsort_merge_runs(const void *d_in, void *d_out, const size_t *h_offsets, i
     for (int q = 0; q < nruns; ++q)
         if (h_offsets[q + 1] < h_offsets[q]) return LABSORT_ERR_ARG;
     if (h_offsets[nruns] > 0xFFFFFFFFu || n > 0x7FFFFFFFu) return LABSORT_ERR_ARG;
-    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
+    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (n == 0) return LABSORT_OK;
     if (!d_in || !d_out || d_in == d_out) return LABSORT_ERR_ARG;
     if (!d_ws || ws_bytes < labsort_merge_runs_workspace_bytes(h_offsets[nruns])) return LABSORT_ERR_ARG;
@@ -709,142 +690,61 @@ int labsort_merge_runs(const void *d_in, void *d_out, const size_t *h_offsets, i
                                static_cast<const uint32_t *>(d_in) + h_offsets[0], n * 4, hipMemcpyDeviceToDevice, s));
         return LABSORT_OK;
     }
-        // log2(nruns) levels of pairwise merge-path passes over explicit pairs of runs
-        // (k_merge_pass_p, one launch per pair), ping-ponging through the workspace so
-        // that the last level writes d_out
-        const uint32_t *src = static_cast<const uint32_t *>(d_in) + h_offsets[0];
-        uint32_t *outp = static_cast<uint32_t *>(d_out) + h_offsets[0];
-        uint32_t *tmp = static_cast<uint32_t *>(d_ws);
-        std::vector<size_t> o(h_offsets, h_offsets + nruns + 1);
-        for (auto &x : o) x -= h_offsets[0];
-        int levels = 0;
-        while ((1 << levels) < nruns) ++levels;
-        const uint32_t flip = flip_of(key_type);
-        TimingScope ts(LABSORT_K_MERGE, s);
-        for (int l = 0; l < levels; ++l) {
-            uint32_t *dst = ((levels - 1 - l) % 2 == 0) ? outp : tmp;
-            std::vector<size_t> no;
-            for (size_t i = 0; i + 1 < o.size(); i += 2) {
-                const size_t a0 = o[i], a1 = o[i + 1], b1 = i + 2 < o.size() ? o[i + 2] : a1;
-                no.push_back(a0);
-                if (b1 == a1) {  // no partner: carried over
-                    if (a1 > a0) HIP_TRY(hipMemcpyAsync(dst + a0, src + a0, (a1 - a0) * 4, hipMemcpyDeviceToDevice, s));
-                    continue;
-                }
-                MgPairs pr{};
-                pr.np = 1;
-                pr.pb[0] = 0;
-                pr.pb[1] = (uint32_t)(b1 - a0);
-                pr.la[0] = (uint32_t)(a1 - a0);
-                HIP_TRY(launch_merge_pass(src + a0, dst + a0, b1 - a0, 0, flip, nullptr, s, nullptr, nullptr, &pr));
+    // log2(nruns) levels of pairwise merge-path passes over explicit pairs of runs
+    // (k_merge_pass_p, one launch per pair), ping-ponging through the workspace so
+    // that the last level writes d_out
+    const uint32_t *src = static_cast<const uint32_t *>(d_in) + h_offsets[0];
+    uint32_t *outp = static_cast<uint32_t *>(d_out) + h_offsets[0];
+    uint32_t *tmp = static_cast<uint32_t *>(d_ws);
+    std::vector<size_t> o(h_offsets, h_offsets + nruns + 1);
+    for (auto &x : o) x -= h_offsets[0];
+    int levels = 0;
+    while ((1 << levels) < nruns) ++levels;
+    const uint32_t flip = flip_of(key_type);
+    TimingScope ts(LABSORT_K_MERGE, s);
+    for (int l = 0; l < levels; ++l) {
+        uint32_t *dst = ((levels - 1 - l) % 2 == 0) ? outp : tmp;
+        std::vector<size_t> no;
+        for (size_t i = 0; i + 1 < o.size(); i += 2) {
+            const size_t a0 = o[i], a1 = o[i + 1], b1 = i + 2 < o.size() ? o[i + 2] : a1;
+            no.push_back(a0);
+            if (b1 == a1) {  // no partner: carried over
+                if (a1 > a0) HIP_TRY(hipMemcpyAsync(dst + a0, src + a0, (a1 - a0) * 4, hipMemcpyDeviceToDevice, s));
+                continue;
             }
-            no.push_back(o.back());
-            o.swap(no);
-            src = dst;
+            MgPairs pr{};
+            pr.np = 1;
+            pr.pb[0] = 0;
+            pr.pb[1] = (uint32_t)(b1 - a0);
+            pr.la[0] = (uint32_t)(a1 - a0);
+            HIP_TRY(launch_merge_pass(src + a0, dst + a0, b1 - a0, 0, flip, nullptr, s, nullptr, nullptr, &pr));
         }
-        return LABSORT_OK;
+        no.push_back(o.back());
+        o.swap(no);
+        src = dst;
+    }
+    return LABSORT_OK;
 }
 
 size_t labsort_pair_tile_keys(void) { return (size_t)TS_TILE_KV; }
 
-namespace {
-// key/value merge sort: levels above the TS_TILE_KV-pair tiles, and its workspace: the keys'
-// and payloads' ping-pong buffers, then (LABSORT_MERGE4) the four-way passes' boundary
-// tables and the two sample buffers
-int pairs_merge_levels(size_t n) {
-    int m = 0;
-    for (size_t run = TS_TILE_KV; run < n; run *= 2) ++m;
-    return m;
-}
-struct PairsMergeLayout {
-    size_t off_err, off_tk, off_tv, off_bnd, off_samp[2], total;
-};
-PairsMergeLayout pairs_merge_layout(size_t n) {
-    PairsMergeLayout L{};
-    size_t o = 0;
-    L.off_err = o;  // (first word: labsort_pairs_workspace_status)
-    o += 256;
-    L.off_tk = o;
-    o = align_up(o + n * 4, 256);
-    L.off_tv = o;
-    o = align_up(o + n * 4, 256);
-    L.off_bnd = o;
-    size_t bw = 0;
-    if (LABSORT_MERGE4)
-        for (size_t r = (pairs_merge_levels(n) % 2 ? 2 : 1) * (size_t)TS_TILE_KV; r < n; r *= 4)
-            bw = std::max(bw, merge4_bnd_words(n, r));
-    o = align_up(o + bw * 4, 256);
-    for (int i = 0; i < 2; ++i) {
-        L.off_samp[i] = o;
-        if (bw) o = align_up(o + merge4_samp_words(n) * 4, 256);
-    }
-    L.total = o;
-    return L;
-}
-}  // namespace
-
 size_t labsort_pairs_workspace_bytes(size_t n, int algo) {
     if (n <= (size_t)TS_TILE_KV) return 256;
     algo = resolve_pairs_algo(algo, n);
-    if (algo == LABSORT_ALGO_MERGE) return pairs_merge_layout(n).total;  // ping-pong keys | payloads | four-way tables
+    if (algo == LABSORT_ALGO_MERGE) return merge_layout(n, true).total;
     // radix workspace | payload ping-pong
     return align_up(radix_layout(n, 8, OSP_TILE).total, 256) + align_up(n * 4, 256);
 }
-
-namespace {
-// 8-bit LSD radix of (key, payload) pairs: the keys' segmented histogram and plans,
-// then the persistent onesweep passes carrying each payload with its key
-// (k_onesweep_p<true>), the final copy of keys and payloads under the same buffer plan.
-int sort_pairs_radix(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, size_t n, uint32_t flip,
-                     char *ws, hipStream_t s) {
-    const RadixLayout L = radix_layout(n, 8, OSP_TILE);
-    Bufs b, vb;
-    b.p[SEL_IN] = const_cast<uint32_t *>(ki);
-    b.p[SEL_OUT] = ko;
-    b.p[SEL_TMP] = reinterpret_cast<uint32_t *>(ws + L.off_tmp);
-    vb.p[SEL_IN] = const_cast<uint32_t *>(vi);
-    vb.p[SEL_OUT] = vo;
-    vb.p[SEL_TMP] = reinterpret_cast<uint32_t *>(ws + align_up(L.total, 256));
-    uint32_t *hist = reinterpret_cast<uint32_t *>(ws + L.off_hist);
-    uint32_t *counters = reinterpret_cast<uint32_t *>(ws + L.off_counter);
-    uint32_t *err = reinterpret_cast<uint32_t *>(ws + L.off_err);
-    uint32_t *lookback = reinterpret_cast<uint32_t *>(ws + L.off_lookback);
-    Plan *plan = reinterpret_cast<Plan *>(ws + L.off_plan);
-    HIP_TRY(launch_zero(ws, L.off_lookback, s));
-    uint32_t *hps = reinterpret_cast<uint32_t *>(ws + L.off_hps);
-    uint32_t *joint = reinterpret_cast<uint32_t *>(ws + L.off_joint);
-    SegPlan *sps = reinterpret_cast<SegPlan *>(ws + L.off_segplan);
-    {
-        TimingScope ts(LABSORT_K_HISTOGRAM, s);
-        HIP_TRY(launch_hist_seg(ki, n, flip, hps, joint, s));
-    }
-    HIP_TRY(launch_plan8(hps, joint, n, ki == ko ? 1 : 0, plan, sps, hist, ws + L.off_lookback,
-                         L.zero_bytes - L.off_lookback, s));
-    for (int p = 0; p < L.P; ++p) {
-        TimingScope ts(LABSORT_K_ONESWEEP, s);
-        HIP_TRY(launch_onesweep_p(b, plan, p, n, flip, sps + p, lookback + (size_t)p * L.ntiles * L.R,
-                                  counters + (size_t)p * OSP_NCTR, err, s, &vb));
-    }
-    if (ki == ko) {  // (out of place: pass 0's launch copies an all-constant input)
-        HIP_TRY(launch_final_copy(b, plan, n, s));
-        HIP_TRY(launch_final_copy(vb, plan, n, s));
-    }
-    return LABSORT_OK;
-}
-}  // namespace
 
 int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void *d_keys_out, void *d_vals_out,
                               size_t n, int key_type, int algo, void *d_ws, size_t ws_bytes, void *stream) {
     if (n == 0) return LABSORT_OK;
     if (!d_keys_in || !d_vals_in || !d_keys_out || !d_vals_out) return LABSORT_ERR_ARG;
-    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
+    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (algo != LABSORT_ALGO_RADIX && algo != LABSORT_ALGO_MERGE && algo != LABSORT_ALGO_AUTO) return LABSORT_ERR_ARG;
     algo = resolve_pairs_algo(algo, n);
     if (n > (algo == LABSORT_ALGO_MERGE ? (size_t)0x7FFFFFFFu : RADIX_MAX_N)) return LABSORT_ERR_ARG;
-    // in place only as a whole: one side aliased and the other not would read
-    // payloads that the key side's passes already overwrote
-    if ((d_keys_in == d_keys_out) != (d_vals_in == d_vals_out)) return LABSORT_ERR_ARG;
-    if (d_keys_out == d_vals_out) return LABSORT_ERR_ARG;
+    if (!pairs_alias_ok(d_keys_in, d_vals_in, d_keys_out, d_vals_out)) return LABSORT_ERR_ARG;
     if (!d_ws || ws_bytes < labsort_pairs_workspace_bytes(n, algo)) return LABSORT_ERR_ARG;
     const uint32_t flip = flip_of(key_type);
     hipStream_t s = as_stream(stream);
@@ -855,410 +755,8 @@ int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void
         HIP_TRY(launch_tile_sort_kv(ki, ko, vi, vo, n, flip, s));
         return LABSORT_OK;
     }
-    if (algo == LABSORT_ALGO_RADIX) return sort_pairs_radix(ki, vi, ko, vo, n, flip, static_cast<char *>(d_ws), s);
-    // merge passes over runs of TS_TILE_KV pairs, ping-pong between out and the workspace:
-    // four-way passes carrying the payloads (k_m4_merge_kv) and, for an odd level count,
-    // one pairwise pass first (as sort_merge); the tile sort writes where the pass count
-    // makes the last pass land in out
-    const PairsMergeLayout L = pairs_merge_layout(n);
     char *ws = static_cast<char *>(d_ws);
-    uint32_t *tk = reinterpret_cast<uint32_t *>(ws + L.off_tk), *tv = reinterpret_cast<uint32_t *>(ws + L.off_tv);
-    uint32_t *bnd = reinterpret_cast<uint32_t *>(ws + L.off_bnd);
-    uint32_t *samp[2] = {reinterpret_cast<uint32_t *>(ws + L.off_samp[0]), reinterpret_cast<uint32_t *>(ws + L.off_samp[1])};
-    uint32_t *err = reinterpret_cast<uint32_t *>(ws + L.off_err);
-    HIP_TRY(launch_zero(err, 16, s));  // (a kernel: graph-replayable)
-    const int m = pairs_merge_levels(n);
-    const bool four = LABSORT_MERGE4 && (((uintptr_t)ko | (uintptr_t)vo | (uintptr_t)tk | (uintptr_t)tv) & 15u) == 0;
-    const int npass = four ? m / 2 + m % 2 : m;
-    uint32_t *ck = (npass % 2 == 0) ? ko : tk, *cv = (npass % 2 == 0) ? vo : tv;
-    int sb = 0;
-    auto next_is_four = [&](int lv) { return four && lv < m && (m - lv) % 2 == 0; };
-    {
-        TimingScope ts(LABSORT_K_TILE_SORT, s);
-        HIP_TRY(launch_tile_sort_kv(ki, ck, vi, cv, n, flip, s, next_is_four(0) ? samp[sb] : nullptr));
-    }
-    size_t run = TS_TILE_KV;
-    for (int lv = 0; lv < m;) {
-        uint32_t *nk = (ck == ko) ? tk : ko, *nv = (cv == vo) ? tv : vo;
-        if (next_is_four(lv)) {
-            TimingScope ts(LABSORT_K_MERGE4, s);
-            HIP_TRY(launch_merge4_pass(ck, nk, n, run, flip, bnd, samp[sb], next_is_four(lv + 2) ? samp[sb ^ 1] : nullptr,
-                                       s, cv, nv, err));
-            sb ^= 1;
-            run *= 4;
-            lv += 2;
-        } else {
-            TimingScope ts(LABSORT_K_MERGE, s);
-            HIP_TRY(launch_merge_pass(ck, nk, n, run, flip, nullptr, s, cv, nv, nullptr,
-                                      next_is_four(lv + 1) ? samp[sb] : nullptr));
-            run *= 2;
-            lv += 1;
-        }
-        ck = nk;
-        cv = nv;
-    }
-    return LABSORT_OK;
-}
-
-// ---------------------------------------------------------------------------------
-// segmented sort (segsort.hip): segment i = [d_offsets[i], d_offsets[i+1])
-// ---------------------------------------------------------------------------------
-size_t labsort_segment_tile_keys(void) { return (size_t)SEG_TILE_KEYS; }
-size_t labsort_segment_pair_tile_keys(void) { return (size_t)SEG_TILE_PAIRS; }
-
-int labsort_segment_class_edges(int pairs, size_t *edges, int cap) {
-    const size_t e[SEG_CLASSES] = {(size_t)SEG_WAVE_KEYS, (size_t)SEG_WAVE2_KEYS, (size_t)SEG_WAVE3_KEYS, (size_t)SEG_BLOCK_KEYS,
-                                   pairs ? (size_t)SEG_TILE_PAIRS : (size_t)SEG_TILE_KEYS};
-    for (int i = 0; i < SEG_CLASSES && i < cap && edges; ++i) edges[i] = e[i];
-    return SEG_CLASSES;
-}
-
-namespace {
-bool seg_lds_path(size_t max_len, int pairs) {
-    return max_len > 0 && max_len <= (pairs ? (size_t)SEG_TILE_PAIRS : (size_t)SEG_TILE_KEYS);
-}
-// LDS path: header | one list of nseg words per class.
-// General path: header | three n-word buffers | the inner pair sorts' workspace.
-struct SegLayout {
-    size_t off_lists, list_stride;    // LDS path (stride in words)
-    size_t off_a, off_b, off_c, off_inner, inner_bytes;  // general path
-    size_t total;
-};
-// the inner pair sort runs LABSORT_ALGO_AUTO; sized so the function never shrinks as n grows
-// across AUTO's merge -> radix switch
-size_t seg_inner_bytes(size_t n) {
-    const size_t m = n < (size_t)LABSORT_AUTO_PAIRS_MERGE_MAX_KEYS ? n : (size_t)LABSORT_AUTO_PAIRS_MERGE_MAX_KEYS;
-    return std::max(labsort_pairs_workspace_bytes(n, LABSORT_ALGO_AUTO), labsort_pairs_workspace_bytes(m, LABSORT_ALGO_MERGE));
-}
-SegLayout seg_layout(size_t n, size_t nseg, bool lds) {
-    SegLayout L{};
-    size_t o = SEG_HDR_BYTES;
-    if (lds) {
-        L.list_stride = align_up(nseg * 4, 256) / 4;
-        L.off_lists = o;
-        o += (size_t)SEG_CLASSES * L.list_stride * 4;
-    } else {
-        L.off_a = o;
-        o = align_up(o + n * 4, 256);
-        L.off_b = o;
-        o = align_up(o + n * 4, 256);
-        L.off_c = o;
-        o = align_up(o + n * 4, 256);
-        L.off_inner = o;
-        L.inner_bytes = seg_inner_bytes(n);
-        o += L.inner_bytes;
-    }
-    L.total = o;
-    return L;
-}
-
-int sort_segments(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, size_t n, const uint32_t *off,
-                  size_t nseg, size_t max_len, int key_type, void *d_ws, size_t ws_bytes, void *stream) {
-    const bool pairs = vi != nullptr || vo != nullptr;
-    if (n == 0) return LABSORT_OK;
-    if (!ki || !ko || !off || (pairs && (!vi || !vo))) return LABSORT_ERR_ARG;
-    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
-    if (nseg == 0 || n > (size_t)0x7FFFFFFFu || nseg > (size_t)0x7FFFFFFFu) return LABSORT_ERR_ARG;
-    if (pairs) {  // the aliasing rules of labsort_sort_pairs_device
-        if ((ki == ko) != (vi == vo)) return LABSORT_ERR_ARG;
-        if (ko == vo) return LABSORT_ERR_ARG;
-    }
-    const bool lds = seg_lds_path(max_len, pairs ? 1 : 0);
-    if (!lds && n > RADIX_MAX_N) return LABSORT_ERR_ARG;
-    if (!d_ws || ws_bytes < labsort_segments_workspace_bytes(n, nseg, max_len, pairs ? 1 : 0)) return LABSORT_ERR_ARG;
-    const SegLayout L = seg_layout(n, nseg, lds);
-    const uint32_t flip = flip_of(key_type);
-    hipStream_t s = as_stream(stream);
-    char *ws = static_cast<char *>(d_ws);
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(ws);
-    const bool inplace = ki == ko;
-    HIP_TRY(launch_zero(hdr, SEG_HDR_BYTES, s));  // (a kernel: graph-replayable)
-    if (lds) {
-        uint32_t *lists = reinterpret_cast<uint32_t *>(ws + L.off_lists);
-        TimingScope ts(LABSORT_K_SEGSORT, s);
-        HIP_TRY(launch_seg_bin(off, nseg, n, max_len, pairs, !inplace, hdr, lists, L.list_stride, s));
-        // the classes max_len admits (host arguments only: the launch sequence is fixed)
-        size_t edges[SEG_CLASSES];
-        labsort_segment_class_edges(pairs ? 1 : 0, edges, SEG_CLASSES);
-        int ncls = 1;
-        while (ncls < SEG_CLASSES && max_len > edges[ncls - 1]) ++ncls;
-        for (int c = 0; c < ncls; ++c)
-            HIP_TRY(launch_seg_sort(c, ki, ko, vi, vo, off, hdr, lists + (size_t)c * L.list_stride, flip, s));
-        return LABSORT_OK;
-    }
-    // general path: two stable pair sorts (by key, then by segment id) on workspace buffers;
-    // the caller's output is written by the last, guarded, kernel only
-    uint32_t *A = reinterpret_cast<uint32_t *>(ws + L.off_a), *B = reinterpret_cast<uint32_t *>(ws + L.off_b),
-             *C = reinterpret_cast<uint32_t *>(ws + L.off_c);
-    char *iws = ws + L.off_inner;
-    uint32_t *ierr = reinterpret_cast<uint32_t *>(iws);
-    HIP_TRY(launch_zero(ierr, 16, s));  // (a one-tile inner sort has no error word of its own)
-    {
-        TimingScope ts(LABSORT_K_SEGSORT, s);
-        HIP_TRY(launch_seg_bin(off, nseg, n, max_len, pairs, false, hdr, nullptr, 0, s));
-        if (pairs) HIP_TRY(launch_seg_ids(off, nseg, n, nullptr, nullptr, A, hdr, s));  // A = 0, 1, 2, ...
-        else HIP_TRY(launch_seg_ids(off, nseg, n, nullptr, A, nullptr, hdr, s));        // A = segment of each position
-    }
-    int st;
-    // (key, A) by key -> (B, C)
-    if ((st = labsort_sort_pairs_device(ki, A, B, C, n, key_type, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream))) return st;
-    HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
-    if (pairs) {
-        // C = positions in key order; B = their segments; (B, C) by segment in place: C = the permutation
-        {
-            TimingScope ts(LABSORT_K_SEGSORT, s);
-            HIP_TRY(launch_seg_ids(off, nseg, n, C, B, nullptr, hdr, s));
-        }
-        if ((st = labsort_sort_pairs_device(B, C, B, C, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
-            return st;
-        HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
-        TimingScope ts(LABSORT_K_SEGSORT, s);
-        if (inplace) {  // through temporaries: the gather reads what it would overwrite
-            HIP_TRY(launch_seg_gather(ki, vi, C, A, B, n, hdr, s));
-            HIP_TRY(launch_seg_gather(A, B, nullptr, ko, vo, n, hdr, s));
-        } else {
-            HIP_TRY(launch_seg_gather(ki, vi, C, ko, vo, n, hdr, s));
-        }
-    } else {
-        // (C = segment ids, B = keys) by segment id in place: B = the result
-        if ((st = labsort_sort_pairs_device(C, B, C, B, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
-            return st;
-        HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
-        TimingScope ts(LABSORT_K_SEGSORT, s);
-        HIP_TRY(launch_seg_gather(B, nullptr, nullptr, ko, nullptr, n, hdr, s));
-    }
-    return LABSORT_OK;
-}
-}  // namespace
-
-size_t labsort_segments_workspace_bytes(size_t n, size_t nseg, size_t max_segment_keys, int pairs) {
-    return seg_layout(n, nseg, seg_lds_path(max_segment_keys, pairs)).total;
-}
-
-int labsort_sort_segments_device(const void *d_keys_in, void *d_keys_out, size_t n, const uint32_t *d_offsets,
-                                 size_t nseg, size_t max_segment_keys, int key_type, void *d_ws, size_t ws_bytes,
-                                 void *stream) {
-    return sort_segments(static_cast<const uint32_t *>(d_keys_in), nullptr, static_cast<uint32_t *>(d_keys_out), nullptr,
-                         n, d_offsets, nseg, max_segment_keys, key_type, d_ws, ws_bytes, stream);
-}
-
-int labsort_sort_segments_pairs_device(const void *d_keys_in, const void *d_vals_in, void *d_keys_out, void *d_vals_out,
-                                       size_t n, const uint32_t *d_offsets, size_t nseg, size_t max_segment_keys,
-                                       int key_type, void *d_ws, size_t ws_bytes, void *stream) {
-    if (n == 0) return LABSORT_OK;
-    if (!d_vals_in || !d_vals_out) return LABSORT_ERR_ARG;
-    return sort_segments(static_cast<const uint32_t *>(d_keys_in), static_cast<const uint32_t *>(d_vals_in),
-                         static_cast<uint32_t *>(d_keys_out), static_cast<uint32_t *>(d_vals_out), n, d_offsets, nseg,
-                         max_segment_keys, key_type, d_ws, ws_bytes, stream);
-}
-
-int labsort_segments_workspace_status(const void *d_ws, void *stream) {
-    hipStream_t s = as_stream(stream);
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!d_ws) return LABSORT_ERR_ARG;
-    uint32_t w[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(w, d_ws, sizeof w, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return w[0] ? LABSORT_ERR_ARG : w[SEG_HDR_DEVERR] ? LABSORT_ERR_DEVICE : LABSORT_OK;
-}
-
-// ---------------------------------------------------------------------------------
-// top-k selection (topk.hip): the k best keys of every row, sorted, with their positions
-// ---------------------------------------------------------------------------------
-namespace {
-static_assert(TK_SORT_DIV == LABSORT_TOPK_SORT_DIV, "labsort.h states the large-k threshold");
-static_assert(SEG_HDR_CNT * 4 + SEG_CLASSES * 4 <= TK_HDR_BYTES && TK_HDR_BYTES == SEG_HDR_BYTES,
-              "the short path hands its header to the segmented sort's kernels");
-enum { TK_PATH_SHORT, TK_PATH_SELECT, TK_PATH_SORT };
-
-// Which path runs: host arguments only.  Whole-row sorting needs the inner sort's limits (one row:
-// any length; several: the segmented sort's general path), else the select serves every k.
-int topk_path(size_t rows, size_t cols, size_t k) {
-    if (cols <= (size_t)SEG_TILE_PAIRS) return TK_PATH_SHORT;
-    const bool sort_ok = rows == 1 || rows * cols <= RADIX_MAX_N;
-    bool want_sort = k * (size_t)TK_SORT_DIV > cols;
-    // LABSORT_TOPK_PATH=select / sort forces the long rows' path (harness/topk_bench.py --sweep)
-    if (const char *e = std::getenv("LABSORT_TOPK_PATH")) {
-        if (!std::strcmp(e, "select")) want_sort = false;
-        else if (!std::strcmp(e, "sort")) want_sort = true;
-    }
-    return (want_sort && sort_ok) ? TK_PATH_SORT : TK_PATH_SELECT;
-}
-
-// header | (select: hist, state, per-chunk tables, candidate buffers) | A, B: the m (u, position)
-// pairs per row to be ordered | SU, SP: the same, ordered | uniform offsets | the inner sort's
-// workspace.  m = k after a select, cols where whole rows are sorted.  The short path keeps the
-// segmented sort's class lists where the others keep the inner workspace, and has no A.
-struct TopkLayout {
-    int path;
-    size_t m, nch, cap, capa;
-    size_t off_hist, zero_bytes, off_st, off_cnt, off_low, off_eq, off_lowbase, off_eqbase, off_cand_u, off_cand_p;
-    size_t off_a, off_b, off_su, off_sp, off_offs, off_lists, list_stride, off_inner, inner_bytes, total;
-};
-TopkLayout topk_layout_path(size_t rows, size_t cols, size_t k, int path) {
-    TopkLayout L{};
-    L.path = path;
-    L.m = path == TK_PATH_SELECT ? k : cols;
-    size_t o = TK_HDR_BYTES;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align_up(o + bytes, 256);
-        return at;
-    };
-    if (path == TK_PATH_SELECT) {
-        L.nch = (cols + TK_CHUNK - 1) / TK_CHUNK;
-        L.cap = cols / TK_CAND_DIV;
-        L.capa = align_up(L.cap, 64);
-        L.off_hist = take(rows * TK_LEVELS * 256 * 4);
-        L.zero_bytes = o;  // header and histograms: the only words a call relies on being clear
-        L.off_st = take(rows * (TK_LEVELS + 1) * sizeof(TkState));
-        L.off_cnt = take(rows * L.nch * 256 * 4);
-        L.off_low = take(rows * L.nch * 4);
-        L.off_eq = take(rows * L.nch * 4);
-        L.off_lowbase = take(rows * L.nch * 4);
-        L.off_eqbase = take(rows * L.nch * 4);
-        L.off_cand_u = take(rows * L.capa * 4);
-        L.off_cand_p = take(rows * L.capa * 4);
-    } else {
-        L.zero_bytes = o;
-    }
-    const size_t n = rows * L.m;
-    if (path != TK_PATH_SHORT) L.off_a = take(n * 4);
-    L.off_b = take(n * 4);
-    L.off_su = take(n * 4);
-    L.off_sp = take(n * 4);
-    L.off_offs = take((rows + 1) * 4);
-    if (path == TK_PATH_SHORT) {
-        L.list_stride = align_up(rows * 4, 256) / 4;
-        L.off_lists = take((size_t)SEG_CLASSES * L.list_stride * 4);
-    } else {
-        L.inner_bytes = rows == 1 ? seg_inner_bytes(n) : labsort_segments_workspace_bytes(n, rows, L.m, 1);
-        L.off_inner = take(L.inner_bytes);
-    }
-    L.total = o;
-    return L;
-}
-TopkLayout topk_layout(size_t rows, size_t cols, size_t k) {
-    const int path = topk_path(rows, cols, k);
-    TopkLayout L = topk_layout_path(rows, cols, k, path);
-    // never less than the largest select below the threshold: the size does not shrink as k grows
-    if (path == TK_PATH_SORT && cols / TK_SORT_DIV >= 1)
-        L.total = std::max(L.total, topk_layout_path(rows, cols, cols / TK_SORT_DIV, TK_PATH_SELECT).total);
-    return L;
-}
-bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-}  // namespace
-
-size_t labsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k) {
-    if (rows == 0 || k == 0 || k > cols || rows > (size_t)0x7FFFFFFFu / cols) return TK_HDR_BYTES;
-    return topk_layout(rows, cols, k).total;
-}
-
-int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, int largest, int key_type,
-                        void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
-    if (rows == 0 || k == 0) return LABSORT_OK;
-    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
-    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
-    if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
-    if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
-    if (ranges_overlap(d_keys, rows * cols * 4, d_keys_out, rows * k * 4)) return LABSORT_ERR_ARG;
-    if (d_idx_out && ranges_overlap(d_keys, rows * cols * 4, d_idx_out, rows * k * 4)) return LABSORT_ERR_ARG;
-    const int path = topk_path(rows, cols, k);
-    // the survivors of several long rows are ordered by the segmented sort: past its LDS tile, its general path
-    if (path == TK_PATH_SELECT && rows > 1 && k > (size_t)SEG_TILE_PAIRS && rows * k > RADIX_MAX_N) return LABSORT_ERR_ARG;
-    if (!d_ws || ws_bytes < labsort_topk_workspace_bytes(rows, cols, k)) return LABSORT_ERR_ARG;
-    const TopkLayout L = topk_layout_path(rows, cols, k, path);
-    const uint32_t xr = flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
-    hipStream_t s = as_stream(stream);
-    char *ws = static_cast<char *>(d_ws);
-    auto W = [&](size_t off) { return reinterpret_cast<uint32_t *>(ws + off); };
-    const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
-    uint32_t *hdr = W(0), *A = W(L.off_a), *B = W(L.off_b), *SU = W(L.off_su), *SP = W(L.off_sp), *offs = W(L.off_offs);
-    uint32_t *ko = static_cast<uint32_t *>(d_keys_out);
-    const size_t n = rows * L.m;
-    HIP_TRY(launch_zero(ws, L.zero_bytes, s));  // (a kernel: graph-replayable)
-    if (path == TK_PATH_SHORT) {
-        // whole rows through the segmented sort's LDS classes, on (key, position) with xr as the flip
-        TimingScope ts(LABSORT_K_TOPK, s);
-        uint32_t *lists = W(L.off_lists);
-        HIP_TRY(launch_topk_offsets(offs, rows, cols, s));
-        HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, s));
-        HIP_TRY(launch_seg_bin(offs, rows, n, cols, true, true, hdr, lists, L.list_stride, s));
-        size_t edges[SEG_CLASSES];
-        labsort_segment_class_edges(1, edges, SEG_CLASSES);
-        int ncls = 1;
-        while (ncls < SEG_CLASSES && cols > edges[ncls - 1]) ++ncls;
-        for (int c = 0; c < ncls; ++c)
-            HIP_TRY(launch_seg_sort(c, keys, SU, B, SP, offs, hdr, lists + (size_t)c * L.list_stride, xr, s));
-        HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, cols, k, 0u, s));  // (the class kernels wrote keys, not u)
-        return LABSORT_OK;
-    }
-    if (path == TK_PATH_SELECT) {
-        TimingScope ts(LABSORT_K_TOPK, s);
-        TkArgs a{};
-        a.keys = keys;
-        a.hist = W(L.off_hist);
-        a.cnt = W(L.off_cnt);
-        a.low = W(L.off_low);
-        a.eq = W(L.off_eq);
-        a.lowbase = W(L.off_lowbase);
-        a.eqbase = W(L.off_eqbase);
-        a.st = reinterpret_cast<TkState *>(ws + L.off_st);
-        a.cand_u = W(L.off_cand_u);
-        a.cand_p = W(L.off_cand_p);
-        a.surv_u = A;
-        a.surv_p = B;
-        a.cols = (uint32_t)cols;
-        a.k = (uint32_t)k;
-        a.nch = (uint32_t)L.nch;
-        a.capa = (uint32_t)L.capa;
-        a.cap = (uint32_t)L.cap;
-        a.xr = xr;
-        for (int level = 0; level < TK_LEVELS; ++level) {
-            HIP_TRY(launch_topk_hist(a, rows, level, s));
-            HIP_TRY(launch_topk_reduce(a, rows, level, s));
-            HIP_TRY(launch_topk_scan(a, rows, level, s));
-            if (level < TK_LEVELS - 1 && L.cap > 0) HIP_TRY(launch_topk_narrow(a, rows, level, s));
-        }
-        HIP_TRY(launch_topk_final(a, rows, s));
-    } else {
-        TimingScope ts(LABSORT_K_TOPK, s);
-        HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, s));
-    }
-    // order the m pairs of every row on u (stable): one pair sort, or the segmented pair sort
-    char *iws = ws + L.off_inner;
-    uint32_t *ierr = reinterpret_cast<uint32_t *>(iws);
-    HIP_TRY(launch_zero(ierr, 16, s));  // (a one-tile inner sort has no error word of its own)
-    int st;
-    if (rows == 1) {
-        if ((st = labsort_sort_pairs_device(A, B, SU, SP, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
-            return st;
-    } else {
-        {
-            TimingScope ts(LABSORT_K_TOPK, s);
-            HIP_TRY(launch_topk_offsets(offs, rows, L.m, s));
-        }
-        if ((st = labsort_sort_segments_pairs_device(A, B, SU, SP, n, offs, rows, L.m, LABSORT_KEY_U32, iws, L.inner_bytes,
-                                                     stream)))
-            return st;
-    }
-    TimingScope ts(LABSORT_K_TOPK, s);
-    HIP_TRY(launch_topk_err_acc(hdr, ierr, 2, s));
-    HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, L.m, k, xr, s));
-    return LABSORT_OK;
-}
-
-int labsort_topk_workspace_status(const void *d_ws, void *stream) {
-    hipStream_t s = as_stream(stream);
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!d_ws) return LABSORT_ERR_ARG;
-    uint32_t w = 0;
-    HIP_TRY(hipMemcpyAsync(&w, d_ws, sizeof w, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return w ? LABSORT_ERR_DEVICE : LABSORT_OK;
+    return algo == LABSORT_ALGO_RADIX ? sort_radix8(ki, vi, ko, vo, n, flip, ws, s) : sort_merge(ki, vi, ko, vo, n, flip, ws, s);
 }
 
 int labsort_histogram(const void *d_keys, size_t n, int key_type, int bits, uint32_t *d_hist, void *stream) {
@@ -1281,7 +779,7 @@ int labsort_upper_bound(const void *d_sorted, size_t n, int key_type, const uint
                         uint32_t *d_out, void *stream) {
     if (nv == 0) return LABSORT_OK;
     if (!d_values || !d_out || (n && !d_sorted) || n > 0xFFFFFFFFu) return LABSORT_ERR_ARG;
-    if (key_type != LABSORT_KEY_U32 && key_type != LABSORT_KEY_I32) return LABSORT_ERR_ARG;
+    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
     HIP_TRY(launch_upper_bound(static_cast<const uint32_t *>(d_sorted), n, flip_of(key_type), d_values, nv, d_out,
                                as_stream(stream)));
     return LABSORT_OK;

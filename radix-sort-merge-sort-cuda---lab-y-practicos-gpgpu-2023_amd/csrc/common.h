@@ -107,14 +107,8 @@ struct GsLayout {
         off_first[2], total;
 };
 GsLayout gs_layout(size_t n);
-// timing hooks around the pass and final-copy launches (api.hip's event scopes)
-struct GsHooks {
-    void *ctx;
-    void (*begin)(void *ctx, int kernel_class, hipStream_t s);
-    void (*end)(void *ctx, int kernel_class, hipStream_t s);
-};
-hipError_t launch_gsweep_sort(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, char *ws, hipStream_t s,
-                              const GsHooks &hooks);
+// (timing scopes around the pass and final-copy launches)
+hipError_t launch_gsweep_sort(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, char *ws, hipStream_t s);
 
 constexpr int MAX_PASSES = 32;
 constexpr uint32_t SEL_IN = 0, SEL_OUT = 1, SEL_TMP = 2, SEL_SKIP = 0xFFu;

@@ -34,9 +34,8 @@
 //   first[T]  e of the run holding logical position T*TILE; first[ntp]: position n-1
 #include <algorithm>
 
-#include "../../include/labsort.h"
-#include "common.h"
 #include "devutil.h"
+#include "host.h"
 
 namespace labsort {
 
@@ -910,8 +909,7 @@ GsLayout gs_layout(size_t n) {
     return L;
 }
 
-hipError_t launch_gsweep_sort(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, char *ws, hipStream_t s,
-                              const GsHooks &hooks) {
+hipError_t launch_gsweep_sort(const uint32_t *in, uint32_t *out, size_t n, uint32_t flip, char *ws, hipStream_t s) {
     const GsLayout L = gs_layout(n);
     const uint32_t ntp = (uint32_t)((n + GT - 1) / GT), ng = (ntp + GS_GROUP - 1) / GS_GROUP;
     GsState *st = reinterpret_cast<GsState *>(ws + L.off_state);
@@ -930,30 +928,28 @@ hipError_t launch_gsweep_sort(const uint32_t *in, uint32_t *out, size_t n, uint3
     if (ng <= (uint32_t)GS_SMALL_NG) {  // fused small path: sweeps 0-3 and the gathered copy, no memset
         uint32_t *acc = flags;
         for (int p = 0; p < 4; ++p) {
-            if (hooks.begin) hooks.begin(hooks.ctx, LABSORT_K_GSWEEP, s);
+            TimingScope ts(LABSORT_K_GSWEEP, s);
             k_gsweep<true><<<grid, GB, 0, s>>>(in, A, B, t[0], t[1], rt, rt2, mm, st, acc, p, (uint32_t)n, ntp, flip, 1);
-            if (hooks.end) hooks.end(hooks.ctx, LABSORT_K_GSWEEP, s);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        if (hooks.begin) hooks.begin(hooks.ctx, LABSORT_K_GCOPY, s);
+        TimingScope ts(LABSORT_K_GCOPY, s);
         k_gcopy<true><<<grid, GB, 0, s>>>(A, B, t[0], t[1], rt, rt2, st, acc, out, (uint32_t)n, ntp);
-        if (hooks.end) hooks.end(hooks.ctx, LABSORT_K_GCOPY, s);
         return hipGetLastError();
     }
     e = launch_zero(ws + L.off_state, 512 + (size_t)4 * ng * 256 * 4, s);
     if (e != hipSuccess) return e;
     for (int p = 0; p < 4; ++p) {
-        if (hooks.begin) hooks.begin(hooks.ctx, LABSORT_K_GSWEEP, s);
-        k_gsweep<false><<<grid, GB, 0, s>>>(in, A, B, t[0], t[1], rt, rt2, mm, st, flags, p, (uint32_t)n, ntp, flip, 0);
-        if (hooks.end) hooks.end(hooks.ctx, LABSORT_K_GSWEEP, s);
+        {
+            TimingScope ts(LABSORT_K_GSWEEP, s);
+            k_gsweep<false><<<grid, GB, 0, s>>>(in, A, B, t[0], t[1], rt, rt2, mm, st, flags, p, (uint32_t)n, ntp, flip, 0);
+        }
         if ((e = hipGetLastError()) != hipSuccess) return e;
         k_gsum<<<ng, 256, 0, s>>>(rt, mm, gsx, gx, gmm, flags, st, p, ntp, ng);
         k_gout<<<ng, 1024, 0, s>>>(rt, gsx, gx, gmm, t[0], t[1], st, p, ntp, (uint32_t)n);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (hooks.begin) hooks.begin(hooks.ctx, LABSORT_K_GCOPY, s);
+    TimingScope ts(LABSORT_K_GCOPY, s);
     k_gcopy<false><<<grid, GB, 0, s>>>(A, B, t[0], t[1], rt, rt2, st, flags, out, (uint32_t)n, ntp);
-    if (hooks.end) hooks.end(hooks.ctx, LABSORT_K_GCOPY, s);
     return hipGetLastError();
 }
 

@@ -1,0 +1,61 @@
+// host.h -- what every host driver of liblabsort.so needs, each defined once (internal:
+// api.hip, gsweep.hip, segsort.hip, topk.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/labsort.h"
+#include "common.h"
+
+namespace labsort {
+
+// records e for labsort_last_hip_error (api.hip's thread-local slot); returns LABSORT_ERR_HIP
+int fail_hip(hipError_t e);
+#define HIP_TRY(x)                                            \
+    do {                                                      \
+        hipError_t _e = (x);                                  \
+        if (_e != hipSuccess) return ::labsort::fail_hip(_e); \
+    } while (0)
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline uint32_t flip_of(int key_type) { return key_type == LABSORT_KEY_I32 ? 0x80000000u : 0u; }
+inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+inline bool key_type_ok(int key_type) { return key_type == LABSORT_KEY_U32 || key_type == LABSORT_KEY_I32; }
+// Key/value calls are in place only as a whole: one side aliased and the other not would
+// read payloads that the key side's passes already overwrote.  Keys and payloads never
+// share their output.
+inline bool pairs_alias_ok(const void *ki, const void *vi, const void *ko, const void *vo) {
+    return (ki == ko) == (vi == vo) && ko != vo;
+}
+
+// Timing scope: with labsort_timing_enable(1), an event pair on s around the launches made
+// while the scope lives, counted under kernel class cls (api.hip keeps the state).
+struct TimingScope {
+    int cls;
+    hipStream_t s;
+    hipEvent_t a = nullptr, b = nullptr;
+    TimingScope(int c, hipStream_t st);
+    ~TimingScope();
+};
+
+// Workspace carver: regions one behind the other, each starting on a 256-byte boundary.
+struct Carver {
+    size_t o = 0;
+    size_t take(size_t bytes) {
+        const size_t at = o;
+        o = align_up(o + bytes, 256);
+        return at;
+    }
+};
+
+// Status read of a workspace: waits for the stream, copies the workspace's first `count`
+// words to `words`, waits again.  What the words mean is the caller's.
+inline int read_ws_words(const void *d_ws, uint32_t *words, int count, hipStream_t s) {
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!d_ws) return LABSORT_ERR_ARG;
+    HIP_TRY(hipMemcpyAsync(words, d_ws, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return LABSORT_OK;
+}
+
+}  // namespace labsort

@@ -1,4 +1,4 @@
-// segsort.h -- segmented sort (segsort.hip): shapes, workspace header and host launchers.
+// segsort.h -- segmented sort (segsort.hip): shapes, workspace header and what top-k shares of it.
 #pragma once
 #include "common.h"
 
@@ -52,18 +52,12 @@ constexpr int SEG_HDR_DEVERR = 1, SEG_HDR_CNT = 4;
 // copy1: out of place, so 1-key segments are listed too (wave class) and get copied.
 hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max_len, bool pairs, bool copy1,
                           uint32_t *hdr, uint32_t *lists, size_t stride, hipStream_t s);
-// The sort kernel of class c (0-2 wave, 3 block, 4 tile) over its list; vin/vout nullptr: keys only.
-hipError_t launch_seg_sort(int c, const uint32_t *in, uint32_t *out, const uint32_t *vin, uint32_t *vout,
-                           const uint32_t *off, const uint32_t *hdr, const uint32_t *list, uint32_t flip,
-                           hipStream_t s);
-// general path helpers (all return at once when hdr word 0 is set)
-// ids[i] = segment of position (idx ? idx[i] : i); iota (or nullptr): iota[i] = i
-hipError_t launch_seg_ids(const uint32_t *off, size_t nseg, size_t n, const uint32_t *idx, uint32_t *ids,
-                          uint32_t *iota, const uint32_t *hdr, hipStream_t s);
-// out[i] = perm ? src[perm[i]] : src[i], for keys and (vsrc != nullptr) payloads
-hipError_t launch_seg_gather(const uint32_t *src, const uint32_t *vsrc, const uint32_t *perm, uint32_t *out,
-                             uint32_t *vout, size_t n, const uint32_t *hdr, hipStream_t s);
-// hdr[SEG_HDR_DEVERR] |= *inner_err; *inner_err = 0
-hipError_t launch_seg_err_acc(uint32_t *hdr, uint32_t *inner_err, hipStream_t s);
+// The LDS path's sort launches: the kernel of every class that max_len admits, each over its list
+// (lists + c * stride).  Host arguments only: the launch sequence is fixed.  vin/vout nullptr: keys only.
+hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in, uint32_t *out, const uint32_t *vin,
+                                  uint32_t *vout, const uint32_t *off, const uint32_t *hdr, const uint32_t *lists,
+                                  size_t stride, uint32_t flip, hipStream_t s);
+// workspace of the general path's inner pair sorts of n pairs (top-k's single-row sort uses the same)
+size_t seg_inner_bytes(size_t n);
 
 }  // namespace labsort

@@ -15,7 +15,10 @@
 // it is set, so rejected offsets never become addresses.
 #include "segsort.h"
 
+#include <algorithm>
+
 #include "devutil.h"
+#include "host.h"
 
 namespace labsort {
 
@@ -488,18 +491,7 @@ unsigned stream_blocks(size_t n) {
     return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
 }
 
-}  // namespace
-
-hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max_len, bool pairs, bool copy1,
-                          uint32_t *hdr, uint32_t *lists, size_t stride, hipStream_t s) {
-    const unsigned g = (unsigned)((nseg + BIN_BLOCK * BIN_SPT - 1) / (BIN_BLOCK * BIN_SPT));
-    (void)pairs;  // the class edges below the tile are the same for keys and pairs
-    const SegEdges e{{(uint32_t)SEG_WAVE_KEYS, (uint32_t)SEG_WAVE2_KEYS, (uint32_t)SEG_WAVE3_KEYS, (uint32_t)SEG_BLOCK_KEYS}};
-    k_seg_bin<<<g, BIN_BLOCK, 0, s>>>(off, (uint32_t)nseg, (uint32_t)n, (uint32_t)max_len, e, copy1 ? 1u : 0u, hdr, lists,
-                                      stride);
-    return hipGetLastError();
-}
-
+// The sort kernel of class c (0-2 wave, 3 block, 4 tile) over its list; vin/vout nullptr: keys only.
 hipError_t launch_seg_sort(int c, const uint32_t *in, uint32_t *out, const uint32_t *vin, uint32_t *vout,
                            const uint32_t *off, const uint32_t *hdr, const uint32_t *list, uint32_t flip,
                            hipStream_t s) {
@@ -527,21 +519,203 @@ hipError_t launch_seg_sort(int c, const uint32_t *in, uint32_t *out, const uint3
     return hipGetLastError();
 }
 
+// general path helpers (all return at once when hdr word 0 is set)
+// ids[i] = segment of position (idx ? idx[i] : i); iota (or nullptr): iota[i] = i
 hipError_t launch_seg_ids(const uint32_t *off, size_t nseg, size_t n, const uint32_t *idx, uint32_t *ids,
                           uint32_t *iota, const uint32_t *hdr, hipStream_t s) {
     k_seg_ids<<<stream_blocks(n), 256, 0, s>>>(off, (uint32_t)nseg, (uint32_t)n, idx, ids, iota, hdr);
     return hipGetLastError();
 }
 
+// out[i] = perm ? src[perm[i]] : src[i], for keys and (vsrc != nullptr) payloads
 hipError_t launch_seg_gather(const uint32_t *src, const uint32_t *vsrc, const uint32_t *perm, uint32_t *out,
                              uint32_t *vout, size_t n, const uint32_t *hdr, hipStream_t s) {
     k_seg_gather<<<stream_blocks(n), 256, 0, s>>>(src, vsrc, perm, out, vout, (uint32_t)n, hdr);
     return hipGetLastError();
 }
 
+// hdr[SEG_HDR_DEVERR] |= *inner_err; *inner_err = 0
 hipError_t launch_seg_err_acc(uint32_t *hdr, uint32_t *inner_err, hipStream_t s) {
     k_seg_err_acc<<<1, 64, 0, s>>>(hdr, inner_err);
     return hipGetLastError();
 }
 
+}  // namespace
+
+hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max_len, bool pairs, bool copy1,
+                          uint32_t *hdr, uint32_t *lists, size_t stride, hipStream_t s) {
+    const unsigned g = (unsigned)((nseg + BIN_BLOCK * BIN_SPT - 1) / (BIN_BLOCK * BIN_SPT));
+    (void)pairs;  // the class edges below the tile are the same for keys and pairs
+    const SegEdges e{{(uint32_t)SEG_WAVE_KEYS, (uint32_t)SEG_WAVE2_KEYS, (uint32_t)SEG_WAVE3_KEYS, (uint32_t)SEG_BLOCK_KEYS}};
+    k_seg_bin<<<g, BIN_BLOCK, 0, s>>>(off, (uint32_t)nseg, (uint32_t)n, (uint32_t)max_len, e, copy1 ? 1u : 0u, hdr, lists,
+                                      stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in, uint32_t *out, const uint32_t *vin,
+                                  uint32_t *vout, const uint32_t *off, const uint32_t *hdr, const uint32_t *lists,
+                                  size_t stride, uint32_t flip, hipStream_t s) {
+    size_t edges[SEG_CLASSES];
+    labsort_segment_class_edges(pairs ? 1 : 0, edges, SEG_CLASSES);
+    int ncls = 1;
+    while (ncls < SEG_CLASSES && max_len > edges[ncls - 1]) ++ncls;
+    for (int c = 0; c < ncls; ++c) {
+        const hipError_t e = launch_seg_sort(c, in, out, vin, vout, off, hdr, lists + (size_t)c * stride, flip, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// the inner pair sort runs LABSORT_ALGO_AUTO; sized so the function never shrinks as n grows
+// across AUTO's merge -> radix switch
+size_t seg_inner_bytes(size_t n) {
+    const size_t m = n < (size_t)LABSORT_AUTO_PAIRS_MERGE_MAX_KEYS ? n : (size_t)LABSORT_AUTO_PAIRS_MERGE_MAX_KEYS;
+    return std::max(labsort_pairs_workspace_bytes(n, LABSORT_ALGO_AUTO), labsort_pairs_workspace_bytes(m, LABSORT_ALGO_MERGE));
+}
+
 }  // namespace labsort
+
+using namespace labsort;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------
+// host driver and C-ABI: segment i = [d_offsets[i], d_offsets[i+1])
+// ---------------------------------------------------------------------------------
+size_t labsort_segment_tile_keys(void) { return (size_t)SEG_TILE_KEYS; }
+size_t labsort_segment_pair_tile_keys(void) { return (size_t)SEG_TILE_PAIRS; }
+
+int labsort_segment_class_edges(int pairs, size_t *edges, int cap) {
+    const size_t e[SEG_CLASSES] = {(size_t)SEG_WAVE_KEYS, (size_t)SEG_WAVE2_KEYS, (size_t)SEG_WAVE3_KEYS, (size_t)SEG_BLOCK_KEYS,
+                                   pairs ? (size_t)SEG_TILE_PAIRS : (size_t)SEG_TILE_KEYS};
+    for (int i = 0; i < SEG_CLASSES && i < cap && edges; ++i) edges[i] = e[i];
+    return SEG_CLASSES;
+}
+
+namespace {
+bool seg_lds_path(size_t max_len, int pairs) {
+    return max_len > 0 && max_len <= (pairs ? (size_t)SEG_TILE_PAIRS : (size_t)SEG_TILE_KEYS);
+}
+// LDS path: header | one list of nseg words per class.
+// General path: header | three n-word buffers | the inner pair sorts' workspace.
+struct SegLayout {
+    size_t off_lists, list_stride;    // LDS path (stride in words)
+    size_t off_a, off_b, off_c, off_inner, inner_bytes;  // general path
+    size_t total;
+};
+SegLayout seg_layout(size_t n, size_t nseg, bool lds) {
+    SegLayout L{};
+    Carver c{SEG_HDR_BYTES};
+    if (lds) {
+        L.list_stride = align_up(nseg * 4, 256) / 4;
+        L.off_lists = c.take((size_t)SEG_CLASSES * L.list_stride * 4);
+        L.total = c.o;
+    } else {
+        L.off_a = c.take(n * 4);
+        L.off_b = c.take(n * 4);
+        L.off_c = c.take(n * 4);
+        L.off_inner = c.o;
+        L.inner_bytes = seg_inner_bytes(n);
+        L.total = c.o + L.inner_bytes;
+    }
+    return L;
+}
+
+int sort_segments(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, size_t n, const uint32_t *off,
+                  size_t nseg, size_t max_len, int key_type, void *d_ws, size_t ws_bytes, void *stream) {
+    const bool pairs = vi != nullptr || vo != nullptr;
+    if (n == 0) return LABSORT_OK;
+    if (!ki || !ko || !off || (pairs && (!vi || !vo))) return LABSORT_ERR_ARG;
+    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (nseg == 0 || n > (size_t)0x7FFFFFFFu || nseg > (size_t)0x7FFFFFFFu) return LABSORT_ERR_ARG;
+    if (pairs && !pairs_alias_ok(ki, vi, ko, vo)) return LABSORT_ERR_ARG;
+    const bool lds = seg_lds_path(max_len, pairs ? 1 : 0);
+    if (!lds && n > RADIX_MAX_N) return LABSORT_ERR_ARG;
+    if (!d_ws || ws_bytes < labsort_segments_workspace_bytes(n, nseg, max_len, pairs ? 1 : 0)) return LABSORT_ERR_ARG;
+    const SegLayout L = seg_layout(n, nseg, lds);
+    const uint32_t flip = flip_of(key_type);
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    uint32_t *hdr = reinterpret_cast<uint32_t *>(ws);
+    const bool inplace = ki == ko;
+    HIP_TRY(launch_zero(hdr, SEG_HDR_BYTES, s));  // (a kernel: graph-replayable)
+    if (lds) {
+        uint32_t *lists = reinterpret_cast<uint32_t *>(ws + L.off_lists);
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        HIP_TRY(launch_seg_bin(off, nseg, n, max_len, pairs, !inplace, hdr, lists, L.list_stride, s));
+        HIP_TRY(launch_seg_lds_classes(max_len, pairs, ki, ko, vi, vo, off, hdr, lists, L.list_stride, flip, s));
+        return LABSORT_OK;
+    }
+    // general path: two stable pair sorts (by key, then by segment id) on workspace buffers;
+    // the caller's output is written by the last, guarded, kernel only
+    uint32_t *A = reinterpret_cast<uint32_t *>(ws + L.off_a), *B = reinterpret_cast<uint32_t *>(ws + L.off_b),
+             *C = reinterpret_cast<uint32_t *>(ws + L.off_c);
+    char *iws = ws + L.off_inner;
+    uint32_t *ierr = reinterpret_cast<uint32_t *>(iws);
+    HIP_TRY(launch_zero(ierr, 16, s));  // (a one-tile inner sort has no error word of its own)
+    {
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        HIP_TRY(launch_seg_bin(off, nseg, n, max_len, pairs, false, hdr, nullptr, 0, s));
+        if (pairs) HIP_TRY(launch_seg_ids(off, nseg, n, nullptr, nullptr, A, hdr, s));  // A = 0, 1, 2, ...
+        else HIP_TRY(launch_seg_ids(off, nseg, n, nullptr, A, nullptr, hdr, s));        // A = segment of each position
+    }
+    int st;
+    // (key, A) by key -> (B, C)
+    if ((st = labsort_sort_pairs_device(ki, A, B, C, n, key_type, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream))) return st;
+    HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
+    if (pairs) {
+        // C = positions in key order; B = their segments; (B, C) by segment in place: C = the permutation
+        {
+            TimingScope ts(LABSORT_K_SEGSORT, s);
+            HIP_TRY(launch_seg_ids(off, nseg, n, C, B, nullptr, hdr, s));
+        }
+        if ((st = labsort_sort_pairs_device(B, C, B, C, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
+            return st;
+        HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        if (inplace) {  // through temporaries: the gather reads what it would overwrite
+            HIP_TRY(launch_seg_gather(ki, vi, C, A, B, n, hdr, s));
+            HIP_TRY(launch_seg_gather(A, B, nullptr, ko, vo, n, hdr, s));
+        } else {
+            HIP_TRY(launch_seg_gather(ki, vi, C, ko, vo, n, hdr, s));
+        }
+    } else {
+        // (C = segment ids, B = keys) by segment id in place: B = the result
+        if ((st = labsort_sort_pairs_device(C, B, C, B, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
+            return st;
+        HIP_TRY(launch_seg_err_acc(hdr, ierr, s));
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        HIP_TRY(launch_seg_gather(B, nullptr, nullptr, ko, nullptr, n, hdr, s));
+    }
+    return LABSORT_OK;
+}
+}  // namespace
+
+size_t labsort_segments_workspace_bytes(size_t n, size_t nseg, size_t max_segment_keys, int pairs) {
+    return seg_layout(n, nseg, seg_lds_path(max_segment_keys, pairs)).total;
+}
+
+int labsort_sort_segments_device(const void *d_keys_in, void *d_keys_out, size_t n, const uint32_t *d_offsets,
+                                 size_t nseg, size_t max_segment_keys, int key_type, void *d_ws, size_t ws_bytes,
+                                 void *stream) {
+    return sort_segments(static_cast<const uint32_t *>(d_keys_in), nullptr, static_cast<uint32_t *>(d_keys_out), nullptr,
+                         n, d_offsets, nseg, max_segment_keys, key_type, d_ws, ws_bytes, stream);
+}
+
+int labsort_sort_segments_pairs_device(const void *d_keys_in, const void *d_vals_in, void *d_keys_out, void *d_vals_out,
+                                       size_t n, const uint32_t *d_offsets, size_t nseg, size_t max_segment_keys,
+                                       int key_type, void *d_ws, size_t ws_bytes, void *stream) {
+    if (n == 0) return LABSORT_OK;
+    if (!d_vals_in || !d_vals_out) return LABSORT_ERR_ARG;
+    return sort_segments(static_cast<const uint32_t *>(d_keys_in), static_cast<const uint32_t *>(d_vals_in),
+                         static_cast<uint32_t *>(d_keys_out), static_cast<uint32_t *>(d_vals_out), n, d_offsets, nseg,
+                         max_segment_keys, key_type, d_ws, ws_bytes, stream);
+}
+
+int labsort_segments_workspace_status(const void *d_ws, void *stream) {
+    uint32_t w[2] = {0, 0};
+    if (const int st = read_ws_words(d_ws, w, 2, as_stream(stream))) return st;
+    return w[0] ? LABSORT_ERR_ARG : w[SEG_HDR_DEVERR] ? LABSORT_ERR_DEVICE : LABSORT_OK;
+}
+
+}  // extern "C"

@@ -21,9 +21,39 @@
 // Every dependency is a kernel boundary; a workgroup beyond a row's current source returns at once.
 #include "topk.h"
 
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
 #include "devutil.h"
+#include "host.h"
+#include "segsort.h"
 
 namespace labsort {
+
+// Per row and level: what the level's kernels read.  Level L's scan writes entry L + 1, so no
+// kernel reads a word that another workgroup of the same launch writes.
+struct TkState {
+    uint32_t prefix;    // digits chosen so far, in place (the top 8 * level bits)
+    uint32_t krem;      // keys still to take among those that match the prefix (>= 1)
+    uint32_t narrowed;  // 1: the source is the candidate buffer
+    uint32_t ccount;    // pairs in the candidate buffer
+    uint32_t sbase;     // survivors written so far (by the narrowing pass)
+    uint32_t jn;        // 1: the previous level narrowed this row (its narrowing pass runs, low[] restarts)
+    uint32_t tlow;      // keys of the source below the prefix: the sum of low[] after this level
+    uint32_t pad;
+};
+
+struct TkArgs {
+    const uint32_t *keys;                    // rows x cols, as the caller gave them
+    uint32_t *hist;                          // [rows][TK_LEVELS][256]
+    uint32_t *cnt;                           // [rows][nch][256]: each chunk's counts of the current level
+    uint32_t *low, *eq, *lowbase, *eqbase;   // [rows][nch]: keys below the prefix / in the bucket, and their exclusive scans
+    TkState *st;                             // [rows][TK_LEVELS + 1]
+    uint32_t *cand_u, *cand_p;               // [rows][capa]
+    uint32_t *surv_u, *surv_p;               // [rows][k]
+    uint32_t cols, k, nch, capa, cap, xr;    // capa: cap rounded up to 64 words; xr: u = key ^ xr
+};
 
 namespace {
 
@@ -360,8 +390,6 @@ unsigned tk_stream_blocks(size_t n) {
     return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
 }
 
-}  // namespace
-
 hipError_t launch_topk_hist(const TkArgs &a, size_t rows, int level, hipStream_t s) {
     const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
     const uint32_t nx = (a.nch + g - 1u) / g;
@@ -390,22 +418,26 @@ hipError_t launch_topk_final(const TkArgs &a, size_t rows, hipStream_t s) {
     return hipGetLastError();
 }
 
+// u[i] = keys[i] ^ xr (u may be nullptr), pos[i] = i % cols
 hipError_t launch_topk_prep(const uint32_t *keys, uint32_t *u, uint32_t *pos, size_t n, size_t cols, uint32_t xr,
                             hipStream_t s) {
     k_tk_prep<<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
     return hipGetLastError();
 }
 
+// off[i] = i * m, i <= rows
 hipError_t launch_topk_offsets(uint32_t *off, size_t rows, size_t m, hipStream_t s) {
     k_tk_offsets<<<tk_stream_blocks(rows + 1), 256, 0, s>>>(off, (uint32_t)rows, (uint32_t)m);
     return hipGetLastError();
 }
 
+// hdr[0] |= any of inner[0 .. nw) set
 hipError_t launch_topk_err_acc(uint32_t *hdr, const uint32_t *inner, int nw, hipStream_t s) {
     k_tk_err_acc<<<1, 64, 0, s>>>(hdr, inner, nw);
     return hipGetLastError();
 }
 
+// keys_out[r][j] = su[r * m + j] ^ xr, idx_out[r][j] = sp[r * m + j] for j < k (idx_out may be nullptr)
 hipError_t launch_topk_write(const uint32_t *su, const uint32_t *sp, uint32_t *keys_out, uint32_t *idx_out, size_t rows,
                              size_t m, size_t k, uint32_t xr, hipStream_t s) {
     // blocks per row: enough for one key per thread, fewer when there are many rows
@@ -416,4 +448,197 @@ hipError_t launch_topk_write(const uint32_t *su, const uint32_t *sp, uint32_t *k
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace labsort
+
+using namespace labsort;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------
+// host driver and C-ABI: the k best keys of every row, sorted, with their positions
+// ---------------------------------------------------------------------------------
+namespace {
+static_assert(TK_SORT_DIV == LABSORT_TOPK_SORT_DIV, "labsort.h states the large-k threshold");
+static_assert(SEG_HDR_CNT * 4 + SEG_CLASSES * 4 <= TK_HDR_BYTES && TK_HDR_BYTES == SEG_HDR_BYTES,
+              "the short path hands its header to the segmented sort's kernels");
+enum { TK_PATH_SHORT, TK_PATH_SELECT, TK_PATH_SORT };
+
+// Which path runs: host arguments only.  Whole-row sorting needs the inner sort's limits (one row:
+// any length; several: the segmented sort's general path), else the select serves every k.
+int topk_path(size_t rows, size_t cols, size_t k) {
+    if (cols <= (size_t)SEG_TILE_PAIRS) return TK_PATH_SHORT;
+    const bool sort_ok = rows == 1 || rows * cols <= RADIX_MAX_N;
+    bool want_sort = k * (size_t)TK_SORT_DIV > cols;
+    // LABSORT_TOPK_PATH=select / sort forces the long rows' path (harness/topk_bench.py --sweep)
+    if (const char *e = std::getenv("LABSORT_TOPK_PATH")) {
+        if (!std::strcmp(e, "select")) want_sort = false;
+        else if (!std::strcmp(e, "sort")) want_sort = true;
+    }
+    return (want_sort && sort_ok) ? TK_PATH_SORT : TK_PATH_SELECT;
+}
+
+// header | (select: hist, state, per-chunk tables, candidate buffers) | A, B: the m (u, position)
+// pairs per row to be ordered | SU, SP: the same, ordered | uniform offsets | the inner sort's
+// workspace.  m = k after a select, cols where whole rows are sorted.  The short path keeps the
+// segmented sort's class lists where the others keep the inner workspace, and has no A.
+struct TopkLayout {
+    int path;
+    size_t m, nch, cap, capa;
+    size_t off_hist, zero_bytes, off_st, off_cnt, off_low, off_eq, off_lowbase, off_eqbase, off_cand_u, off_cand_p;
+    size_t off_a, off_b, off_su, off_sp, off_offs, off_lists, list_stride, off_inner, inner_bytes, total;
+};
+TopkLayout topk_layout_path(size_t rows, size_t cols, size_t k, int path) {
+    TopkLayout L{};
+    L.path = path;
+    L.m = path == TK_PATH_SELECT ? k : cols;
+    Carver c{TK_HDR_BYTES};
+    if (path == TK_PATH_SELECT) {
+        L.nch = (cols + TK_CHUNK - 1) / TK_CHUNK;
+        L.cap = cols / TK_CAND_DIV;
+        L.capa = align_up(L.cap, 64);
+        L.off_hist = c.take(rows * TK_LEVELS * 256 * 4);
+        L.zero_bytes = c.o;  // header and histograms: the only words a call relies on being clear
+        L.off_st = c.take(rows * (TK_LEVELS + 1) * sizeof(TkState));
+        L.off_cnt = c.take(rows * L.nch * 256 * 4);
+        L.off_low = c.take(rows * L.nch * 4);
+        L.off_eq = c.take(rows * L.nch * 4);
+        L.off_lowbase = c.take(rows * L.nch * 4);
+        L.off_eqbase = c.take(rows * L.nch * 4);
+        L.off_cand_u = c.take(rows * L.capa * 4);
+        L.off_cand_p = c.take(rows * L.capa * 4);
+    } else {
+        L.zero_bytes = c.o;
+    }
+    const size_t n = rows * L.m;
+    if (path != TK_PATH_SHORT) L.off_a = c.take(n * 4);
+    L.off_b = c.take(n * 4);
+    L.off_su = c.take(n * 4);
+    L.off_sp = c.take(n * 4);
+    L.off_offs = c.take((rows + 1) * 4);
+    if (path == TK_PATH_SHORT) {
+        L.list_stride = align_up(rows * 4, 256) / 4;
+        L.off_lists = c.take((size_t)SEG_CLASSES * L.list_stride * 4);
+    } else {
+        L.inner_bytes = rows == 1 ? seg_inner_bytes(n) : labsort_segments_workspace_bytes(n, rows, L.m, 1);
+        L.off_inner = c.take(L.inner_bytes);
+    }
+    L.total = c.o;
+    return L;
+}
+TopkLayout topk_layout(size_t rows, size_t cols, size_t k) {
+    const int path = topk_path(rows, cols, k);
+    TopkLayout L = topk_layout_path(rows, cols, k, path);
+    // never less than the largest select below the threshold: the size does not shrink as k grows
+    if (path == TK_PATH_SORT && cols / TK_SORT_DIV >= 1)
+        L.total = std::max(L.total, topk_layout_path(rows, cols, cols / TK_SORT_DIV, TK_PATH_SELECT).total);
+    return L;
+}
+bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+}  // namespace
+
+size_t labsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k) {
+    if (rows == 0 || k == 0 || k > cols || rows > (size_t)0x7FFFFFFFu / cols) return TK_HDR_BYTES;
+    return topk_layout(rows, cols, k).total;
+}
+
+int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, int largest, int key_type,
+                        void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
+    if (rows == 0 || k == 0) return LABSORT_OK;
+    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
+    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
+    if (ranges_overlap(d_keys, rows * cols * 4, d_keys_out, rows * k * 4)) return LABSORT_ERR_ARG;
+    if (d_idx_out && ranges_overlap(d_keys, rows * cols * 4, d_idx_out, rows * k * 4)) return LABSORT_ERR_ARG;
+    const int path = topk_path(rows, cols, k);
+    // the survivors of several long rows are ordered by the segmented sort: past its LDS tile, its general path
+    if (path == TK_PATH_SELECT && rows > 1 && k > (size_t)SEG_TILE_PAIRS && rows * k > RADIX_MAX_N) return LABSORT_ERR_ARG;
+    if (!d_ws || ws_bytes < labsort_topk_workspace_bytes(rows, cols, k)) return LABSORT_ERR_ARG;
+    const TopkLayout L = topk_layout_path(rows, cols, k, path);
+    const uint32_t xr = flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t *>(ws + off); };
+    const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
+    uint32_t *hdr = W(0), *A = W(L.off_a), *B = W(L.off_b), *SU = W(L.off_su), *SP = W(L.off_sp), *offs = W(L.off_offs);
+    uint32_t *ko = static_cast<uint32_t *>(d_keys_out);
+    const size_t n = rows * L.m;
+    HIP_TRY(launch_zero(ws, L.zero_bytes, s));  // (a kernel: graph-replayable)
+    if (path == TK_PATH_SHORT) {
+        // whole rows through the segmented sort's LDS classes, on (key, position) with xr as the flip
+        TimingScope ts(LABSORT_K_TOPK, s);
+        uint32_t *lists = W(L.off_lists);
+        HIP_TRY(launch_topk_offsets(offs, rows, cols, s));
+        HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, s));
+        HIP_TRY(launch_seg_bin(offs, rows, n, cols, true, true, hdr, lists, L.list_stride, s));
+        HIP_TRY(launch_seg_lds_classes(cols, true, keys, SU, B, SP, offs, hdr, lists, L.list_stride, xr, s));
+        HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, cols, k, 0u, s));  // (the class kernels wrote keys, not u)
+        return LABSORT_OK;
+    }
+    if (path == TK_PATH_SELECT) {
+        TimingScope ts(LABSORT_K_TOPK, s);
+        TkArgs a{};
+        a.keys = keys;
+        a.hist = W(L.off_hist);
+        a.cnt = W(L.off_cnt);
+        a.low = W(L.off_low);
+        a.eq = W(L.off_eq);
+        a.lowbase = W(L.off_lowbase);
+        a.eqbase = W(L.off_eqbase);
+        a.st = reinterpret_cast<TkState *>(ws + L.off_st);
+        a.cand_u = W(L.off_cand_u);
+        a.cand_p = W(L.off_cand_p);
+        a.surv_u = A;
+        a.surv_p = B;
+        a.cols = (uint32_t)cols;
+        a.k = (uint32_t)k;
+        a.nch = (uint32_t)L.nch;
+        a.capa = (uint32_t)L.capa;
+        a.cap = (uint32_t)L.cap;
+        a.xr = xr;
+        for (int level = 0; level < TK_LEVELS; ++level) {
+            HIP_TRY(launch_topk_hist(a, rows, level, s));
+            HIP_TRY(launch_topk_reduce(a, rows, level, s));
+            HIP_TRY(launch_topk_scan(a, rows, level, s));
+            if (level < TK_LEVELS - 1 && L.cap > 0) HIP_TRY(launch_topk_narrow(a, rows, level, s));
+        }
+        HIP_TRY(launch_topk_final(a, rows, s));
+    } else {
+        TimingScope ts(LABSORT_K_TOPK, s);
+        HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, s));
+    }
+    // order the m pairs of every row on u (stable): one pair sort, or the segmented pair sort
+    char *iws = ws + L.off_inner;
+    uint32_t *ierr = reinterpret_cast<uint32_t *>(iws);
+    HIP_TRY(launch_zero(ierr, 16, s));  // (a one-tile inner sort has no error word of its own)
+    int st;
+    if (rows == 1) {
+        if ((st = labsort_sort_pairs_device(A, B, SU, SP, n, LABSORT_KEY_U32, LABSORT_ALGO_AUTO, iws, L.inner_bytes, stream)))
+            return st;
+    } else {
+        {
+            TimingScope ts(LABSORT_K_TOPK, s);
+            HIP_TRY(launch_topk_offsets(offs, rows, L.m, s));
+        }
+        if ((st = labsort_sort_segments_pairs_device(A, B, SU, SP, n, offs, rows, L.m, LABSORT_KEY_U32, iws, L.inner_bytes,
+                                                     stream)))
+            return st;
+    }
+    TimingScope ts(LABSORT_K_TOPK, s);
+    HIP_TRY(launch_topk_err_acc(hdr, ierr, 2, s));
+    HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, L.m, k, xr, s));
+    return LABSORT_OK;
+}
+
+int labsort_topk_workspace_status(const void *d_ws, void *stream) {
+    uint32_t w = 0;
+    if (const int st = read_ws_words(d_ws, &w, 1, as_stream(stream))) return st;
+    return w ? LABSORT_ERR_DEVICE : LABSORT_OK;
+}
+
+}  // extern "C"

@@ -421,6 +421,46 @@ def test_timing_hooks(ls, oracle, torch_gpu, monkeypatch, impl):
     assert cnt2 == (1 if impl == "gather" else 0)
 
 
+MERGE_CLASSES, RADIX_CLASSES = ("tile_sort", "merge", "merge4"), ("histogram", "onesweep")
+
+
+@pytest.mark.parametrize("pairs,algo,n,classes,counts", [
+    (False, "merge", 1 << 20, MERGE_CLASSES, (1, 1, 2)),
+    (False, "merge", (1 << 20) + 1, MERGE_CLASSES, (1, 0, 3)),
+    (True, "merge", 1 << 20, MERGE_CLASSES, (1, 0, 3)),
+    (True, "merge", (1 << 20) + 1, MERGE_CLASSES, (1, 1, 3)),
+    (True, "radix", 1 << 20, RADIX_CLASSES, (1, 4)),
+], ids=["keys-merge-2^20", "keys-merge-2^20+1", "pairs-merge-2^20", "pairs-merge-2^20+1", "pairs-radix-2^20"])
+def test_driver_launch_structure(ls, oracle, torch_gpu, pairs, algo, n, classes, counts):
+    """The launches of the merge and 8-bit radix drivers, keys only and key/value, as the timing
+    scopes count them.  Merge: one tile sort, then the levels above the tile (32768 keys, 16384
+    pairs) two per four-way pass, an odd level first as one pairwise pass.  Radix with payloads:
+    one histogram, four onesweep passes.  The result is checked against the oracle."""
+    torch = torch_gpu
+    assert (ls.tile_keys(), ls.pair_tile_keys()) == (32768, 16384)
+    a = oracle.gen(n, SEED + 90, "u32")
+    t = to_dev(torch, a)
+    o = torch.empty_like(t)
+    v, vo = torch.arange(n, dtype=torch.int32, device="cuda"), torch.empty_like(t)
+    ls.timing_enable(True)
+    try:
+        if pairs:
+            ls.sort_pairs_device(t, v, o, vo, n, algo=algo)
+        else:
+            ls.sort_device(t, o, n, algo=algo)
+        torch.cuda.synchronize()
+        got = tuple(ls.timing_read(c)[1] for c in classes)
+    finally:
+        ls.timing_enable(False)
+    if pairs:
+        ek, ev = oracle.stable_sort_pairs(a, np.arange(n, dtype=np.uint32), "u32")
+        np.testing.assert_array_equal(from_dev(vo), ev)
+    else:
+        ek = oracle.sort_u32(a)
+    np.testing.assert_array_equal(from_dev(o), ek)
+    assert got == counts
+
+
 # ---- segmented look-back chains: pass structure edge cases ----------------------------
 @pytest.mark.parametrize("mask,name", [
     (0xFFFF00FF, "trivial middle pass (byte 1 constant)"),

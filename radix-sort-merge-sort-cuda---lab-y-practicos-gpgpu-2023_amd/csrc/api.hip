@@ -273,7 +273,7 @@ int sort_merge(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *v
             lv += 2;
         } else {
             TimingScope ts(LABSORT_K_MERGE, s);
-            HIP_TRY(launch_merge_pass(ck, nk, n, run, flip, nullptr, s, cv, nv, nullptr,
+            HIP_TRY(launch_merge_pass(ck, nk, n, run, flip, s, cv, nv, nullptr,
                                       next_is_four(lv + 1) ? samp[sb] : nullptr));
             run *= 2;
             lv += 1;
@@ -656,7 +656,7 @@ int labsort_merge_pass(const void *d_in, void *d_out, size_t n, size_t run, int 
     if (run == 0 || (run & (run - 1)) != 0 || 2 * run < (size_t)MG_TILE) return LABSORT_ERR_ARG;
     TimingScope ts(LABSORT_K_MERGE, as_stream(stream));
     HIP_TRY(launch_merge_pass(static_cast<const uint32_t *>(d_in), static_cast<uint32_t *>(d_out), n, run,
-                              flip_of(key_type), d_part, as_stream(stream)));
+                              flip_of(key_type), as_stream(stream)));
     return LABSORT_OK;
 }
 
@@ -717,7 +717,7 @@ int labsort_merge_runs(const void *d_in, void *d_out, const size_t *h_offsets, i
             pr.pb[0] = 0;
             pr.pb[1] = (uint32_t)(b1 - a0);
             pr.la[0] = (uint32_t)(a1 - a0);
-            HIP_TRY(launch_merge_pass(src + a0, dst + a0, b1 - a0, 0, flip, nullptr, s, nullptr, nullptr, &pr));
+            HIP_TRY(launch_merge_pass(src + a0, dst + a0, b1 - a0, 0, flip, s, nullptr, nullptr, &pr));
         }
         no.push_back(o.back());
         o.swap(no);

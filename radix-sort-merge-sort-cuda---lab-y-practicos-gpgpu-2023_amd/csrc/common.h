@@ -160,7 +160,7 @@ hipError_t launch_tile_sort(const uint32_t *in, uint32_t *out, size_t n, uint32_
                             uint32_t *samp_out = nullptr);
 hipError_t launch_wave_tile_sort(uint32_t *keys, size_t n, uint32_t flip, hipStream_t s);
 hipError_t launch_merge_pass(const uint32_t *in, uint32_t *out, size_t n, size_t run, uint32_t flip,
-                             uint32_t *part, hipStream_t s, const uint32_t *vin = nullptr, uint32_t *vout = nullptr,
+                             hipStream_t s, const uint32_t *vin = nullptr, uint32_t *vout = nullptr,
                              const MgPairs *pairs = nullptr, uint32_t *samp_out = nullptr);
 hipError_t launch_tile_sort_kv(const uint32_t *in, uint32_t *out, const uint32_t *vin, uint32_t *vout, size_t n,
                                uint32_t flip, hipStream_t s, uint32_t *samp_out = nullptr);

@@ -79,7 +79,13 @@ __device__ __forceinline__ uint64_t lds_peers(uint64_t *slot, uint32_t lane) {
 // that hit one address in ascending lane order, on five sharing patterns (all lanes,
 // contiguous groups, strided groups, two scrambled ones).  Call with the whole wave
 // active; `scratch` = 64 words of LDS private to the wave.
+// LABSORT_RANK_FALLBACK=1 (A/B and test builds): answer false, so every kernel ranks by
+// rank8's ballot path, which lane-ordered hardware otherwise never runs.
+#ifndef LABSORT_RANK_FALLBACK
+#define LABSORT_RANK_FALLBACK 0
+#endif
 __device__ __forceinline__ bool lds_lane_ordered(uint32_t *scratch, uint32_t lane) {
+    if constexpr (LABSORT_RANK_FALLBACK != 0) return false;
     bool ok = true;
 #pragma unroll
     for (int p = 0; p < 5; ++p) {
@@ -110,6 +116,71 @@ __device__ __forceinline__ uint32_t wave_atomic_rank(uint32_t *wh, uint32_t d, u
     return __hip_atomic_fetch_add(wh + d, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
+// Stable rank of 8-bit digit d among this wave's keys so far, on the wave's counters wh:
+// the returning atomic where lanes are ordered (atomic_rank, wave-uniform), else the
+// lanes with my digit by 8 ballots and one add by the first of them.  All 64 lanes active.
+__device__ __forceinline__ uint32_t rank8(uint32_t *wh, uint32_t d, uint32_t lane, bool atomic_rank) {
+    if (atomic_rank) return wave_atomic_rank(wh, d, lane);
+    const uint64_t m = match8(d);
+    const uint32_t pre = mbcnt64(m);
+    const uint32_t old = wh[d];
+    if (pre == 0) wh[d] = old + (uint32_t)__popcll(m);
+    return old + pre;
+}
+
+// lds_lane_ordered once per workgroup: wave 0 probes (`scratch`: 64 LDS words) and
+// publishes the answer in *flag; after the next barrier lane_order_probed reads it
+// wave-uniformly.
+__device__ __forceinline__ void probe_lane_order(uint32_t *scratch, uint32_t *flag, uint32_t lane, uint32_t wid) {
+    if (wid == 0) {
+        const bool ord = lds_lane_ordered(scratch, lane);
+        if (lane == 0) *flag = ord ? 1u : 0u;
+    }
+}
+__device__ __forceinline__ bool lane_order_probed(const uint32_t *flag) {
+    return __builtin_amdgcn_readfirstlane(*flag) != 0u;
+}
+
+// Two 16-bit values (wave-local ranks, LDS slots) per register: value j of p.
+template <int N>
+__device__ __forceinline__ uint32_t get16(const uint32_t (&p)[N], int j) {
+    return (p[j / 2] >> ((j & 1) * 16)) & 0xFFFFu;
+}
+template <int N>
+__device__ __forceinline__ void set16(uint32_t (&p)[N], int j, uint32_t v) {
+    __builtin_assume(v < 65536u);  // (spares the mask of a half that is filled first)
+    p[j / 2] = (j & 1) ? (p[j / 2] & 0xFFFFu) | (v << 16) : (p[j / 2] & 0xFFFF0000u) | v;
+}
+
+// AND and OR of a value pair over the wave (all lanes get both); with a = o = key ^ flip
+// over a set of keys, a ^ o is the bits the keys differ in.
+__device__ __forceinline__ void wave_and_or(uint32_t &a, uint32_t &o) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a &= __shfl_xor(a, off);
+        o |= __shfl_xor(o, off);
+    }
+}
+// The bits the workgroup's keys differ in, from each lane's AND / OR: over the wave, then
+// over the W waves through red_and / red_or (W words each).  Contains a barrier.
+template <int W>
+__device__ __forceinline__ uint32_t block_diff_bits(uint32_t a, uint32_t o, uint32_t *red_and, uint32_t *red_or,
+                                                    uint32_t lane, uint32_t wid) {
+    wave_and_or(a, o);
+    if (lane == 0) {
+        red_and[wid] = a;
+        red_or[wid] = o;
+    }
+    __syncthreads();
+    uint32_t aa = ~0u, oo = 0u;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        aa &= red_and[w];
+        oo |= red_or[w];
+    }
+    return aa ^ oo;
+}
+
 // Exclusive scan over the first R threads of the block (value v in thread tid < R,
 // others pass 0).  Must be called by every thread (contains a barrier when R > 64).
 template <int BLOCK, int R>
@@ -132,6 +203,36 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum) 
         x += add;
     }
     return x - v;
+}
+
+// Digit d = tid < 256 of a tile ranked by W waves: its count over the waves and its first
+// slot in the digit-ordered tile (meaningless in threads 256 and up).
+struct DigitSpan {
+    uint32_t tot, start;
+};
+// whist[w * 256 + d] = wave w's count of digit d on entry (complete: after a barrier),
+// the first slot of wave w's keys of digit d on return (visible after the next barrier):
+// with the tile-wide offsets folded in, the reorder reads one LDS word per key (r17).
+// Must be called by every thread.
+template <int BLOCK, int W>
+__device__ __forceinline__ DigitSpan fold_digit_offsets(uint32_t *whist, uint32_t *wsum) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t tot = 0;
+    if (tid < 256u) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) tot += whist[w * 256 + tid];
+    }
+    const uint32_t ds = block_excl_scan<BLOCK, 256>(tot, wsum);
+    if (tid < 256u) {
+        uint32_t run = ds;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const uint32_t c = whist[w * 256 + tid];
+            whist[w * 256 + tid] = run;
+            run += c;
+        }
+    }
+    return {tot, ds};
 }
 
 // Stable rank of KPT digits per lane inside one wave (slot-major order: slot j of

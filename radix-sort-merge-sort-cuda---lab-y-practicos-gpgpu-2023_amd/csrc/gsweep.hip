@@ -567,10 +567,7 @@ __global__ __launch_bounds__(GB, GS_WAVES_PER_EU) void k_gsweep(const uint32_t *
     const uint32_t shift = (uint32_t)pass * 8u;
 
     for (uint32_t i = tid; i < (uint32_t)(GW * 256); i += GB) sm.wh[i] = 0u;
-    if (wid == 0) {
-        const bool ord = lds_lane_ordered(sm.probe, lane);
-        if (lane == 0) sm.ordered = ord ? 1u : 0u;
-    }
+    probe_lane_order(sm.probe, &sm.ordered, lane, wid);
     uint32_t k[GK];
     if (cur == 0) {
         const uint32_t *s = src + L0 + wid * (GK * WAVE) + lane;
@@ -588,26 +585,13 @@ __global__ __launch_bounds__(GB, GS_WAVES_PER_EU) void k_gsweep(const uint32_t *
         else gs_gather(src, cur == 1 ? tA : tB, T, L0, nvalid, sentinel, sm.g, k, tid, lane, wid);
         __syncthreads();
     }
-    const bool atomic_rank = __builtin_amdgcn_readfirstlane(sm.ordered) != 0u;
+    const bool atomic_rank = lane_order_probed(&sm.ordered);
 
     // stable wave rank (slot-major order = position order), two 16-bit ranks per register
     uint32_t *wh = sm.wh + wid * 256;
-    uint32_t rk[GK / 2];
+    uint32_t rk[GK / 2] = {};
 #pragma unroll
-    for (int j = 0; j < GK; ++j) {
-        const uint32_t d = ((k[j] ^ flip) >> shift) & 255u;
-        uint32_t r;
-        if (atomic_rank) {
-            r = wave_atomic_rank(wh, d, lane);
-        } else {
-            const uint64_t m = match8(d);
-            const uint32_t pre = mbcnt64(m);
-            const uint32_t old = wh[d];
-            if (pre == 0) wh[d] = old + (uint32_t)__popcll(m);
-            r = old + pre;
-        }
-        rk[j / 2] = (j & 1) ? rk[j / 2] | (r << 16) : r;
-    }
+    for (int j = 0; j < GK; ++j) set16(rk, j, rank8(wh, ((k[j] ^ flip) >> shift) & 255u, lane, atomic_rank));
     // pass 0: digit min / max over the valid keys (for the later passes' skip test)
     if (pass == 0) {
         uint32_t mn = 0xFFFFFFFFu, mx = 0u;  // bytes: digits 0..3 of (key ^ flip)
@@ -649,22 +633,10 @@ __global__ __launch_bounds__(GB, GS_WAVES_PER_EU) void k_gsweep(const uint32_t *
     __syncthreads();  // (1) wave counts
 
     // tile histogram, local digit offsets, per-wave offsets
-    uint32_t tot = 0;
+    const DigitSpan dg = fold_digit_offsets<GB, GW>(sm.wh, sm.wsum);
     if (tid < 256u) {
-#pragma unroll
-        for (int w = 0; w < GW; ++w) tot += sm.wh[w * 256 + tid];
-    }
-    const uint32_t ds = block_excl_scan<GB, 256>(tot, sm.wsum);
-    if (tid < 256u) {
-        uint32_t run = ds;
-#pragma unroll
-        for (int w = 0; w < GW; ++w) {
-            const uint32_t c = sm.wh[w * 256 + tid];
-            sm.wh[w * 256 + tid] = run;
-            run += c;
-        }
-        const uint32_t cnt = tid == 255u ? tot - ((uint32_t)GT - nvalid) : tot;  // drop sentinels
-        (FUSED && dst == bufB ? rt2 : rt)[(size_t)T * 256 + tid] = ds | (cnt << 16);
+        const uint32_t cnt = tid == 255u ? dg.tot - ((uint32_t)GT - nvalid) : dg.tot;  // drop sentinels
+        (FUSED && dst == bufB ? rt2 : rt)[(size_t)T * 256 + tid] = dg.start | (cnt << 16);
         if (FUSED && cnt && !(nozero && pass == 0))
             atomicAdd(acc + ((size_t)pass * GS_FSLOTS + T % GS_FSLOTS) * 256 + tid, cnt);  // next pass's totals
     }
@@ -698,7 +670,7 @@ __global__ __launch_bounds__(GB, GS_WAVES_PER_EU) void k_gsweep(const uint32_t *
 #pragma unroll
     for (int j = 0; j < GK; ++j) {
         const uint32_t d = ((k[j] ^ flip) >> shift) & 255u;
-        sm.keys[gs_pad(wh[d] + ((rk[j / 2] >> ((j & 1) * 16)) & 0xFFFFu))] = k[j];
+        sm.keys[gs_pad(wh[d] + get16(rk, j))] = k[j];
     }
     __syncthreads();  // (3) tile sorted in LDS
     if (nvalid == (uint32_t)GT) {

@@ -19,15 +19,20 @@
 //                     global offsets, LDS reorder, coalesced scatter; <true>: key/value.
 //                     (k_onesweep: the non-persistent form, 1-bit digits for radix1.)
 //   k_tile_sort       stage 1+2 of order_array (lab.cu:323-346): an LDS-resident
-//                     32768-key (16384 pairs) LSD radix sort per workgroup.
+//                     32768-key (16384 pairs) LSD radix sort per workgroup.  Its passes are
+//                     lds_sort_passes (lds_pass.h), which k_seg_block (segsort.hip) runs too.
 //   k_merge_pass_p    stage 3 (separators_kernel :209-270 + merge_segments_kernel
 //                     :272-300) as merge-path: co-rank searches per output tile
 //                     (busquedaPorBiparticion :102-132, same tie rule: A before B on
 //                     equal keys) and an LDS merge per tile; k_merge_ab: two arrays.
 //                     The four-way pass of the merge sort is in merge4.hip, the
 //                     gathered radix (2^16 <= n < 2^25) in gsweep.hip.
+// The pieces of an 8-bit LDS digit pass that these kernels, gsweep.hip and segsort.hip share
+// are in devutil.h: rank8 (the rank and its ballot fallback), probe_lane_order /
+// lane_order_probed, fold_digit_offsets, block_diff_bits, get16 / set16.
 #include "common.h"
 #include "devutil.h"
+#include "lds_pass.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -129,6 +134,21 @@ __global__ __launch_bounds__(HIST_BLOCK) void k_histogram(const uint32_t *__rest
 // pass plan: skip passes whose digit is the same for every key; choose buffers so
 // the last non-trivial pass writes OUT and no pass scatters in place.
 // ---------------------------------------------------------------------------------
+// The buffers of the k active passes act[0..k) (plan->src / dst; the skipped passes' entries
+// are set by the caller) and plan->copy_from.  The last pass writes OUT and the passes before
+// it alternate backwards; if the first pass would then read and write OUT (in place, k odd),
+// they alternate forwards from TMP instead and the result is copied from the last one's buffer.
+__device__ void plan_buffers(Plan *__restrict__ plan, const int *act, int k, int in_is_out) {
+    const bool from_tmp = in_is_out && (k & 1);
+    uint32_t src = SEL_IN;
+    for (int i = 0; i < k; ++i) {
+        const bool to_out = from_tmp ? (i & 1) : !((k - 1 - i) & 1);
+        plan->src[act[i]] = src;
+        plan->dst[act[i]] = src = to_out ? SEL_OUT : SEL_TMP;
+    }
+    plan->copy_from = (k == 0 && in_is_out) || src == SEL_OUT ? SEL_SKIP : src;
+}
+
 __global__ __launch_bounds__(256) void k_plan(const uint32_t *__restrict__ hist, uint32_t n, int bits,
                                               int in_is_out, Plan *__restrict__ plan) {
     __shared__ uint32_t triv[MAX_PASSES];
@@ -148,25 +168,7 @@ __global__ __launch_bounds__(256) void k_plan(const uint32_t *__restrict__ hist,
         if (p < P && !triv[p]) act[k++] = p;
     }
     plan->active = (uint32_t)k;
-    if (k == 0) {
-        plan->copy_from = in_is_out ? SEL_SKIP : SEL_IN;
-        return;
-    }
-    uint32_t d[MAX_PASSES];
-    uint32_t cur = SEL_OUT;
-    for (int i = k - 1; i >= 0; --i) {
-        d[i] = cur;
-        cur = (cur == SEL_OUT) ? SEL_TMP : SEL_OUT;
-    }
-    if (in_is_out && d[0] == SEL_OUT)  // first pass would read and write the same buffer
-        for (int i = 0; i < k; ++i) d[i] = (i & 1) ? SEL_OUT : SEL_TMP;
-    uint32_t src = SEL_IN;
-    for (int i = 0; i < k; ++i) {
-        plan->src[act[i]] = src;
-        plan->dst[act[i]] = d[i];
-        src = d[i];
-    }
-    plan->copy_from = (d[k - 1] == SEL_OUT) ? SEL_SKIP : d[k - 1];
+    plan_buffers(plan, act, k, in_is_out);
 }
 
 // ---------------------------------------------------------------------------------
@@ -325,25 +327,14 @@ __global__ __launch_bounds__(HIST_BLOCK) void k_hist_seg(const uint32_t *__restr
 // hs[s][d] (s < NSEG) and segment starts.  256 threads (one per digit).
 __device__ void build_segplan(SegPlan *__restrict__ sp, const uint32_t *__restrict__ hs, const uint32_t *start,
                               uint32_t mode, uint32_t *sh /* LDS: NSEG*256 + 8 words */) {
-    const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint32_t tot = 0;
     for (int s = 0; s < NSEG; ++s) {
         const uint32_t v = hs[s * 256 + t];
         sh[s * 256 + t] = v;
         tot += v;
     }
-    uint32_t x = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= (uint32_t)off) x += y;
-    }
-    uint32_t *wsum = sh + NSEG * 256;
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    uint32_t add = 0;
-    for (uint32_t w = 0; w < wid; ++w) add += wsum[w];
-    uint32_t run = x + add - tot;  // global start of digit t
+    uint32_t run = block_excl_scan<256, 256>(tot, sh + NSEG * 256);  // global start of digit t
     for (int s = 0; s < NSEG; ++s) {
         sp->base[s * 256 + t] = run;
         run += sh[s * 256 + t];
@@ -374,7 +365,7 @@ __device__ void build_segplan(SegPlan *__restrict__ sp, const uint32_t *__restri
 __device__ void build_segplan_later(SegPlan *__restrict__ out, int q, uint32_t prev, uint32_t n, int seg_later,
                                     const uint32_t *hist, const uint32_t *__restrict__ joint, uint32_t *sh,
                                     uint32_t *start) {
-    const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
+    const uint32_t t = threadIdx.x;
     if (seg_later <= 0 || prev + 1u != (uint32_t)q) {  // one chain over the whole input
         for (int s = 0; s < NSEG; ++s) sh[s * 256 + t] = s ? 0u : hist[q * 256 + t];
         if (t <= (uint32_t)NSEG) start[t] = t ? n : 0u;
@@ -383,18 +374,8 @@ __device__ void build_segplan_later(SegPlan *__restrict__ out, int q, uint32_t p
         return;
     }
     // segment starts: exclusive prefix over nibble groups of hist[prev]
-    const uint32_t v = hist[prev * 256 + t];
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= (uint32_t)off) x += y;
-    }
-    if (lane == 63) sh[NSEG * 256 + wid] = x;
-    __syncthreads();
-    uint32_t add = 0;
-    for (uint32_t w = 0; w < wid; ++w) add += sh[NSEG * 256 + w];
-    if ((t & 15u) == 0) start[t >> 4] = x + add - v;
+    const uint32_t ex = block_excl_scan<256, 256>(hist[prev * 256 + t], sh + NSEG * 256);
+    if ((t & 15u) == 0) start[t >> 4] = ex;
     if (t == 0) start[NSEG] = n;
     __syncthreads();
     build_segplan(out, joint + (size_t)q * NSEG * 256, start, 1u, sh);
@@ -472,30 +453,11 @@ __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps,
         }
         for (int i = 0; i + 1 < k; ++i) {
             plan->next[act[i]] = (uint32_t)act[i + 1];
-            prevs[act[i + 1]] = (uint32_t)act[i];
+            plan->prev[act[i + 1]] = prevs[act[i + 1]] = (uint32_t)act[i];
         }
         plan->active = (uint32_t)k;
         first = k ? act[0] : -1;
-        if (k == 0) {
-            plan->copy_from = in_is_out ? SEL_SKIP : SEL_IN;
-        } else {
-            uint32_t d[4];
-            uint32_t cur = SEL_OUT;
-            for (int i = k - 1; i >= 0; --i) {
-                d[i] = cur;
-                cur = (cur == SEL_OUT) ? SEL_TMP : SEL_OUT;
-            }
-            if (in_is_out && d[0] == SEL_OUT)
-                for (int i = 0; i < k; ++i) d[i] = (i & 1) ? SEL_OUT : SEL_TMP;
-            uint32_t src = SEL_IN;
-            for (int i = 0; i < k; ++i) {
-                plan->src[act[i]] = src;
-                plan->dst[act[i]] = d[i];
-                plan->prev[act[i]] = i ? (uint32_t)act[i - 1] : NEXT_NONE;
-                src = d[i];
-            }
-            plan->copy_from = (d[k - 1] == SEL_OUT) ? SEL_SKIP : d[k - 1];
-        }
+        plan_buffers(plan, act, k, in_is_out);
     }
     __syncthreads();
     if (first < 0 || me < first) return;
@@ -820,12 +782,11 @@ void k_onesweep_p(Bufs bufs, const Plan *__restrict__ plan, int pass, uint32_t n
         sm.next = c0;
         sm.next2 = (PF && c0 != OSP_DONE) ? acquire() : OSP_DONE;
     }
-    if (wid == 0) {
-        const bool ord = lds_lane_ordered(sm.probe, lane);
-        if (lane == 0) sm.ordered = ord ? 1u : 0u;
-    }
+    probe_lane_order(sm.probe, &sm.ordered, lane, wid);
     __syncthreads();
     uint32_t cB = sm.next, cC = sm.next2;
+    // (lane_order_probed, written out: read through the helper, the key/value pass is compiled to
+    // 6460 instructions instead of 5743, with other spills: 1 VGPR and 2 SGPRs instead of 2 VGPRs)
     const bool atomic_rank = __builtin_amdgcn_readfirstlane(sm.ordered) != 0u;
 
     // carried state of tile A (slot = look-back slot, lo = slot of its segment's first tile)
@@ -1052,7 +1013,7 @@ void k_onesweep_p(Bufs bufs, const Plan *__restrict__ plan, int pass, uint32_t n
         __syncthreads();  // (3) wave offsets of B
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
-            const uint32_t pos = osp_pad(wh[((kB[j] ^ flip) >> shift) & 255u] + ((rB[j / 2] >> ((j & 1) * 16)) & 0xFFFFu));
+            const uint32_t pos = osp_pad(wh[((kB[j] ^ flip) >> shift) & 255u] + get16(rB, j));
             sm.keys[pos] = kB[j];
             if constexpr (KV) sm.vals[pos] = vB[j];
         }
@@ -1091,22 +1052,8 @@ void k_onesweep_p(Bufs bufs, const Plan *__restrict__ plan, int pass, uint32_t n
 // ---------------------------------------------------------------------------------
 // LDS-resident tile sort: 8-bit LSD passes entirely in LDS, one global read and write
 // ---------------------------------------------------------------------------------
-template <int BLOCK, int KPT, bool KV = false>
-struct TsSmem {
-    static constexpr int R = 256, W = BLOCK / WAVE, TILE = BLOCK * KPT;
-    uint32_t keys[TILE];
-    uint32_t vals[KV ? TILE : 1];  // key/value: the payload follows its key through every pass
-    uint32_t whist[W * R];
-    uint32_t wsum[W];
-    uint32_t red_and[W];
-    uint32_t red_or[W];
-    uint32_t probe[WAVE];
-    uint32_t ordered;
-};
-
-// One TILE-key tile per workgroup, sorted by up to four 8-bit LSD passes in LDS (passes
-// whose digit is uniform over the tile are skipped: the reference's "stop when sorted",
-// lab.cu:61, per tile).  KV: key/value pairs (vin/vout, 4-byte payloads); the sort is
+// One TILE-key tile per workgroup, sorted by up to four 8-bit LSD passes in LDS
+// (lds_sort_passes, lds_pass.h; TsSmem: its LDS).  KV: key/value pairs (vin/vout, 4-byte payloads); the sort is
 // stable, so equal keys keep their input order and their payloads with them.
 // Measured and not kept (r26): a persistent grid, the next tile's keys
 // loaded before the last pass, 16-B grouped loads and stores; r28: nontemporal output
@@ -1120,14 +1067,11 @@ __global__ __launch_bounds__(BLOCK, 4) void k_tile_sort(const uint32_t *in, uint
                                                          uint32_t *vout, uint32_t n, uint32_t flip,
                                                          uint32_t *samp_out = nullptr) {
     using S = TsSmem<BLOCK, KPT, KV>;
-    constexpr int R = S::R, W = S::W, TILE = S::TILE;
+    constexpr int W = S::W, TILE = S::TILE;
     __shared__ S sm;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
     const uint32_t sentinel = ~flip;
-    if (wid == 0) {  // lane-ordered LDS atomics (see k_onesweep_p): rank by one atomic per key
-        const bool ord = lds_lane_ordered(sm.probe, lane);
-        if (lane == 0) sm.ordered = ord ? 1u : 0u;
-    }
+    probe_lane_order(sm.probe, &sm.ordered, lane, wid);  // (see k_onesweep_p)
     const uint32_t base = blockIdx.x * (uint32_t)TILE;
     const uint32_t wbase = base + wid * (KPT * WAVE) + lane;
     uint32_t k[KPT];
@@ -1161,92 +1105,8 @@ __global__ __launch_bounds__(BLOCK, 4) void k_tile_sort(const uint32_t *in, uint
         }
     }
     // bits on which the tile's keys differ -> passes that are not the identity
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a &= __shfl_xor(a, off);
-        o |= __shfl_xor(o, off);
-    }
-    if (lane == 0) {
-        sm.red_and[wid] = a;
-        sm.red_or[wid] = o;
-    }
-    __syncthreads();
-    const bool atomic_rank = __builtin_amdgcn_readfirstlane(sm.ordered) != 0u;
-    uint32_t diff = 0;
-    {
-        uint32_t aa = ~0u, oo = 0u;
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            aa &= sm.red_and[w];
-            oo |= sm.red_or[w];
-        }
-        diff = aa ^ oo;
-    }
-    uint32_t *wh = sm.whist + wid * R;
-    for (int pass = 0; pass < 4; ++pass) {
-        const uint32_t shift = pass * 8;
-        if (((diff >> shift) & 0xFFu) == 0u) continue;  // uniform over the tile
-        for (uint32_t i = lane; i < (uint32_t)R; i += WAVE) wh[i] = 0u;
-        uint32_t rank[KPT / 2];  // two 16-bit wave-local ranks per register
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            // stable wave rank: lane-ordered returning atomic, else peers by 8 ballots
-            const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
-            uint32_t r;
-            if (atomic_rank) {
-                r = wave_atomic_rank(wh, d, lane);
-            } else {
-                const uint64_t m = match8(d);
-                const uint32_t pre = mbcnt64(m);
-                const uint32_t old = wh[d];
-                if (pre == 0) wh[d] = old + (uint32_t)__popcll(m);
-                r = old + pre;
-            }
-            rank[j / 2] = (j & 1) ? rank[j / 2] | (r << 16) : r;
-        }
-        __syncthreads();
-        // tile-wide digit offsets folded into the per-wave offsets: the reorder then
-        // reads one LDS word per key instead of two (r17)
-        uint32_t tot = 0;
-        if (tid < (uint32_t)R) {
-#pragma unroll
-            for (int w = 0; w < W; ++w) tot += sm.whist[w * R + tid];
-        }
-        const uint32_t ds = block_excl_scan<BLOCK, R>(tot, sm.wsum);
-        if (tid < (uint32_t)R) {
-            uint32_t run = ds;
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                const uint32_t c = sm.whist[w * R + tid];
-                sm.whist[w * R + tid] = run;
-                run += c;
-            }
-        }
-        __syncthreads();
-        // every destination first (replacing its 16-bit rank: dst < TILE), the stores after:
-        // interleaved, each counter read would wait for the store before it (the compiler
-        // cannot tell the stores from the counters), 32 LDS round trips in a row per wave
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
-            const uint32_t dst = wh[d] + ((rank[j / 2] >> ((j & 1) * 16)) & 0xFFFFu);
-            rank[j / 2] = (j & 1) ? (rank[j / 2] & 0xFFFFu) | (dst << 16) : (rank[j / 2] & 0xFFFF0000u) | dst;
-        }
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const uint32_t dst = (rank[j / 2] >> ((j & 1) * 16)) & 0xFFFFu;
-            sm.keys[dst] = k[j];
-            if constexpr (KV) sm.vals[dst] = v[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) k[j] = sm.keys[wid * (KPT * WAVE) + j * WAVE + lane];
-        if constexpr (KV) {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) v[j] = sm.vals[wid * (KPT * WAVE) + j * WAVE + lane];
-        }
-        // (the next pass's reorder writes sm.keys two barriers later)
-    }
+    const uint32_t diff = block_diff_bits<W>(a, o, sm.red_and, sm.red_or, lane, wid);
+    lds_sort_passes(sm, k, v, diff, flip, wid * (KPT * WAVE), lane_order_probed(&sm.ordered), AllGroups{}, lane, wid);
     // samp_out: every M4_S-th output key for a four-way merge pass next (merge4.hip)
     static_assert((KPT * WAVE) % M4_S == 0 && M4_S % WAVE == 0, "samples at lane 0 of fixed slots");
     if (samp_out && lane == 0) {
@@ -1878,12 +1738,11 @@ hipError_t launch_wave_tile_sort(uint32_t *keys, size_t n, uint32_t flip, hipStr
 }
 
 hipError_t launch_merge_pass(const uint32_t *in, uint32_t *out, size_t n, size_t run, uint32_t flip,
-                             uint32_t *part, hipStream_t s, const uint32_t *vin, uint32_t *vout, const MgPairs *pairs,
+                             hipStream_t s, const uint32_t *vin, uint32_t *vout, const MgPairs *pairs,
                              uint32_t *samp_out) {
     MgPairs pr{};
     if (pairs) pr = *pairs;
     if (n == 0) return hipSuccess;
-    (void)part;  // co-ranks are found inside k_merge_pass_p
     const uint32_t ntiles = (uint32_t)((n + MG_TILE - 1) / MG_TILE);
     const uint32_t want = (uint32_t)(MG_BLOCKS_PER_CU * cu_count());
     uint32_t m = (ntiles + want - 1) / want;  // consecutive tiles per workgroup

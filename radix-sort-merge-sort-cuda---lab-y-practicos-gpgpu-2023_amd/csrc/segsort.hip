@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "devutil.h"
+#include "lds_pass.h"
 #include "host.h"
 
 namespace labsort {
@@ -146,11 +147,7 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_seg_wave(const uint32_t
             a &= ok ? x : ~0u;
             o |= ok ? x : 0u;
         }
-#pragma unroll
-        for (int offx = 32; offx > 0; offx >>= 1) {
-            a &= __shfl_xor(a, offx);
-            o |= __shfl_xor(o, offx);
-        }
+        wave_and_or(a, o);
         const uint32_t diff = __builtin_amdgcn_readfirstlane(a ^ o);
         for (int pass = 0; pass < 4; ++pass) {
             const uint32_t shift = pass * 8;
@@ -162,18 +159,8 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_seg_wave(const uint32_t
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
                 rank[j] = 0u;
-                if ((uint32_t)j < jn) {  // wave-uniform; a group past the end holds padding only
-                    const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
-                    if (atomic_rank) {
-                        rank[j] = wave_atomic_rank(sm.hist, d, lane);
-                    } else {
-                        const uint64_t m = match8(d);
-                        const uint32_t pre = mbcnt64(m);
-                        const uint32_t old = sm.hist[d];
-                        if (pre == 0) sm.hist[d] = old + (uint32_t)__popcll(m);
-                        rank[j] = old + pre;
-                    }
-                }
+                if ((uint32_t)j < jn)  // wave-uniform; a group past the end holds padding only
+                    rank[j] = rank8(sm.hist, ((k[j] ^ flip) >> shift) & 0xFFu, lane, atomic_rank);
             }
             __builtin_amdgcn_wave_barrier();
             {  // exclusive scan of the 256 counters: four per lane, then across the wave
@@ -228,42 +215,29 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_seg_wave(const uint32_t
 }
 
 // ---------------------------------------------------------------------------------
-// block and tile classes: k_tile_sort's passes (kernels.hip) on one segment per workgroup.
-// The segment is striped over the waves in runs of S = 64 ceil(len / (64 W)) slots, so a
-// short segment of the class costs every wave the same few 64-key groups; groups that
-// start past the end are neither ranked nor read back.
+// block and tile classes: the passes k_tile_sort runs (lds_sort_passes, lds_pass.h) on one
+// segment per workgroup.  The segment is striped over the waves in runs of
+// S = 64 ceil(len / (64 W)) slots, so a short segment of the class costs every wave the same
+// few 64-key groups; groups that start past the end are neither ranked nor read back
+// (LeadingGroups).
 // ---------------------------------------------------------------------------------
 template <int BLOCK, int KPT, bool KV>
 __global__ __launch_bounds__(BLOCK, 4) void k_seg_block(const uint32_t *in, uint32_t *out, const uint32_t *vin,
                                                          uint32_t *vout, const uint32_t *__restrict__ off,
                                                          const uint32_t *__restrict__ hdr,
                                                          const uint32_t *__restrict__ list, int cls, uint32_t flip) {
-    constexpr int R = 256, W = BLOCK / WAVE;
-    constexpr uint32_t TILE = (uint32_t)BLOCK * KPT;
-    static_assert(TILE <= 65536u, "16-bit LDS slots");
-    struct S {
-        uint32_t keys[TILE];
-        uint32_t vals[KV ? TILE : 1];
-        uint32_t whist[W * R];
-        uint32_t wsum[W];
-        uint32_t red_and[W];
-        uint32_t red_or[W];
-        uint32_t probe[WAVE];
-        uint32_t ordered;
-    };
+    using S = TsSmem<BLOCK, KPT, KV>;
+    constexpr int W = S::W;
+    constexpr uint32_t TILE = S::TILE;
     __shared__ S sm;
     if (ld_agent(hdr) != 0u) return;  // rejected offsets: touch nothing
     const uint32_t cnt = hdr[SEG_HDR_CNT + cls];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t sentinel = ~flip;
     if (blockIdx.x >= cnt) return;  // (an empty class costs its launch only; uniform over the workgroup)
-    if (wid == 0) {
-        const bool ord = lds_lane_ordered(sm.probe, lane);
-        if (lane == 0) sm.ordered = ord ? 1u : 0u;
-    }
+    probe_lane_order(sm.probe, &sm.ordered, lane, wid);
     __syncthreads();
-    const bool atomic_rank = __builtin_amdgcn_readfirstlane(sm.ordered) != 0u;
-    uint32_t *wh = sm.whist + wid * R;
+    const bool atomic_rank = lane_order_probed(&sm.ordered);
     // the list entry and the two offsets are three dependent loads: those of the next segment
     // are issued before this one is sorted
     uint32_t nb = 0u, ne = 0u;
@@ -323,91 +297,8 @@ __global__ __launch_bounds__(BLOCK, 4) void k_seg_block(const uint32_t *in, uint
             a &= x;
             o |= ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) ? x : 0u;
         }
-#pragma unroll
-        for (int offx = 32; offx > 0; offx >>= 1) {
-            a &= __shfl_xor(a, offx);
-            o |= __shfl_xor(o, offx);
-        }
-        if (lane == 0) {
-            sm.red_and[wid] = a;
-            sm.red_or[wid] = o;
-        }
-        __syncthreads();
-        uint32_t diff = 0;
-        {
-            uint32_t aa = ~0u, oo = 0u;
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                aa &= sm.red_and[w];
-                oo |= sm.red_or[w];
-            }
-            diff = __builtin_amdgcn_readfirstlane(aa ^ oo);
-        }
-        for (int pass = 0; pass < 4; ++pass) {
-            const uint32_t shift = pass * 8;
-            if (((diff >> shift) & 0xFFu) == 0u) continue;  // uniform over the segment
-            for (uint32_t i = lane; i < (uint32_t)R; i += WAVE) wh[i] = 0u;
-            uint32_t rank[KPT / 2];  // two 16-bit ranks / slots per register, as k_tile_sort
-            // (the group count through an empty asm: the per-group compares are redone where they are
-            // used; hoisted out of the pass loop they were held in SGPRs across it and spilled)
-            uint32_t ngr = ng, ngs = ng, ngb = ng;
-            asm volatile("" : "+s"(ngr), "+s"(ngs), "+s"(ngb));
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                uint32_t r = 0u;
-                if ((uint32_t)j < ngr) {  // wave-uniform: the group holds keys
-                    const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
-                    if (atomic_rank) {
-                        r = wave_atomic_rank(wh, d, lane);
-                    } else {
-                        const uint64_t m = match8(d);
-                        const uint32_t pre = mbcnt64(m);
-                        const uint32_t old = wh[d];
-                        if (pre == 0) wh[d] = old + (uint32_t)__popcll(m);
-                        r = old + pre;
-                    }
-                }
-                rank[j / 2] = (j & 1) ? rank[j / 2] | (r << 16) : r;
-            }
-            __syncthreads();
-            uint32_t tot = 0;
-            if (tid < (uint32_t)R) {
-#pragma unroll
-                for (int w = 0; w < W; ++w) tot += sm.whist[w * R + tid];
-            }
-            const uint32_t ds = block_excl_scan<BLOCK, R>(tot, sm.wsum);
-            if (tid < (uint32_t)R) {
-                uint32_t run = ds;
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    const uint32_t c = sm.whist[w * R + tid];
-                    sm.whist[w * R + tid] = run;
-                    run += c;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const uint32_t d = ((k[j] ^ flip) >> shift) & 0xFFu;
-                const uint32_t dst = wh[d] + ((rank[j / 2] >> ((j & 1) * 16)) & 0xFFFFu);
-                rank[j / 2] = (j & 1) ? (rank[j / 2] & 0xFFFFu) | (dst << 16) : (rank[j / 2] & 0xFFFF0000u) | dst;
-            }
-            // ranked slots number the keys and the padding of the last group: dst < 64 ceil(len / 64) <= TILE
-#pragma unroll
-            for (int j = 0; j < KPT; ++j)
-                if ((uint32_t)j < ngs) {
-                    const uint32_t dst = (rank[j / 2] >> ((j & 1) * 16)) & 0xFFFFu;
-                    sm.keys[dst] = k[j];
-                    if constexpr (KV) sm.vals[dst] = v[j];
-                }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < KPT; ++j)
-                if ((uint32_t)j < ngb) {
-                    k[j] = sm.keys[ws0 + (uint32_t)j * WAVE + lane];
-                    if constexpr (KV) v[j] = sm.vals[ws0 + (uint32_t)j * WAVE + lane];
-                }
-        }
+        const uint32_t diff = __builtin_amdgcn_readfirstlane(block_diff_bits<W>(a, o, sm.red_and, sm.red_or, lane, wid));
+        lds_sort_passes(sm, k, v, diff, flip, ws0, atomic_rank, LeadingGroups{ng}, lane, wid);
         uint32_t nfs = nf, lout = lane;
         asm volatile("" : "+s"(nfs), "+v"(lout));
         if (nfs == (uint32_t)KPT) {

@@ -82,7 +82,8 @@ extern "C" {
 #define LABSORT_K_GCOPY 6        /* its final gathered copy */
 #define LABSORT_K_COPY 7         /* the streaming copy (labsort_copy: the bench's copy ceiling) */
 #define LABSORT_K_MERGE4 8       /* four-way merge pass of the merge sort (k_m4_rank + k_m4_merge) */
-#define LABSORT_K_SEGSORT 9      /* segmented sort: classification, the LDS class kernels, the general path's glue */
+#define LABSORT_K_SEGSORT 9      /* segmented sort: classification, the LDS class kernels, the general path's glue;
+                                    also the hybrid radix sort's finish (bucket offsets, lists, class kernels) */
 #define LABSORT_K_TOPK 10        /* top-k selection: the select's own kernels and the glue around the inner sorts */
 #define LABSORT_K_COUNT 11
 
@@ -118,6 +119,17 @@ int labsort_sort_host(void *h_keys, size_t n, int key_type, int algo);
  * reference's policy (CUDA_CHK after every launch, utils.h:18-26) checks launch status
  * only; this adds the kernels' own failure report. */
 int labsort_workspace_status(const void *d_workspace, size_t n, int algo, void *stream);
+/* Which path the last keys-only LABSORT_ALGO_RADIX sort of n keys on d_workspace took, after
+ * synchronising `stream`: 0 the classic four scatter passes (also: gathered passes, one tile,
+ * key/value sorts), 1 the hybrid path -- scatter passes on the two high digits, then every
+ * bucket of the top 16 bits sorted in LDS.  The choice is made on the device from the keys:
+ * hybrid when both low digits vary and no value of the top 14 bits has more than 20480 keys.
+ * LABSORT_RADIX_HYBRID (read per call): unset or =1 offers it for 15 * 2^24 <= n <= 19 * 2^24
+ * keys, where it measured faster; =0 never; =2 at every n the onesweep passes take, and up to
+ * 32768 keys per value of the top 14 bits, the bound that keeps it correct.  The workspace of
+ * the onesweep passes holds the path's counters, bucket offsets and lists at every n.
+ * A negative value: -LABSORT_ERR_HIP. */
+int labsort_radix_path(const void *d_workspace, size_t n, void *stream);
 /* The same for the last labsort_sort_pairs_device(n, algo) on d_workspace. */
 int labsort_pairs_workspace_status(const void *d_workspace, size_t n, int algo, void *stream);
 

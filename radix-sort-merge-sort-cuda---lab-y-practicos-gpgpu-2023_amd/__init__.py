@@ -44,7 +44,7 @@ C_SYMBOLS = [
     "labsort_count_descents", "labsort_timing_enable", "labsort_timing_read", "labsort_upper_bound", "sort",
     "labsort_merge_runs_workspace_bytes", "labsort_merge_runs",
     "labsort_pair_tile_keys", "labsort_pairs_workspace_bytes", "labsort_sort_pairs_device",
-    "labsort_workspace_status", "labsort_pairs_workspace_status",
+    "labsort_workspace_status", "labsort_pairs_workspace_status", "labsort_radix_path",
     "labsort_sort_host_multi", "labsort_sort_host_ranks", "labsort_multi_timing", "labsort_multi_last_hip_error",
     "labsort_multi_plan", "labsort_multi_error_detail", "labsort_multi_range_counts",
     "labsort_comm_unique_id", "labsort_comm_init_rccl", "labsort_comm_init_host", "labsort_comm_destroy",
@@ -152,6 +152,8 @@ def _load() -> ctypes.CDLL:
     L.labsort_pairs_workspace_bytes.argtypes = [sz, i]
     L.labsort_sort_pairs_device.argtypes = [p, p, p, p, sz, i, i, p, sz, p]
     L.labsort_workspace_status.argtypes = [p, sz, i, p]
+    if hasattr(L, "labsort_radix_path"):  # (an older build loaded through LABSORT_LIBRARY for an A/B has none)
+        L.labsort_radix_path.argtypes = [p, sz, p]
     L.labsort_sort_host_multi.argtypes = [p, sz, i, i]
     L.labsort_sort_host_ranks.argtypes = [p, sz, i, i, p, i]
     L.labsort_multi_timing.argtypes = [ctypes.POINTER(ctypes.c_double), i, ctypes.POINTER(sz)]
@@ -512,6 +514,15 @@ def workspace_status(workspace, n: int, algo: str = "radix", stream=None) -> Non
     """Synchronise `stream` and raise LabsortError(device-side error) if a kernel of the
     last sort_device(n, algo) on `workspace` reported a failure (labsort_workspace_status)."""
     _check(lib.labsort_workspace_status(_ptr(workspace), n, ALGO[algo], _stream(stream)), "sort_device (status)")
+
+
+def radix_path(workspace, n: int, stream=None) -> int:
+    """Synchronise `stream`; 1 if the last keys-only radix sort of n keys on `workspace` took the
+    hybrid path (two scatter passes, buckets finished in LDS), 0 for the classic passes."""
+    r = int(lib.labsort_radix_path(_ptr(workspace), n, _stream(stream)))
+    if r < 0:
+        _check(-r, "radix_path")
+    return r
 
 
 def pairs_workspace_status(workspace, n: int, algo: str = "radix", stream=None) -> None:

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "host.h"
+#include "segsort.h"
 
 using namespace labsort;
 
@@ -46,7 +47,7 @@ int labsort::fail_hip(hipError_t e) {
 }
 
 TimingScope::TimingScope(int c, hipStream_t st) : cls(c), s(st) {
-    if (!g_timing_on) return;
+    if (!g_timing_on || c == LABSORT_K_UNTIMED) return;
     if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
     (void)hipEventRecord(a, s);
 }
@@ -81,6 +82,9 @@ struct RadixLayout {
     size_t ntiles;  // look-back slots per pass (tiles + one partial tile per segment)
     size_t off_tmp, off_hist, off_hps, off_joint, off_counter, off_err, off_lookback, zero_bytes, off_plan,
         off_segplan, total;
+    // 8-bit, the hybrid path: its two counted fields and the finish's header in
+    // the zeroed block, the bucket offsets and class lists behind the plans
+    size_t off_hps2, off_top14, off_fin_hdr, off_fin_off, off_fin_lists;
 };
 
 // `tile`: keys per look-back slot of the pass kernel that will run (OSP_TILE for the
@@ -99,11 +103,16 @@ RadixLayout radix_layout(size_t n, int bits, size_t tile) {
     L.off_hist = c.take((size_t)L.P * L.R * 4);
     L.off_hps = c.take(bits == 8 ? (size_t)NSEG * 256 * 4 : 0);
     L.off_joint = c.take(bits == 8 ? (size_t)4 * NSEG * 256 * 4 : 0);
+    L.off_hps2 = c.take(bits == 8 ? (size_t)NSEG * 256 * 4 : 0);
+    L.off_top14 = c.take(bits == 8 ? (size_t)HY_TOP * 4 : 0);
+    L.off_fin_hdr = c.take(bits == 8 ? (size_t)SEG_HDR_BYTES : 0);
     L.off_counter = c.take((size_t)L.P * OSP_NCTR * 4);
     L.off_lookback = c.take((size_t)L.P * L.ntiles * L.R * 4);
     L.zero_bytes = c.o;
     L.off_plan = c.take(sizeof(Plan));
     L.off_segplan = c.take(bits == 8 ? 4 * sizeof(SegPlan) : 0);
+    L.off_fin_off = c.take(bits == 8 ? ((size_t)HY_BUCKETS + 1) * 4 : 0);
+    L.off_fin_lists = c.take(bits == 8 ? (size_t)SEG_CLASSES * HY_BUCKETS * 4 : 0);
     // the ping-pong key buffer last, 64 KiB aligned (tiles are 64 KiB of keys)
     L.off_tmp = align_up(c.o, 65536);
     L.total = align_up(L.off_tmp + n * 4, 256);
@@ -158,6 +167,17 @@ bool use_gather(size_t n) {
     return !(e && !std::strcmp(e, "onesweep"));
 }
 
+// LABSORT_RADIX_HYBRID (read per call): "0" the classic four passes only; unset or "1" the
+// hybrid launch sequence for keys-only sorts of HY_MIN_N..HY_MAX_N keys, the plan taking the
+// hybrid path up to HY_FAST_GROUP keys per top-14-bit group; "2" at any n the onesweep path
+// takes, up to the sound bound HY_MAX_BUCKET (tests).  Returns that bound, 0: not offered.
+uint32_t hybrid_gate(size_t n) {
+    const char *e = std::getenv("LABSORT_RADIX_HYBRID");
+    if (e && !std::strcmp(e, "0")) return 0u;
+    if (e && !std::strcmp(e, "2")) return HY_MAX_BUCKET;
+    return n >= HY_MIN_N && n <= HY_MAX_N ? HY_FAST_GROUP : 0u;
+}
+
 bool small_path(size_t n, int algo) { return algo != LABSORT_ALGO_RADIX1 && n <= (size_t)TS_TILE; }
 
 // 8-bit LSD radix of keys (vi == vo == nullptr) or (key, payload) pairs: the keys' segmented
@@ -185,17 +205,32 @@ int sort_radix8(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *
     uint32_t *hps = reinterpret_cast<uint32_t *>(ws + L.off_hps);
     uint32_t *joint = reinterpret_cast<uint32_t *>(ws + L.off_joint);
     SegPlan *sps = reinterpret_cast<SegPlan *>(ws + L.off_segplan);
+    // keys only, host gate open: the histogram counts the hybrid path's fields too and the plan
+    // chooses between the paths on the device.  The launch sequence is the same either way
+    // (captured graphs): on the hybrid path the launches of digits 0 and 1 return at once, on the
+    // classic path the finish's do.
+    const uint32_t hy_limit = vi ? 0u : hybrid_gate(n);
+    const bool hyb = hy_limit != 0u;
+    const HyCounts hc{reinterpret_cast<uint32_t *>(ws + L.off_hps2), reinterpret_cast<uint32_t *>(ws + L.off_top14), hy_limit};
     {
         TimingScope ts(LABSORT_K_HISTOGRAM, s);
-        HIP_TRY(launch_hist_seg(ki, n, flip, hps, joint, s));
+        HIP_TRY(launch_hist_seg(ki, n, flip, hps, joint, s, hyb ? &hc : nullptr));
     }
     // the look-back clear rides in the plan launch (k_plan8's workgroups 1..)
     HIP_TRY(launch_plan8(hps, joint, n, ki == ko ? 1 : 0, plan, sps, hist, ws + L.off_lookback,
-                         L.zero_bytes - L.off_lookback, s));
+                         L.zero_bytes - L.off_lookback, s, hyb ? &hc : nullptr));
     for (int p = 0; p < L.P; ++p) {
-        TimingScope ts(LABSORT_K_ONESWEEP, s);
+        // (host gate open: only digits 2 and 3 are timed as passes, so the class's time per launch
+        // stays the average of real passes on either path)
+        TimingScope ts(hyb && p < 2 ? LABSORT_K_UNTIMED : LABSORT_K_ONESWEEP, s);
         HIP_TRY(launch_onesweep_p(b, plan, p, n, flip, sps + p, lookback + (size_t)p * L.ntiles * L.R,
                                   counters + (size_t)p * OSP_NCTR, err, s, vi ? &vb : nullptr));
+    }
+    if (hyb) {
+        TimingScope ts(LABSORT_K_SEGSORT, s);
+        HIP_TRY(launch_hybrid_finish(plan, b, n, flip, hc.top14, reinterpret_cast<uint32_t *>(ws + L.off_fin_hdr),
+                                     reinterpret_cast<uint32_t *>(ws + L.off_fin_off),
+                                     reinterpret_cast<uint32_t *>(ws + L.off_fin_lists), s));
     }
     // pass 0's launch copies an input whose every digit is constant (IN -> OUT), so only an
     // in-place sort (its odd pass count ends in TMP) needs the final copy launches
@@ -506,6 +541,21 @@ int read_status(const void *d_ws, bool has_err_word, hipStream_t s) {
 
 int labsort_workspace_status(const void *d_ws, size_t n, int algo, void *stream) {
     return read_status(d_ws, n != 0 && !small_path(n, resolve_algo(algo, n)), as_stream(stream));
+}
+
+int labsort_radix_path(const void *d_ws, size_t n, void *stream) {
+    hipStream_t s = as_stream(stream);
+    uint32_t hybrid = 0;
+    hipError_t e = hipStreamSynchronize(s);
+    // (one tile, the gathered passes: no plan in these workspaces, and no hybrid path)
+    const bool planned = n != 0 && d_ws && !small_path(n, LABSORT_ALGO_RADIX) && !use_gather(n) && n <= RADIX_MAX_N;
+    if (e == hipSuccess && planned) {
+        const size_t at = radix_layout(n, 8, OSP_TILE).off_plan + offsetof(Plan, hybrid);
+        e = hipMemcpyAsync(&hybrid, static_cast<const char *>(d_ws) + at, 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) return -fail_hip(e);
+    return hybrid ? 1 : 0;
 }
 
 int labsort_pairs_workspace_status(const void *d_ws, size_t n, int algo, void *stream) {

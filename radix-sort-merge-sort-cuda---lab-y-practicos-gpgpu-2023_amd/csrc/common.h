@@ -126,7 +126,33 @@ struct Plan {
     uint32_t prev[MAX_PASSES];  // 8-bit radix: previous active pass (NEXT_NONE for the first)
     uint32_t copy_from;  // SEL_SKIP: result already in OUT
     uint32_t active;     // number of non-trivial passes
-    uint32_t pad[2];
+    uint32_t hybrid;     // 8-bit radix, keys only: 1 when k_plan8 chose the hybrid path (below)
+    uint32_t fin_src;    // hybrid: the buffer that holds the keys when the finish starts
+};
+
+// ---- hybrid radix (keys only): scatter passes on digits 2 and 3 only, then
+// every bucket of the top 16 bits (a contiguous range) sorted in LDS by its low 16 bits
+// (segsort.hip's class kernels).  k_plan8 chooses it on the device when digits 0 and 1 are both
+// non-trivial and no value of the top HY_TOP_BITS bits has more than HY_MAX_BUCKET keys,
+// which bounds every bucket by what one workgroup sorts in LDS. ----
+constexpr int HY_TOP_BITS = 14, HY_TOP = 1 << HY_TOP_BITS;
+constexpr uint32_t HY_BUCKETS = 1u << 16;
+constexpr uint32_t HY_MAX_BUCKET = 32768;  // = SEG_TILE_KEYS (segsort.h)
+// Host gate (LABSORT_RADIX_HYBRID unset or 1), by measurement (DESIGN.md §3.9,
+// profiles/hybrid_sizes.txt): uniform keys gain from 0.94 x 2^28 keys (below, the two scatter
+// passes saved cost less than the finish) to 1.19 x 2^28 (above, the 4096-key average bucket
+// outgrows the finish's 5120-key block class and lands in the tile class: 1.4-1.8 x slower).
+constexpr size_t HY_MIN_N = ((size_t)1 << 28) - ((size_t)1 << 24);
+constexpr size_t HY_MAX_N = ((size_t)1 << 28) + 3 * ((size_t)1 << 24);
+// Under that gate the plan also asks that no top-14-bit group (four buckets) has more keys than
+// four buckets of the block class hold, so inputs whose buckets would mostly land in the tile
+// class (2^28 keys below 2^31: 8192-key buckets) keep the classic passes.
+constexpr uint32_t HY_FAST_GROUP = 4u * 5120u;
+// what the hybrid path adds to the upfront histogram and the plan (nullptr: classic only)
+struct HyCounts {
+    uint32_t *hps2;   // digit-2 histogram of each position segment
+    uint32_t *top14;  // histogram of the top HY_TOP_BITS bits
+    uint32_t limit;   // the plan takes the hybrid path up to this largest top14 count (<= HY_MAX_BUCKET)
 };
 
 struct Bufs {
@@ -148,10 +174,12 @@ hipError_t launch_plan(const uint32_t *hist, size_t n, int bits, int in_is_out, 
 hipError_t launch_onesweep(Bufs b, const Plan *plan, int pass, int bits, size_t n, uint32_t flip,
                            const uint32_t *hist, uint32_t *lookback, uint32_t *counter, uint32_t *err,
                            hipStream_t s);
+// hy (or nullptr): the histogram also counts the hybrid path's fields and the plan may choose it
 hipError_t launch_hist_seg(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *hps, uint32_t *joint,
-                           hipStream_t s);
+                           hipStream_t s, const HyCounts *hy = nullptr);
 hipError_t launch_plan8(const uint32_t *hps, const uint32_t *joint, size_t n, int in_is_out, Plan *plan,
-                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, hipStream_t s);
+                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, hipStream_t s,
+                        const HyCounts *hy = nullptr);
 hipError_t launch_onesweep_p(Bufs b, const Plan *plan, int pass, size_t n, uint32_t flip, const SegPlan *sp,
                              uint32_t *lookback, uint32_t *counter, uint32_t *err, hipStream_t s,
                              const Bufs *vb = nullptr);

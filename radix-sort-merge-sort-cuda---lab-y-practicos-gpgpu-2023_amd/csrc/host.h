@@ -30,6 +30,7 @@ inline bool pairs_alias_ok(const void *ki, const void *vi, const void *ko, const
 
 // Timing scope: with labsort_timing_enable(1), an event pair on s around the launches made
 // while the scope lives, counted under kernel class cls (api.hip keeps the state).
+constexpr int LABSORT_K_UNTIMED = -1;  // a scope that records nothing
 struct TimingScope {
     int cls;
     hipStream_t s;

@@ -190,22 +190,38 @@ __global__ __launch_bounds__(256) void k_plan(const uint32_t *__restrict__ hist,
 //     Digit histograms of passes 1-3 are its marginals.
 //     (A pass whose previous active digit is not p - 1 runs as one chain.)
 // ---------------------------------------------------------------------------------
+//
+// HY (keys-only sorts the host gate admits to the hybrid path) also counts, in
+// the same read: the digit-2 histogram of each position segment (hy.hps2: the hybrid's first
+// pass is on digit 2) and a histogram of the top 14 bits (hy.top14: its largest count bounds
+// every bucket of the top 16 bits).  Neither costs a counter of its own kind: the 14-bit
+// histogram replaces the third joint field, which is its marginal (groups of four, summed at
+// the flush), and a workgroup reads one position segment only, so its digit-2 counts are the
+// marginal of its second joint field (bits 12-23) over the low nibble.  One more LDS atomic
+// per key than the plain form, 128 KB of LDS.
+template <bool HY>
 __global__ __launch_bounds__(HIST_BLOCK) void k_hist_seg(const uint32_t *__restrict__ keys, size_t n, uint32_t flip,
                                                          uint32_t *__restrict__ hps, uint32_t *__restrict__ joint,
-                                                         uint32_t bps) {
+                                                         uint32_t bps, HyCounts hy) {
     constexpr int SL = 32;  // replicated digit-0 counters: the 32 lanes of a ds_add group hit 32 banks
     constexpr int JF = 4096;  // 12-bit joint fields per pass
+    constexpr int NJ = HY ? 2 : 3;  // joint fields counted as such
     __shared__ uint32_t h[256 * SL];
-    __shared__ uint32_t hj[3 * JF];
+    __shared__ uint32_t hj[NJ * JF];
+    __shared__ uint32_t ht[HY ? HY_TOP : 1];
     for (int i = threadIdx.x; i < 256 * SL; i += HIST_BLOCK) h[i] = 0u;
-    for (int i = threadIdx.x; i < 3 * JF; i += HIST_BLOCK) hj[i] = 0u;
+    for (int i = threadIdx.x; i < NJ * JF; i += HIST_BLOCK) hj[i] = 0u;
+    if constexpr (HY) {
+        for (int i = threadIdx.x; i < HY_TOP; i += HIST_BLOCK) ht[i] = 0u;
+    }
     __syncthreads();
     const uint32_t slot = threadIdx.x & (SL - 1);
     auto count = [&](uint32_t k) {
         k ^= flip;
         atomicAdd(&h[(k & 255u) * SL + slot], 1u);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) atomicAdd(&hj[p * JF + ((k >> (8 * p + 4)) & (JF - 1))], 1u);
+        for (int p = 0; p < NJ; ++p) atomicAdd(&hj[p * JF + ((k >> (8 * p + 4)) & (JF - 1))], 1u);
+        if constexpr (HY) atomicAdd(&ht[k >> (32 - HY_TOP_BITS)], 1u);
     };
     // 16 keys of one lane (4 uint4 of 4 consecutive keys): digit 0 as above
     // (replicated slots: contention-free for any data).  Joint fields: with one add per
@@ -227,44 +243,54 @@ __global__ __launch_bounds__(HIST_BLOCK) void k_hist_seg(const uint32_t *__restr
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j) atomicAdd(&h[(k[j] & 255u) * SL + slot], 1u);
-        if (__ballot(fld(k[0], 2) == fld(k[3], 2)) == 0ull) {  // no repeats here
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) atomicAdd(&hj[p * JF + fld(k[j], p)], 1u);
-            return;
-        }
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const uint32_t f0 = fld(k[0], p);
-            bool same = fld(k[15], p) == f0;
+        // one field of the 16 keys into its counters (ctr(f): the counter of field value f), a
+        // repeated value added once per wave, per lane or per uint4
+        auto add_field = [&](auto &&fv, auto &&ctr) {
+            const uint32_t f0 = fv(k[0]);
+            bool same = fv(k[15]) == f0;
             if (same) {  // first and last agree: check the rest
 #pragma unroll
-                for (int j = 1; j < 15; ++j) same &= fld(k[j], p) == f0;
+                for (int j = 1; j < 15; ++j) same &= fv(k[j]) == f0;
             }
             // the whole wave on one field (sorted or clustered input): one add for it
             const uint32_t w0 = __builtin_amdgcn_readfirstlane(f0);
             const uint64_t act = __ballot(true);
             if (__ballot(same && f0 == w0) == act) {
-                if (mbcnt64(act) == 0u) atomicAdd(&hj[p * JF + w0], 16u * (uint32_t)__popcll(act));
-                continue;
+                if (mbcnt64(act) == 0u) atomicAdd(ctr(w0), 16u * (uint32_t)__popcll(act));
+                return;
             }
             if (same) {
-                atomicAdd(&hj[p * JF + f0], 16u);
-                continue;
+                atomicAdd(ctr(f0), 16u);
+                return;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const uint32_t fa = fld(k[4 * u], p);
-                const bool s4 = fld(k[4 * u + 3], p) == fa && fld(k[4 * u + 1], p) == fa && fld(k[4 * u + 2], p) == fa;
+                const uint32_t fa = fv(k[4 * u]);
+                const bool s4 = fv(k[4 * u + 3]) == fa && fv(k[4 * u + 1]) == fa && fv(k[4 * u + 2]) == fa;
                 if (s4) {
-                    atomicAdd(&hj[p * JF + fa], 4u);
+                    atomicAdd(ctr(fa), 4u);
                 } else {
 #pragma unroll
-                    for (int j = 4 * u; j < 4 * u + 4; ++j) atomicAdd(&hj[p * JF + fld(k[j], p)], 1u);
+                    for (int j = 4 * u; j < 4 * u + 4; ++j) atomicAdd(ctr(fv(k[j])), 1u);
                 }
             }
+        };
+        auto top = [&](uint32_t x) { return HY ? x >> (32 - HY_TOP_BITS) : fld(x, 2); };  // the topmost field counted
+        if (__ballot(top(k[0]) == top(k[3])) == 0ull) {  // no repeats here
+#pragma unroll
+            for (int p = 0; p < NJ; ++p)
+#pragma unroll
+                for (int j = 0; j < 16; ++j) atomicAdd(&hj[p * JF + fld(k[j], p)], 1u);
+            if constexpr (HY) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) atomicAdd(&ht[top(k[j])], 1u);
+            }
+            return;
         }
+#pragma unroll
+        for (int p = 0; p < NJ; ++p)
+            add_field([&](uint32_t x) { return fld(x, p); }, [&](uint32_t f) { return &hj[p * JF + f]; });
+        if constexpr (HY) add_field(top, [&](uint32_t f) { return &ht[f]; });
     };
     const uint32_t seg = blockIdx.x / bps, part = blockIdx.x % bps;
     const size_t sb = seg_start(seg, n), se = seg_start(seg + 1, n);
@@ -309,17 +335,39 @@ __global__ __launch_bounds__(HIST_BLOCK) void k_hist_seg(const uint32_t *__restr
 #pragma unroll 8
         for (int q = 0; q < SL; ++q) c += h[i * SL + ((q + i) & (SL - 1))];
         if (c) atomicAdd(&hps[seg * 256 + i], c);
+        if constexpr (HY) {
+            uint32_t c2 = 0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) c2 += hj[JF + i * 16 + ((q + i) & 15)];  // field (key >> 12) & 4095
+            if (c2) atomicAdd(&hy.hps2[seg * 256 + i], c2);
+        }
     }
     // field f = (digit p+1) << 4 | (top nibble of digit p) -> joint[p+1][nibble][digit].
     // Each workgroup starts its flush at a different place, so the ~12 K
     // atomics of workgroups that finish together do not queue on the same lines.
-    const uint32_t rot = (blockIdx.x * (uint32_t)HIST_BLOCK) % (3u * JF);
-    for (int i0 = threadIdx.x; i0 < 3 * JF; i0 += HIST_BLOCK) {
+    const uint32_t rot = (blockIdx.x * (uint32_t)HIST_BLOCK) % ((uint32_t)NJ * JF);
+    for (int i0 = threadIdx.x; i0 < NJ * JF; i0 += HIST_BLOCK) {
         int i = i0 + (int)rot;
-        i = i >= 3 * JF ? i - 3 * JF : i;
+        i = i >= NJ * JF ? i - NJ * JF : i;
         const uint32_t c = hj[i];
         const uint32_t p = (uint32_t)i / JF, f = (uint32_t)i % JF;
         if (c) atomicAdd(&joint[((p + 1) * NSEG + (f & 15u)) * 256 + (f >> 4)], c);
+    }
+    if constexpr (HY) {
+        // the top-14-bit counts, four at a time: their sum is the third joint field's count
+        // (field f = key >> 20); rotated per workgroup like the joint flush
+        const uint32_t rot4 = (blockIdx.x * 272u) % (uint32_t)JF;
+        for (uint32_t g0 = threadIdx.x; g0 < (uint32_t)JF; g0 += HIST_BLOCK) {
+            const uint32_t f = (g0 + rot4) % (uint32_t)JF;
+            uint32_t sum = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < 4u; ++q) {
+                const uint32_t c = ht[4u * f + q];
+                sum += c;
+                if (c) atomicAdd(&hy.top14[4u * f + q], c);
+            }
+            if (sum) atomicAdd(&joint[(3u * NSEG + (f & 15u)) * 256 + (f >> 4)], sum);
+        }
     }
 }
 
@@ -394,7 +442,7 @@ __device__ void build_segplan_later(SegPlan *__restrict__ out, int q, uint32_t p
 __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps, const uint32_t *__restrict__ joint,
                                                uint32_t n, int in_is_out, int seg_later, Plan *__restrict__ plan,
                                                SegPlan *__restrict__ sps, uint32_t *__restrict__ hist_out,
-                                               uint4 *__restrict__ zp, size_t zn4) {
+                                               uint4 *__restrict__ zp, size_t zn4, HyCounts hy) {
     constexpr uint32_t PW = 4;  // plan workgroups, one per pass
     if (blockIdx.x >= PW) {
         const size_t stride = (size_t)(gridDim.x - PW) * blockDim.x;
@@ -409,9 +457,17 @@ __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps,
     __shared__ uint32_t start[NSEG + 1];
     __shared__ uint32_t prevs[4];
     __shared__ int first;
+    __shared__ uint32_t max14;
     const uint32_t t = threadIdx.x;
     if (t < 4) triv[t] = 0;
+    if (t == 0) max14 = 0u;
     __syncthreads();
+    // hybrid path (hy.top14 != nullptr: the host gate admits it): the largest top-14-bit count
+    if (hy.top14) {
+        uint32_t m = 0;
+        for (uint32_t i = t; i < (uint32_t)HY_TOP; i += 256u) m = max(m, hy.top14[i]);
+        atomicMax(&max14, m);
+    }
     uint32_t v[4] = {0, 0, 0, 0};
     for (int s = 0; s < NSEG; ++s) {
         v[0] += hps[s * 256 + t];
@@ -425,6 +481,14 @@ __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps,
         if (v[p] == n) triv[p] = 1;
     }
     if (t <= (uint32_t)NSEG) start[t] = seg_later < 0 ? (t ? n : 0u) : seg_start(t, n);
+    __syncthreads();
+    // The hybrid path is taken when digits 0 and 1 both vary and every bucket of the top 16 bits
+    // fits one workgroup's LDS sort: a bucket is part of a top-14-bit group, so the largest
+    // group bounds it (conservative, never wrong).  Digits 0 and 1 then count as trivial here:
+    // the finish sorts them, bucket by bucket, after the pass on digit 3.
+    const bool hybrid = hy.top14 && !triv[0] && !triv[1] && max14 <= min(hy.limit, HY_MAX_BUCKET);
+    __syncthreads();
+    if (hybrid && t < 2) triv[t] = 1;
     __syncthreads();
     if (t == 0 && me != 0) {  // the pass structure only
         int k = 0, last = -1;
@@ -457,7 +521,23 @@ __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps,
         }
         plan->active = (uint32_t)k;
         first = k ? act[0] : -1;
-        plan_buffers(plan, act, k, in_is_out);
+        plan->hybrid = hybrid ? 1u : 0u;
+        plan->fin_src = SEL_OUT;
+        if (!hybrid) {
+            plan_buffers(plan, act, k, in_is_out);
+        } else {
+            // the last scatter pass lands in OUT, where the finish runs in place (digit 2
+            // IN -> TMP, digit 3 TMP -> OUT); a single active pass of an in-place call lands in
+            // TMP, and with none the keys are still in IN: the finish reads them from there
+            // and writes OUT.  No final copy on this path.
+            uint32_t src = SEL_IN;
+            for (int i = 0; i < k; ++i) {
+                plan->src[act[i]] = src;
+                plan->dst[act[i]] = src = (i == k - 1 && !(k == 1 && in_is_out)) ? SEL_OUT : SEL_TMP;
+            }
+            plan->fin_src = src;
+            plan->copy_from = SEL_SKIP;
+        }
     }
     __syncthreads();
     if (first < 0 || me < first) return;
@@ -467,13 +547,15 @@ __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps,
             build_segplan_later(sps + me, me, prevs[me], n, seg_later, hist, joint, sh, start);
         return;
     }
-    if (seg_later < 0 || first != 0) {
+    // (hybrid: digit 2 is the first pass, with the position-segment histograms counted for it)
+    const uint32_t *hp = first == 0 ? hps : (hybrid && first == 2) ? hy.hps2 : nullptr;
+    if (seg_later < 0 || !hp) {
         if (t <= (uint32_t)NSEG) start[t] = t ? n : 0u;
         for (int s = 0; s < NSEG; ++s) sh[s * 256 + t] = s ? 0u : hist[first * 256 + t];
         __syncthreads();
         build_segplan(sps + first, sh, start, 2u, sh);
     } else {
-        for (int s = 0; s < NSEG; ++s) sh[s * 256 + t] = hps[s * 256 + t];
+        for (int s = 0; s < NSEG; ++s) sh[s * 256 + t] = hp[s * 256 + t];
         __syncthreads();
         build_segplan(sps + first, sh, start, 0u, sh);
     }
@@ -1670,19 +1752,21 @@ hipError_t launch_onesweep_p(Bufs b, const Plan *plan, int pass, size_t n, uint3
 
 
 hipError_t launch_hist_seg(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *hps, uint32_t *joint,
-                           hipStream_t s) {
+                           hipStream_t s, const HyCounts *hy) {
     if (n == 0) return hipSuccess;
     // workgroups per position segment: HS_BPS at large n; at small n at least
     // HS_MIN_KEYS keys each, since every workgroup flushes ~13 K counters with global
     // atomics (512 workgroups at 2^20: 97 us, contended on the same 48 KB)
     size_t bps = n / ((size_t)NSEG * HS_MIN_KEYS);
     bps = bps < 1 ? 1 : bps > (size_t)HS_BPS ? (size_t)HS_BPS : bps;
-    k_hist_seg<<<NSEG * (unsigned)bps, HIST_BLOCK, 0, s>>>(keys, n, flip, hps, joint, (uint32_t)bps);
+    if (hy) k_hist_seg<true><<<NSEG * (unsigned)bps, HIST_BLOCK, 0, s>>>(keys, n, flip, hps, joint, (uint32_t)bps, *hy);
+    else k_hist_seg<false><<<NSEG * (unsigned)bps, HIST_BLOCK, 0, s>>>(keys, n, flip, hps, joint, (uint32_t)bps, HyCounts{});
     return hipGetLastError();
 }
 
 hipError_t launch_plan8(const uint32_t *hps, const uint32_t *joint, size_t n, int in_is_out, Plan *plan,
-                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, hipStream_t s) {
+                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, hipStream_t s,
+                        const HyCounts *hy) {
     // the look-back clear rides in the plan launch (workgroups 1..): one launch fewer (r27)
     const bool fold = zero_bytes % 16 == 0;
     if (!fold && zero_bytes) {
@@ -1692,7 +1776,7 @@ hipError_t launch_plan8(const uint32_t *hps, const uint32_t *joint, size_t n, in
     const size_t zn4 = fold ? zero_bytes / 16 : 0;
     const unsigned g = 4u + (zn4 ? blocks_for(zn4, 256 * 4, 2048) : 0u);
     k_plan8<<<g, 256, 0, s>>>(hps, joint, (uint32_t)n, in_is_out, 1, plan, segplans, hist,
-                              static_cast<uint4 *>(zero_p), zn4);
+                              static_cast<uint4 *>(zero_p), zn4, hy ? *hy : HyCounts{});
     return hipGetLastError();
 }
 

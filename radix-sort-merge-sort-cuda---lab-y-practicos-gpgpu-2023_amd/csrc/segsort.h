@@ -28,8 +28,22 @@ constexpr int SEG_WAVE_KEYS = WAVE * SEG_WAVE_KPT, SEG_WAVE2_KEYS = WAVE * SEG_W
 static_assert(SEG_WAVE_KEYS < SEG_WAVE2_KEYS && SEG_WAVE2_KEYS < SEG_WAVE3_KEYS, "class edges ascend");
 constexpr int SEG_WAVE_WPB = 4;  // segments (waves) per workgroup
 // block class: one 256-thread workgroup per segment, 16 keys per thread
-constexpr int SEG_BLOCK = 256;
-constexpr int SEG_BLOCK_KPT = 16;
+#ifndef LABSORT_SEG_BLOCK
+#define LABSORT_SEG_BLOCK 256  // A/B build knobs of the hybrid finish probe
+#endif
+#ifndef LABSORT_SEG_BLOCK_KPT
+#define LABSORT_SEG_BLOCK_KPT 16
+#endif
+#ifndef LABSORT_SEG_BLOCK_WGS
+#define LABSORT_SEG_BLOCK_WGS 6  // keys-only grid: workgroups per CU
+#endif
+#ifndef LABSORT_SEG_BLOCK_WPE
+#define LABSORT_SEG_BLOCK_WPE 4  // block class: waves per SIMD the register budget allows
+#endif
+constexpr int SEG_BLOCK_WPE = LABSORT_SEG_BLOCK_WPE;
+constexpr int SEG_BLOCK = LABSORT_SEG_BLOCK;
+constexpr int SEG_BLOCK_KPT = LABSORT_SEG_BLOCK_KPT;
+constexpr int SEG_BLOCK_WGS = LABSORT_SEG_BLOCK_WGS;
 constexpr int SEG_BLOCK_KEYS = SEG_BLOCK * SEG_BLOCK_KPT;  // 4096
 // tile class: k_tile_sort's shapes, 1024 threads x 32 keys or x 16 pairs
 constexpr int SEG_TILE_KEYS = TS_BLOCK * TS_KPT;        // 32768
@@ -57,6 +71,29 @@ hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max
 hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in, uint32_t *out, const uint32_t *vin,
                                   uint32_t *vout, const uint32_t *off, const uint32_t *hdr, const uint32_t *lists,
                                   size_t stride, uint32_t flip, hipStream_t s);
+// ---- the hybrid radix sort's finish (api.hip's sort_radix8) ----
+// After the scatter passes on digits 2 and 3 every bucket of the top 16 bits is a contiguous
+// range; the finish finds the 65537 bucket offsets and sorts each bucket with the class kernels
+// above, through class lists and a header of its own in the radix workspace.  Its kernels read
+// the plan's choice first and return at once when the classic path was chosen.
+struct HySel {
+    const Plan *plan;        // nullptr: the segmented sort's own launches
+    const uint32_t *buf[3];  // IN, OUT, TMP: the input is buf[plan->fin_src]
+};
+// finish classes: the three wave classes, a 256 x 20 block class that holds the 4096 +- 300-key
+// buckets of 2^28 uniform keys (a 4096-key edge would send half of them to the tile class:
+// 2.07 ms against 0.69, profiles/hybrid_finish_shapes.txt), the tile class
+constexpr int HY_BLOCK = 256, HY_BLOCK_KPT = 20, HY_BLOCK_WPE = 5, HY_BLOCK_KEYS = HY_BLOCK * HY_BLOCK_KPT;  // 5120
+static_assert((uint32_t)SEG_TILE_KEYS == HY_MAX_BUCKET, "the plan's bound is the tile class's capacity");
+static_assert(SEG_WAVE3_KEYS < HY_BLOCK_KEYS && HY_BLOCK_KEYS < SEG_TILE_KEYS, "class edges ascend");
+static_assert(HY_FAST_GROUP == 4u * HY_BLOCK_KEYS, "the default gate's group bound: four block-class buckets");
+// hdr: SEG_HDR_BYTES cleared since the last finish; off: HY_BUCKETS + 1 words; lists: SEG_CLASSES
+// lists of HY_BUCKETS words.  Bucket offsets, class lists, the five class kernels: seven
+// launches, host arguments only.  top14: the histogram of the keys' top 14 bits, which brackets
+// each bucket's boundary search.
+hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t flip, const uint32_t *top14, uint32_t *hdr,
+                                uint32_t *off, uint32_t *lists, hipStream_t s);
+
 // workspace of the general path's inner pair sorts of n pairs (top-k's single-row sort uses the same)
 size_t seg_inner_bytes(size_t n);
 

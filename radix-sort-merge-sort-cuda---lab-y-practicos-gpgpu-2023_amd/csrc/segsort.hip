@@ -30,8 +30,9 @@ constexpr int BIN_BLOCK = 1024, BIN_SPT = 4;  // 4096 segments per workgroup
 __global__ __launch_bounds__(BIN_BLOCK) void k_seg_bin(const uint32_t *__restrict__ off, uint32_t nseg, uint32_t n,
                                                         uint32_t max_len, SegEdges e, uint32_t copy1,
                                                         uint32_t *__restrict__ hdr, uint32_t *__restrict__ lists,
-                                                        size_t stride) {
+                                                        size_t stride, const Plan *__restrict__ hyplan) {
     __shared__ uint32_t cnt[SEG_CLASSES], base[SEG_CLASSES];
+    if (hyplan && hyplan->hybrid == 0u) return;  // the radix sort's finish, classic path chosen: no offsets
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (tid < (uint32_t)SEG_CLASSES) cnt[tid] = 0u;
     __syncthreads();
@@ -101,9 +102,13 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_seg_wave(const uint32_t
                                                                   uint32_t *vout, const uint32_t *__restrict__ off,
                                                                   const uint32_t *__restrict__ hdr,
                                                                   const uint32_t *__restrict__ list, int cls,
-                                                                  uint32_t flip) {
+                                                                  uint32_t flip, HySel hy) {
     constexpr uint32_t CAP = WAVE * KPT;
     __shared__ SwSmem<KPT, KV> sm_all[SEG_WAVE_WPB];
+    if (hy.plan) {  // the radix sort's finish: the plan's choice first, and the buffer it names
+        if (hy.plan->hybrid == 0u) return;
+        in = hy.buf[hy.plan->fin_src];
+    }
     if (ld_agent(hdr) != 0u) return;  // rejected offsets: touch nothing
     const uint32_t cnt = hdr[SEG_HDR_CNT + cls];
     const uint32_t lane = threadIdx.x & 63u, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -221,15 +226,20 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_seg_wave(const uint32_t
 // few 64-key groups; groups that start past the end are neither ranked nor read back
 // (LeadingGroups).
 // ---------------------------------------------------------------------------------
-template <int BLOCK, int KPT, bool KV>
-__global__ __launch_bounds__(BLOCK, 4) void k_seg_block(const uint32_t *in, uint32_t *out, const uint32_t *vin,
-                                                         uint32_t *vout, const uint32_t *__restrict__ off,
-                                                         const uint32_t *__restrict__ hdr,
-                                                         const uint32_t *__restrict__ list, int cls, uint32_t flip) {
+template <int BLOCK, int KPT, bool KV, int WPE = 4>
+__global__ __launch_bounds__(BLOCK, WPE) void k_seg_block(const uint32_t *in, uint32_t *out, const uint32_t *vin,
+                                                           uint32_t *vout, const uint32_t *__restrict__ off,
+                                                           const uint32_t *__restrict__ hdr,
+                                                           const uint32_t *__restrict__ list, int cls, uint32_t flip,
+                                                           HySel hy) {
     using S = TsSmem<BLOCK, KPT, KV>;
     constexpr int W = S::W;
     constexpr uint32_t TILE = S::TILE;
     __shared__ S sm;
+    if (hy.plan) {  // the radix sort's finish: the plan's choice first, and the buffer it names
+        if (hy.plan->hybrid == 0u) return;
+        in = hy.buf[hy.plan->fin_src];
+    }
     if (ld_agent(hdr) != 0u) return;  // rejected offsets: touch nothing
     const uint32_t cnt = hdr[SEG_HDR_CNT + cls];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -336,7 +346,7 @@ __global__ __launch_bounds__(256) void k_seg_ids(const uint32_t *__restrict__ of
         if (p >= n) p = n - 1u;
         // first q in [1, nseg] with off[q] > p (off[nseg] = n > p): p lies in segment q - 1
         uint32_t lo = 1u, hi = nseg;
-        while (lo < hi) {
+        while (lo < hi) {  // first position in [lo, hi) with (key ^ flip) >> 16 >= q
             const uint32_t mid = lo + (hi - lo) / 2u;
             if (off[mid] > p) hi = mid;
             else lo = mid + 1u;
@@ -385,25 +395,25 @@ unsigned stream_blocks(size_t n) {
 // The sort kernel of class c (0-2 wave, 3 block, 4 tile) over its list; vin/vout nullptr: keys only.
 hipError_t launch_seg_sort(int c, const uint32_t *in, uint32_t *out, const uint32_t *vin, uint32_t *vout,
                            const uint32_t *off, const uint32_t *hdr, const uint32_t *list, uint32_t flip,
-                           hipStream_t s) {
+                           hipStream_t s, const HySel &hy = HySel{}) {
     const bool kv = vin != nullptr;
     const unsigned cus = (unsigned)cu_count();
     // fixed grids, multiples of the CU count: what stays resident per CU by LDS
     if (c == 0) {
-        if (kv) k_seg_wave<SEG_WAVE_KPT, true><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip);
-        else k_seg_wave<SEG_WAVE_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip);
+        if (kv) k_seg_wave<SEG_WAVE_KPT, true><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip, hy);
+        else k_seg_wave<SEG_WAVE_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip, hy);
     } else if (c == 1) {
-        if (kv) k_seg_wave<SEG_WAVE2_KPT, true><<<cus * 6u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip);
-        else k_seg_wave<SEG_WAVE2_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip);
+        if (kv) k_seg_wave<SEG_WAVE2_KPT, true><<<cus * 6u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip, hy);
+        else k_seg_wave<SEG_WAVE2_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip, hy);
     } else if (c == 2) {  // 110-127 VGPRs: four waves per SIMD
-        if (kv) k_seg_wave<SEG_WAVE3_KPT, true><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip);
-        else k_seg_wave<SEG_WAVE3_KPT, false><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip);
+        if (kv) k_seg_wave<SEG_WAVE3_KPT, true><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip, hy);
+        else k_seg_wave<SEG_WAVE3_KPT, false><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip, hy);
     } else if (c == 3) {
-        if (kv) k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, true><<<cus * 4u, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip);
-        else k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, false><<<cus * 6u, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip);
+        if (kv) k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, true, SEG_BLOCK_WPE><<<cus * 4u, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip, hy);
+        else k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, false, SEG_BLOCK_WPE><<<cus * (unsigned)SEG_BLOCK_WGS, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip, hy);
     } else if (c == 4) {
-        if (kv) k_seg_block<TS_BLOCK, TS_KPT_KV, true><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip);
-        else k_seg_block<TS_BLOCK, TS_KPT, false><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip);
+        if (kv) k_seg_block<TS_BLOCK, TS_KPT_KV, true><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip, hy);
+        else k_seg_block<TS_BLOCK, TS_KPT, false><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip, hy);
     } else {
         return hipErrorInvalidValue;
     }
@@ -439,7 +449,7 @@ hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max
     (void)pairs;  // the class edges below the tile are the same for keys and pairs
     const SegEdges e{{(uint32_t)SEG_WAVE_KEYS, (uint32_t)SEG_WAVE2_KEYS, (uint32_t)SEG_WAVE3_KEYS, (uint32_t)SEG_BLOCK_KEYS}};
     k_seg_bin<<<g, BIN_BLOCK, 0, s>>>(off, (uint32_t)nseg, (uint32_t)n, (uint32_t)max_len, e, copy1 ? 1u : 0u, hdr, lists,
-                                      stride);
+                                      stride, nullptr);
     return hipGetLastError();
 }
 
@@ -452,6 +462,95 @@ hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in
     while (ncls < SEG_CLASSES && max_len > edges[ncls - 1]) ++ncls;
     for (int c = 0; c < ncls; ++c) {
         const hipError_t e = launch_seg_sort(c, in, out, vin, vout, off, hdr, lists + (size_t)c * stride, flip, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------
+// the hybrid radix sort's finish
+// ---------------------------------------------------------------------------------
+namespace {
+constexpr int FB_BLOCK = 1024;  // buckets per workgroup of k_fin_bounds
+
+// off[q] = first position whose key's top 16 bits are >= q, for the HY_BUCKETS buckets q, and
+// off[HY_BUCKETS] = n.  The keys are ordered by their top 16 bits.  Bucket q lies in the range of
+// its top-14-bit group q >> 2, which the exclusive scan of top14 gives: at most HY_MAX_BUCKET
+// keys when the plan chose the hybrid path, so the search takes 15 steps, not 28.
+__global__ __launch_bounds__(FB_BLOCK) void k_fin_bounds(const Plan *__restrict__ plan, Bufs bufs, uint32_t n, uint32_t flip,
+                                                         const uint32_t *__restrict__ top14, uint32_t *__restrict__ off) {
+    constexpr uint32_t GPB = FB_BLOCK / 4;  // top-14-bit groups per workgroup
+    __shared__ uint32_t wsum[FB_BLOCK / WAVE];
+    __shared__ uint32_t gstart[GPB + 1];
+    if (plan->hybrid == 0u) return;
+    const uint32_t *__restrict__ keys = bufs.p[plan->fin_src];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+    const uint32_t g0 = blockIdx.x * GPB;  // this workgroup's first group
+    // keys in the groups before g0, then the exclusive scan of this workgroup's groups
+    uint32_t before = 0u;
+    for (uint32_t i = tid; i < g0; i += FB_BLOCK) before += top14[i];
+    const uint32_t mine = tid < GPB ? top14[g0 + tid] : 0u;
+    uint32_t x = mine, tot = before;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(x, o);
+        if (lane >= (uint32_t)o) x += t;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+    if (lane == 63u) wsum[wid] = x;
+    __syncthreads();
+    uint32_t pre = 0u;  // counts of the waves before this one (the groups sit in waves 0-3)
+    for (uint32_t w = 0; w < wid && w < GPB / WAVE; ++w) pre += wsum[w];
+    __syncthreads();
+    if (lane == 0u) wsum[wid] = tot;
+    __syncthreads();
+    uint32_t base = 0u;
+    for (uint32_t w = 0; w < (uint32_t)(FB_BLOCK / WAVE); ++w) base += wsum[w];
+    if (tid < GPB) {
+        gstart[tid] = base + pre + x - mine;
+        if (tid == GPB - 1u) gstart[GPB] = base + pre + x;
+    }
+    __syncthreads();
+    const uint32_t q = blockIdx.x * FB_BLOCK + tid;  // bucket
+    uint32_t lo = min(gstart[tid >> 2], n), hi = min(gstart[(tid >> 2) + 1u], n);
+    // (seven probes per round instead of one, 4 + 3 dependent rounds instead of 15, measured slower:
+    // 78 us against 45 at 2^28 -- the probes are scattered single-word loads over 1 GiB, and their
+    // number, not the length of the chain, is what costs)
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (((keys[mid] ^ flip) >> 16) >= q) hi = mid;
+        else lo = mid + 1u;
+    }
+    off[q] = lo;
+    if (q == HY_BUCKETS - 1u) off[HY_BUCKETS] = n;
+}
+}  // namespace
+
+hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t flip, const uint32_t *top14, uint32_t *hdr,
+                                uint32_t *off, uint32_t *lists, hipStream_t s) {
+    static_assert(HY_BUCKETS % FB_BLOCK == 0 && HY_TOP * 4 == (int)HY_BUCKETS, "four buckets per top-14-bit group");
+    const size_t stride = HY_BUCKETS;
+    k_fin_bounds<<<HY_BUCKETS / FB_BLOCK, FB_BLOCK, 0, s>>>(plan, b, (uint32_t)n, flip, top14, off);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // every bucket is written (the finish may read TMP or IN and write OUT): one-key buckets are listed
+    const SegEdges ed{{(uint32_t)SEG_WAVE_KEYS, (uint32_t)SEG_WAVE2_KEYS, (uint32_t)SEG_WAVE3_KEYS, (uint32_t)HY_BLOCK_KEYS}};
+    k_seg_bin<<<HY_BUCKETS / (BIN_BLOCK * BIN_SPT), BIN_BLOCK, 0, s>>>(off, HY_BUCKETS, (uint32_t)n, HY_MAX_BUCKET, ed, 1u, hdr,
+                                                                      lists, stride, plan);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const HySel hy{plan, {b.p[0], b.p[1], b.p[2]}};
+    uint32_t *out = b.p[SEL_OUT];
+    const unsigned cus = (unsigned)cu_count();
+    for (int c = 0; c < SEG_CLASSES; ++c) {
+        const uint32_t *list = lists + (size_t)c * stride;
+        if (c == 3) {  // the finish's own block class
+            k_seg_block<HY_BLOCK, HY_BLOCK_KPT, false, HY_BLOCK_WPE><<<cus * (unsigned)HY_BLOCK_WPE, HY_BLOCK, 0, s>>>(
+                out, out, nullptr, nullptr, off, hdr, list, 3, flip, hy);
+            e = hipGetLastError();
+        } else {
+            e = launch_seg_sort(c, out, out, nullptr, nullptr, off, hdr, list, flip, s, hy);
+        }
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -2,7 +2,8 @@
 """Segmented sort measurements on an MI355X (output kept as
 profiles/segsort_bench.txt).
 
-int32 keys, 2^28 in all, as rows x cols for four row lengths, keys only and pairs:
+int32 keys (--key i32; uniform) or float32 keys (--key f32; standard normal), 2^28 in all, as
+rows x cols for four row lengths, keys only and pairs:
   lds       labsort_sort_segments[_pairs]_device with max_segment_keys = cols (LDS path)
   general   the same call with max_segment_keys = 0 (two pair sorts of the whole array)
   copy      labsort_copy of the same keys: the 8 B/key floor
@@ -63,13 +64,17 @@ def raw_call(lib, pairs):
     return f
 
 
-def shapes_main(logn, reps, out):
+def shapes_main(logn, reps, out, key="i32"):
     n = 1 << logn
-    keys = torch.empty(n, dtype=torch.int32, device="cuda")
-    ls.fill(keys, n, seed=0x5E65EED, dist="u32")
+    if key == "f32":
+        keys = torch.empty(n, dtype=torch.float32, device="cuda")
+        keys.normal_(generator=torch.Generator(device="cuda").manual_seed(0x5E65EED))
+    else:
+        keys = torch.empty(n, dtype=torch.int32, device="cuda")
+        ls.fill(keys, n, seed=0x5E65EED, dist="u32")
     vals = torch.arange(n, dtype=torch.int32, device="cuda")
     ko, vo = torch.empty_like(keys), torch.empty_like(vals)
-    print(f"# segmented sort, int32 keys, n = 2^{logn}, {reps} alternating repetitions, ms: median [min, max]", file=out)
+    print(f"# segmented sort, {'float32' if key == 'f32' else 'int32'} keys, n = 2^{logn}, {reps} alternating repetitions, ms: median [min, max]", file=out)
     print(f"# device: {torch.cuda.get_device_name(0)}; {ls.version()}", file=out)
     for cols in (16, 256, 4096, 32768):
         rows = n // cols
@@ -81,17 +86,17 @@ def shapes_main(logn, reps, out):
             if cols <= tile:
                 ws_l = torch.zeros(ls.segments_workspace_bytes(n, rows, cols, pairs), dtype=torch.uint8, device="cuda")
                 if pairs:
-                    v["lds"] = lambda: ls.sort_segments_pairs_device(keys, vals, ko, vo, n, offs, rows, cols, key="i32", workspace=ws_l)
+                    v["lds"] = lambda: ls.sort_segments_pairs_device(keys, vals, ko, vo, n, offs, rows, cols, key=key, workspace=ws_l)
                 else:
-                    v["lds"] = lambda: ls.sort_segments_device(keys, ko, n, offs, rows, cols, key="i32", workspace=ws_l)
+                    v["lds"] = lambda: ls.sort_segments_device(keys, ko, n, offs, rows, cols, key=key, workspace=ws_l)
             if pairs:
-                v["general"] = lambda: ls.sort_segments_pairs_device(keys, vals, ko, vo, n, offs, rows, 0, key="i32", workspace=ws_g)
+                v["general"] = lambda: ls.sort_segments_pairs_device(keys, vals, ko, vo, n, offs, rows, 0, key=key, workspace=ws_g)
             else:
-                v["general"] = lambda: ls.sort_segments_device(keys, ko, n, offs, rows, 0, key="i32", workspace=ws_g)
+                v["general"] = lambda: ls.sort_segments_device(keys, ko, n, offs, rows, 0, key=key, workspace=ws_g)
             v["copy"] = lambda: ls.copy(keys, ko, n)
             if not pairs:
                 v["torch"] = lambda: torch.sort(keys.view(rows, cols), dim=1)
-                if cols == ls.tile_keys():
+                if cols == ls.tile_keys() and key == "i32":
                     v["tile"] = lambda: ls.tile_sort(keys, ko, n, key="i32")
             else:
                 v["torch"] = lambda: torch.sort(keys.view(rows, cols), dim=1, stable=True)
@@ -152,6 +157,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--logn", type=int, default=28)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--key", choices=["i32", "f32"], default="i32", help="f32: standard-normal float32 keys")
     ap.add_argument("--edges", default="", help="comma-separated alternative builds of liblabsort.so")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -161,4 +167,4 @@ if __name__ == "__main__":
     if a.edges:
         edges_main(a.logn, a.reps, [p for p in a.edges.split(",") if p], out)
     else:
-        shapes_main(a.logn, a.reps, out)
+        shapes_main(a.logn, a.reps, out, a.key)

@@ -2,8 +2,9 @@
 """Top-k selection measurements on an MI355X (output kept as
 profiles/topk_bench.txt).
 
-int32 keys, 2^28 in all, as rows x cols, smallest k with positions, on uniform keys and on
-keys % 1000:
+int32 keys (--key i32), 2^28 in all, as rows x cols, smallest k with positions, on uniform keys and
+on keys % 1000; or float32 keys (--key f32), standard normal, on which the torch comparator runs
+as it would for a caller with float data:
   topk      labsort_topk_device
   fullsort  what a caller could do before it: one row, labsort_sort_pairs_device of (key, iota);
             several rows, labsort_sort_segments_pairs_device with max_segment_keys = cols
@@ -75,30 +76,33 @@ def check(keys, rows, cols, k, ko, io):
     del exp
 
 
-def shapes_main(logn, reps, out, with_torch):
+def shapes_main(logn, reps, out, with_torch, key="i32"):
     n = 1 << logn
-    keys = torch.empty(n, dtype=torch.int32, device="cuda")
+    keys = torch.empty(n, dtype=torch.float32 if key == "f32" else torch.int32, device="cuda")
     iota = torch.arange(n, dtype=torch.int32, device="cuda")
-    so, sv = torch.empty_like(keys), torch.empty_like(keys)
-    print(f"# top-k, int32 keys, smallest k with positions, n = 2^{logn}, {reps} alternating repetitions, "
+    so, sv = torch.empty_like(keys), torch.empty_like(iota)
+    print(f"# top-k, {'float32' if key == 'f32' else 'int32'} keys, smallest k with positions, n = 2^{logn}, {reps} alternating repetitions, "
           "ms: median [min, max]", file=out)
     print(f"# device: {torch.cuda.get_device_name(0)}; {ls.version()}", file=out)
     shapes = [(1, n, 1), (1, n, 1024), (1, n, min(1 << 20, n)), (n >> 16, 1 << 16, 64), (n >> 12, 4096, 8)]
-    for dist in ("u32", "mod1000"):
-        ls.fill(keys, n, seed=0x70C0EED, dist=dist)
+    for dist in (("normal",) if key == "f32" else ("u32", "mod1000")):
+        if key == "f32":
+            keys.normal_(generator=torch.Generator(device="cuda").manual_seed(0x70C0EED))
+        else:
+            ls.fill(keys, n, seed=0x70C0EED, dist=dist)
         torch.cuda.synchronize()
         for rows, cols, k in shapes:
-            ko = torch.empty(rows * k, dtype=torch.int32, device="cuda")
+            ko = torch.empty(rows * k, dtype=keys.dtype, device="cuda")
             io = torch.empty(rows * k, dtype=torch.int32, device="cuda")
             ws = torch.full((ls.topk_workspace_bytes(rows, cols, k),), 0xFF, dtype=torch.uint8, device="cuda")
-            v = {"topk": lambda: ls.topk_device(keys, rows, cols, k, ko, io, key="i32", workspace=ws)}
+            v = {"topk": lambda: ls.topk_device(keys, rows, cols, k, ko, io, key=key, workspace=ws)}
             if rows == 1:
                 ws_f = torch.empty(ls.pairs_workspace_bytes(n, "auto"), dtype=torch.uint8, device="cuda")
-                v["fullsort"] = lambda: ls.sort_pairs_device(keys, iota, so, sv, n, key="i32", algo="auto", workspace=ws_f)
+                v["fullsort"] = lambda: ls.sort_pairs_device(keys, iota, so, sv, n, key=key, algo="auto", workspace=ws_f)
             else:
                 offs = ls.row_offsets(rows, cols)
                 ws_f = torch.empty(ls.segments_workspace_bytes(n, rows, cols, True), dtype=torch.uint8, device="cuda")
-                v["fullsort"] = lambda: ls.sort_segments_pairs_device(keys, iota, so, sv, n, offs, rows, cols, key="i32",
+                v["fullsort"] = lambda: ls.sort_segments_pairs_device(keys, iota, so, sv, n, offs, rows, cols, key=key,
                                                                       workspace=ws_f)
             v["copy"] = lambda: ls.copy(keys, so, n)
             if with_torch:
@@ -147,6 +151,7 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--key", choices=["i32", "f32"], default="i32", help="f32: standard-normal float32 keys")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -155,4 +160,4 @@ if __name__ == "__main__":
     if a.sweep:
         sweep_main(a.logn, a.reps, out)
     else:
-        shapes_main(a.logn, a.reps, out, not a.no_torch)
+        shapes_main(a.logn, a.reps, out, not a.no_torch, a.key)

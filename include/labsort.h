@@ -61,6 +61,30 @@ extern "C" {
 /* key types: how the 32-bit words are ordered */
 #define LABSORT_KEY_U32 0
 #define LABSORT_KEY_I32 1
+/* IEEE-754 binary32.  A word x is ordered by its image
+ *   ord(x) = 0xFFFFFFFF        if x is a NaN ((x & 0x7FFFFFFF) > 0x7F800000)
+ *          = ~x                if the sign bit is set
+ *          = x | 0x80000000    otherwise
+ * in plain uint32 order: -inf < ... < -0.0 < +0.0 < ... < +inf < NaN.  -0.0 sorts before +0.0
+ * (the two stay distinct words, so the result is deterministic); every NaN equals every other
+ * and is greater than everything else, as in torch.sort / torch.topk.  Ties, NaNs included,
+ * are broken by position wherever an entry promises stability or a tie order.  Non-NaN keys
+ * come back bit-exact.  A NaN comes back as a NaN, its sign and payload not promised: paths
+ * that sort the image write unord(0xFFFFFFFF) = 0x7FFFFFFF (labsort_sort_device,
+ * labsort_sort_pairs_device, the segmented sorts' LDS path, top-k), paths that gather from the
+ * input write the original word (the segmented sorts' general path in its pairs form), where
+ *   unord(o) = (o & 0x80000000) ? (o & 0x7FFFFFFF) : ~o.
+ * Accepted by labsort_sort_device, labsort_sort_pairs_device, labsort_sort_segments_device,
+ * labsort_sort_segments_pairs_device and labsort_topk_device only; every other entry that
+ * checks its key type returns LABSORT_ERR_ARG for it (host-pointer, multi-GPU and distributed
+ * sorts, labsort_merge_runs, labsort_upper_bound, the C++ drop-ins).  The building blocks
+ * that take a key type without checking it order U32 / I32 words only. */
+#define LABSORT_KEY_F32 2
+/* The order image of a key word, and its inverse (host functions; the kernels compile the same
+ * definition): U32 word, I32 word ^ 0x80000000, F32 ord(word) / unord(bits) as above.  An
+ * unknown key type gives the word back. */
+uint32_t labsort_key_order_bits(uint32_t word, int key_type);
+uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type);
 
 /* generator distributions (oracle/cpu_sort.cpp uses the same codes and formula) */
 #define LABSORT_DIST_U32 0
@@ -100,7 +124,11 @@ size_t labsort_merge_tile_keys(void);             /* output keys per merge workg
 /* Bytes of device workspace labsort_sort_device needs for n keys. */
 size_t labsort_workspace_bytes(size_t n, int algo);
 /* Sort n keys from d_in into d_out (d_in == d_out allowed: in place).
- * Asynchronous on `stream`; no host synchronisation, graph-capturable. */
+ * Asynchronous on `stream`; no host synchronisation, graph-capturable.
+ * key_type LABSORT_KEY_F32: one streaming kernel writes the order image of d_in into d_out, the
+ * sort runs in place on it as LABSORT_KEY_U32 with the same algo and workspace, one streaming
+ * kernel undoes the image in place: two more sweeps over the keys (about 0.37 ms each at 2^28).
+ * d_in is not written when d_out differs; NaNs come back as 0x7FFFFFFF. */
 int labsort_sort_device(const void *d_in, void *d_out, size_t n, int key_type, int algo, void *d_workspace,
                         size_t workspace_bytes, void *stream);
 /* Host pointer in/out, synchronous: the order_array contract (lab.cu:303).
@@ -250,7 +278,10 @@ int labsort_test_fault(const char *phase, int rank);
  * algo: LABSORT_ALGO_RADIX (8-bit LSD onesweep passes carrying the payload),
  * LABSORT_ALGO_MERGE (LDS tile sort of labsort_pair_tile_keys() pairs + merge-path
  * passes) or LABSORT_ALGO_AUTO (merge up to LABSORT_AUTO_PAIRS_MERGE_MAX_KEYS, radix above).
- * Asynchronous on `stream`, no allocation; d_ws >= labsort_pairs_workspace_bytes(n, algo). */
+ * Asynchronous on `stream`, no allocation; d_ws >= labsort_pairs_workspace_bytes(n, algo).
+ * key_type LABSORT_KEY_F32: as labsort_sort_device, around the same sort in place on the outputs;
+ * an out-of-place call also copies the payloads to d_vals_out first (three more sweeps), and the
+ * inputs are not written.  Stable: equal keys, -0.0 and +0.0 apart, NaNs as one value. */
 size_t labsort_pair_tile_keys(void);
 size_t labsort_pairs_workspace_bytes(size_t n, int algo);
 int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void *d_keys_out, void *d_vals_out,
@@ -280,7 +311,12 @@ int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void
  * call then returns without touching the key and payload buffers.
  * labsort_segments_workspace_status synchronises `stream` and returns LABSORT_ERR_ARG for
  * rejected offsets, LABSORT_ERR_DEVICE if an inner pair sort of the general path reported
- * an error, else LABSORT_OK. */
+ * an error, else LABSORT_OK.
+ * key_type LABSORT_KEY_F32 on the LDS path: the class kernels take the order image of a key
+ * as they load it and undo it as they store it, so the call still reads and writes every key
+ * once (NaNs come back as 0x7FFFFFFF).  On the general path the inner pair sorts take the key
+ * type (labsort_sort_pairs_device): the keys form writes NaNs as 0x7FFFFFFF, the pairs form
+ * gathers the original words. */
 /* longest segment the one-pass LDS path sorts (keys only / key+payload) */
 size_t labsort_segment_tile_keys(void);
 size_t labsort_segment_pair_tile_keys(void);
@@ -306,6 +342,10 @@ int labsort_segments_workspace_status(const void *d_workspace, void *stream);
  * back untransformed: best first, equal keys in order of position, and of the ties of the k-th
  * key those with the lowest positions.  The output, indices included, is a deterministic
  * function of the input (torch.topk leaves the tie order open).
+ * key_type LABSORT_KEY_F32: the same with u(x) = ord(x) ^ (largest ? 0xFFFFFFFF : 0), ord as at
+ * LABSORT_KEY_F32 above: NaNs are the largest keys, -0.0 is below +0.0, ties (NaNs among
+ * themselves included) go by position.  The image is taken where the select's kernels read the
+ * input and undone where the k keys are written (no extra pass); NaNs come back as 0x7FFFFFFF.
  * 1 <= k <= cols, rows * cols <= 2^31 - 1; rows == 0 or k == 0 launches nothing.
  * LABSORT_ERR_ARG before any launch: NULL d_keys / d_keys_out, a bad key type, k > cols, a
  * missing or short workspace, an output that overlaps the input, d_idx_out == d_keys_out, and

@@ -28,7 +28,9 @@ LIB_PATH = os.environ.get("LABSORT_LIBRARY") or os.path.join(HERE, "liblabsort.s
 
 OK, ERR_ARG, ERR_HIP, ERR_DEVICE, ERR_PEER = 0, 1, 2, 3, 4
 ALGO = {"radix": 0, "merge": 1, "radix1": 2, "auto": 3}
-KEY = {"u32": 0, "i32": 1}
+# "f32": IEEE-754 order with -0.0 < +0.0 and every NaN equal and last; the device sorts, the segmented
+# sorts and top-k take it, the host-pointer and multi-GPU entries do not (labsort.h)
+KEY = {"u32": 0, "i32": 1, "f32": 2}
 DIST = {"u32": 0, "u31": 1, "mod100": 2, "mod1000": 3, "sorted": 4, "reversed": 5, "const": 6, "lowbits": 7}
 KCLASS = {"histogram": 0, "onesweep": 1, "tile_sort": 2, "merge": 3, "partition": 4, "gsweep": 5, "gcopy": 6,
           "copy": 7, "merge4": 8, "segsort": 9, "topk": 10}
@@ -55,6 +57,7 @@ C_SYMBOLS = [
     "labsort_segments_workspace_bytes", "labsort_sort_segments_device", "labsort_sort_segments_pairs_device",
     "labsort_segments_workspace_status",
     "labsort_topk_workspace_bytes", "labsort_topk_device", "labsort_topk_workspace_status",
+    "labsort_key_order_bits", "labsort_key_from_order_bits",
 ]
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
 MULTI_PHASES = ["h2d", "local_sort", "plan", "exchange", "merge", "d2h", "total", "plan_work", "plan_wait"]
@@ -188,6 +191,10 @@ def _load() -> ctypes.CDLL:
     L.labsort_topk_workspace_bytes.argtypes = [sz, sz, sz]
     L.labsort_topk_device.argtypes = [p, sz, sz, sz, i, i, p, p, p, sz, p]
     L.labsort_topk_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_key_order_bits"):  # (as labsort_radix_path above)
+        for f in ("labsort_key_order_bits", "labsort_key_from_order_bits"):
+            getattr(L, f).restype = ctypes.c_uint32
+            getattr(L, f).argtypes = [ctypes.c_uint32, i]
     L.labsort_histogram.argtypes = [p, sz, i, i, p, p]
     L.labsort_fill.argtypes = [p, sz, u64, i, u64, u64, p]
     L.labsort_count_descents.argtypes = [p, sz, i, p, p]
@@ -496,7 +503,8 @@ def _workspace(workspace, nbytes):
 
 def sort_device(d_in, d_out, n: int, key: str = "u32", algo: str = "radix", workspace=None,
                 workspace_bytes_: int | None = None, stream=None) -> None:
-    """Sort n keys d_in -> d_out (may alias) asynchronously on `stream`.
+    """Sort n keys d_in -> d_out (may alias) asynchronously on `stream`.  key: "u32", "i32" or
+    "f32" (float32 tensors as they are: IEEE-754 order, -0.0 < +0.0, NaNs equal and last).
 
     With a caller-owned `workspace` the call stays asynchronous; check the kernels'
     own error report with workspace_status() once the result is needed.  Without
@@ -655,7 +663,8 @@ def topk_device(d_keys, rows: int, cols: int, k: int, d_keys_out, d_idx_out=None
     """The k smallest (largest) keys of every row of the dense rows x cols matrix d_keys, best
     first, into d_keys_out (rows x k), and their positions within the row into d_idx_out (rows x k
     int32 / uint32 words, or None): torch.topk(x, k, largest=..., sorted=True) with the tie order
-    fixed (equal keys in order of position; of the k-th key's ties the lowest positions).  With a
+    fixed (equal keys in order of position; of the k-th key's ties the lowest positions).  key="f32":
+    float32 tensors as they are, NaNs the largest keys and equal to each other, -0.0 below +0.0.  With a
     caller-owned `workspace` the call stays asynchronous (check topk_workspace_status when the
     result is needed); without one it allocates, synchronises and checks."""
     workspace, wsb, own = _workspace(workspace, lambda: topk_workspace_bytes(rows, cols, k))
@@ -670,6 +679,17 @@ def topk_workspace_status(workspace, stream=None) -> None:
     """Synchronise `stream`; raise LabsortError with ERR_DEVICE if an inner sort of the last
     topk_device call on `workspace` reported a failure."""
     _check(lib.labsort_topk_workspace_status(_ptr(workspace), _stream(stream)), "topk (status)")
+
+
+def key_order_bits(word: int, key: str = "u32") -> int:
+    """The uint32 whose plain order is the key type's order of `word` (labsort_key_order_bits):
+    u32 the word, i32 the word ^ 0x80000000, f32 the IEEE-754 order image (every NaN 0xFFFFFFFF)."""
+    return int(lib.labsort_key_order_bits(int(word) & 0xFFFFFFFF, KEY[key]))
+
+
+def key_from_order_bits(bits: int, key: str = "u32") -> int:
+    """The inverse of key_order_bits (f32: the NaN image comes back as 0x7FFFFFFF)."""
+    return int(lib.labsort_key_from_order_bits(int(bits) & 0xFFFFFFFF, KEY[key]))
 
 
 def histogram(d_keys, n: int, d_hist, bits: int = 8, key: str = "u32", stream=None) -> None:

@@ -477,6 +477,13 @@ size_t labsort_max_keys(int algo) {
     if (algo == LABSORT_ALGO_MERGE || algo == LABSORT_ALGO_AUTO) return (size_t)0x7FFFFFFFu;
     return RADIX_MAX_N;
 }
+uint32_t labsort_key_order_bits(uint32_t word, int key_type) {
+    return key_type == LABSORT_KEY_F32 ? f32_ord(word) : word ^ flip_of(key_type);
+}
+uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type) {
+    return key_type == LABSORT_KEY_F32 ? f32_unord(bits) : bits ^ flip_of(key_type);
+}
+
 size_t labsort_tile_keys(void) { return (size_t)TS_TILE; }
 size_t labsort_merge_tile_keys(void) { return (size_t)MG_TILE; }
 size_t labsort_merge_parts(size_t n) { return (n + MG_TILE - 1) / MG_TILE + 2; }
@@ -499,7 +506,7 @@ int labsort_sort_device(const void *d_in, void *d_out, size_t n, int key_type, i
                         size_t ws_bytes, void *stream) {
     if (n == 0) return LABSORT_OK;
     if (!d_in || !d_out) return LABSORT_ERR_ARG;
-    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (!device_key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (algo != LABSORT_ALGO_RADIX && algo != LABSORT_ALGO_MERGE && algo != LABSORT_ALGO_RADIX1 &&
         algo != LABSORT_ALGO_AUTO)
         return LABSORT_ERR_ARG;
@@ -510,6 +517,13 @@ int labsort_sort_device(const void *d_in, void *d_out, size_t n, int key_type, i
     hipStream_t s = as_stream(stream);
     const uint32_t *in = static_cast<const uint32_t *>(d_in);
     uint32_t *out = static_cast<uint32_t *>(d_out);
+    if (key_type == LABSORT_KEY_F32) {
+        // the order image into d_out, the sort in place on it as uint32, the image undone in place
+        HIP_TRY(launch_f32_map(in, out, n, false, s));
+        if (const int st = labsort_sort_device(out, out, n, LABSORT_KEY_U32, algo, d_ws, ws_bytes, stream)) return st;
+        HIP_TRY(launch_f32_map(out, out, n, true, s));
+        return LABSORT_OK;
+    }
     if (small_path(n, algo)) {
         TimingScope ts(LABSORT_K_TILE_SORT, s);
         HIP_TRY(launch_tile_sort(in, out, n, flip, s));
@@ -790,7 +804,7 @@ int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void
                               size_t n, int key_type, int algo, void *d_ws, size_t ws_bytes, void *stream) {
     if (n == 0) return LABSORT_OK;
     if (!d_keys_in || !d_vals_in || !d_keys_out || !d_vals_out) return LABSORT_ERR_ARG;
-    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (!device_key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (algo != LABSORT_ALGO_RADIX && algo != LABSORT_ALGO_MERGE && algo != LABSORT_ALGO_AUTO) return LABSORT_ERR_ARG;
     algo = resolve_pairs_algo(algo, n);
     if (n > (algo == LABSORT_ALGO_MERGE ? (size_t)0x7FFFFFFFu : RADIX_MAX_N)) return LABSORT_ERR_ARG;
@@ -800,6 +814,16 @@ int labsort_sort_pairs_device(const void *d_keys_in, const void *d_vals_in, void
     hipStream_t s = as_stream(stream);
     const uint32_t *ki = static_cast<const uint32_t *>(d_keys_in), *vi = static_cast<const uint32_t *>(d_vals_in);
     uint32_t *ko = static_cast<uint32_t *>(d_keys_out), *vo = static_cast<uint32_t *>(d_vals_out);
+    if (key_type == LABSORT_KEY_F32) {
+        // the order image into keys_out (out of place: the payloads copied beside it, since only a
+        // fully in-place call may alias), the sort in place on it as uint32, the image undone
+        HIP_TRY(launch_f32_map(ki, ko, n, false, s));
+        if (vi != vo) HIP_TRY(launch_stream_copy(vi, vo, n, s));
+        if (const int st = labsort_sort_pairs_device(ko, vo, ko, vo, n, LABSORT_KEY_U32, algo, d_ws, ws_bytes, stream))
+            return st;
+        HIP_TRY(launch_f32_map(ko, ko, n, true, s));
+        return LABSORT_OK;
+    }
     if (n <= (size_t)TS_TILE_KV) {
         TimingScope ts(LABSORT_K_TILE_SORT, s);
         HIP_TRY(launch_tile_sort_kv(ki, ko, vi, vo, n, flip, s));

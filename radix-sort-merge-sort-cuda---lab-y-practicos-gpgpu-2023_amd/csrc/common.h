@@ -8,6 +8,16 @@ namespace labsort {
 
 constexpr int WAVE = 64;
 
+// ---- float32 keys (LABSORT_KEY_F32): the order image of an IEEE-754 binary32 word ----
+// Plain uint32 order on f32_ord(x) is -inf < ... < -0.0 < +0.0 < ... < +inf < NaN, every NaN
+// equal (0xFFFFFFFF).  f32_unord inverts it for every non-NaN word; the NaN image comes back
+// as 0x7FFFFFFF.  The one definition: the kernels and labsort_key_order_bits compile this.
+__host__ __device__ inline uint32_t f32_ord(uint32_t x) {
+    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
+    return (x & 0x80000000u) ? ~x : x | 0x80000000u;
+}
+__host__ __device__ inline uint32_t f32_unord(uint32_t o) { return (o & 0x80000000u) ? o & 0x7FFFFFFFu : ~o; }
+
 // ---- radix configuration (8-bit digits, onesweep) ----
 constexpr int RADIX_BITS = 8;
 constexpr int OS_BLOCK = 512;     // threads per onesweep workgroup (8 waves)
@@ -222,6 +232,8 @@ void verify_or_exit(const char *who, const int *a, size_t n, const KeyPrint &bef
 
 hipError_t launch_zero(void *p, size_t bytes, hipStream_t s);  // graph-replayable memset (16-B aligned p)
 hipError_t launch_stream_copy(const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);
+// out[i] = f32_ord(in[i]), inverse: f32_unord (in == out allowed; 16-B accesses where both are aligned)
+hipError_t launch_f32_map(const uint32_t *in, uint32_t *out, size_t n, bool inverse, hipStream_t s);
 hipError_t launch_count_descents(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *count, hipStream_t s);
 
 }  // namespace labsort

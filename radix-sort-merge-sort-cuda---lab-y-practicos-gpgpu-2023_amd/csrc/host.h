@@ -21,6 +21,10 @@ inline uint32_t flip_of(int key_type) { return key_type == LABSORT_KEY_I32 ? 0x8
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline bool key_type_ok(int key_type) { return key_type == LABSORT_KEY_U32 || key_type == LABSORT_KEY_I32; }
+// The entries that also order float32 keys: the device sorts, the segmented sorts and top-k.  F32
+// has no uniform flip (flip_of gives 0): those entries apply f32_ord / f32_unord (common.h)
+// where a key enters and leaves, and everything between orders the image as uint32.
+inline bool device_key_type_ok(int key_type) { return key_type_ok(key_type) || key_type == LABSORT_KEY_F32; }
 // Key/value calls are in place only as a whole: one side aliased and the other not would
 // read payloads that the key side's passes already overwrote.  Keys and payloads never
 // share their output.

@@ -1645,6 +1645,39 @@ __global__ __launch_bounds__(256) void k_word_copy(const uint32_t *__restrict__ 
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) b[i] = a[i];
 }
 
+// b[i] = f32_ord(a[i]) (INV: f32_unord), a == b allowed: the streaming copy's shape with the
+// float32 order map between its loads and stores (the whole-array F32 sorts' two sweeps).
+template <bool INV>
+__device__ __forceinline__ u32x4 f32_map4(u32x4 v) {
+    u32x4 r;
+    r.x = INV ? f32_unord(v.x) : f32_ord(v.x);
+    r.y = INV ? f32_unord(v.y) : f32_ord(v.y);
+    r.z = INV ? f32_unord(v.z) : f32_ord(v.z);
+    r.w = INV ? f32_unord(v.w) : f32_ord(v.w);
+    return r;
+}
+template <bool INV>
+__global__ __launch_bounds__(1024) void k_f32_map(const u32x4 *a, u32x4 *b, size_t n4) {
+    const size_t ntiles = n4 / 4096;
+    const uint32_t tid = threadIdx.x;
+    for (size_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const u32x4 *s = a + t * 4096 + tid;
+        u32x4 k[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) k[j] = __builtin_nontemporal_load(s + j * 1024);
+        u32x4 *d = b + t * 4096 + tid;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(f32_map4<INV>(k[j]), d + j * 1024);
+    }
+    for (size_t i = ntiles * 4096 + (size_t)blockIdx.x * 1024 + tid; i < n4; i += (size_t)gridDim.x * 1024)
+        b[i] = f32_map4<INV>(a[i]);
+}
+template <bool INV>
+__global__ __launch_bounds__(256) void k_f32_map_words(const uint32_t *a, uint32_t *b, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        b[i] = INV ? f32_unord(a[i]) : f32_ord(a[i]);
+}
+
 // ---------------------------------------------------------------------------------
 // verification helper
 // ---------------------------------------------------------------------------------
@@ -1878,6 +1911,23 @@ hipError_t launch_stream_copy(const uint32_t *in, uint32_t *out, size_t n, hipSt
         k_word_copy<<<blocks_for(n, 256 * 16, 4096), 256, 0, s>>>(in, out, n);
     }
     return hipGetLastError();
+}
+
+template <bool INV>
+static hipError_t launch_f32_map_t(const uint32_t *in, uint32_t *out, size_t n, hipStream_t s) {
+    if (((((uintptr_t)in) | ((uintptr_t)out)) & 15u) == 0) {
+        const size_t n4 = n / 4;
+        if (n4) k_f32_map<INV><<<(unsigned)cu_count(), 1024, 0, s>>>(reinterpret_cast<const u32x4 *>(in), reinterpret_cast<u32x4 *>(out), n4);
+        if (n % 4) k_f32_map_words<INV><<<1, 256, 0, s>>>(in + n4 * 4, out + n4 * 4, n % 4);
+    } else {
+        k_f32_map_words<INV><<<blocks_for(n, 256 * 16, 4096), 256, 0, s>>>(in, out, n);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_f32_map(const uint32_t *in, uint32_t *out, size_t n, bool inverse, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    return inverse ? launch_f32_map_t<true>(in, out, n, s) : launch_f32_map_t<false>(in, out, n, s);
 }
 
 hipError_t launch_count_descents(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *count, hipStream_t s) {

@@ -68,9 +68,10 @@ hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max
                           uint32_t *hdr, uint32_t *lists, size_t stride, hipStream_t s);
 // The LDS path's sort launches: the kernel of every class that max_len admits, each over its list
 // (lists + c * stride).  Host arguments only: the launch sequence is fixed.  vin/vout nullptr: keys only.
+// f32: the keys are float32 words, ordered by (f32_ord(key) ^ flip) and written back as words.
 hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in, uint32_t *out, const uint32_t *vin,
                                   uint32_t *vout, const uint32_t *off, const uint32_t *hdr, const uint32_t *lists,
-                                  size_t stride, uint32_t flip, hipStream_t s);
+                                  size_t stride, uint32_t flip, bool f32, hipStream_t s);
 // ---- the hybrid radix sort's finish (api.hip's sort_radix8) ----
 // After the scatter passes on digits 2 and 3 every bucket of the top 16 bits is a contiguous
 // range; the finish finds the 65537 bucket offsets and sorts each bucket with the class kernels

@@ -10,6 +10,8 @@
 //   k_seg_block  block and tile classes: k_tile_sort's LDS passes on a [start, end) range,
 //                one workgroup per segment, grid-stride over the class list
 //   k_seg_ids, k_seg_gather, k_seg_err_acc   the general path's glue around the pair sorts
+// k_seg_wave and k_seg_block live in seg_kernels.h: this file compiles their integer-key
+// instantiations, segsort_f32.hip the float32 ones.
 //
 // Every kernel after k_seg_bin reads the workspace's error word first and returns when
 // it is set, so rejected offsets never become addresses.
@@ -18,8 +20,8 @@
 #include <algorithm>
 
 #include "devutil.h"
-#include "lds_pass.h"
 #include "host.h"
+#include "seg_kernels.h"
 
 namespace labsort {
 
@@ -87,251 +89,6 @@ __global__ __launch_bounds__(BIN_BLOCK) void k_seg_bin(const uint32_t *__restric
 }
 
 // ---------------------------------------------------------------------------------
-// wave class
-// ---------------------------------------------------------------------------------
-template <int KPT, bool KV>
-struct SwSmem {
-    uint32_t keys[WAVE * KPT];
-    uint32_t vals[KV ? WAVE * KPT : 1];
-    uint32_t hist[256];
-    uint32_t probe[WAVE];
-};
-
-template <int KPT, bool KV>
-__global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_seg_wave(const uint32_t *in, uint32_t *out, const uint32_t *vin,
-                                                                  uint32_t *vout, const uint32_t *__restrict__ off,
-                                                                  const uint32_t *__restrict__ hdr,
-                                                                  const uint32_t *__restrict__ list, int cls,
-                                                                  uint32_t flip, HySel hy) {
-    constexpr uint32_t CAP = WAVE * KPT;
-    __shared__ SwSmem<KPT, KV> sm_all[SEG_WAVE_WPB];
-    if (hy.plan) {  // the radix sort's finish: the plan's choice first, and the buffer it names
-        if (hy.plan->hybrid == 0u) return;
-        in = hy.buf[hy.plan->fin_src];
-    }
-    if (ld_agent(hdr) != 0u) return;  // rejected offsets: touch nothing
-    const uint32_t cnt = hdr[SEG_HDR_CNT + cls];
-    const uint32_t lane = threadIdx.x & 63u, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (blockIdx.x * SEG_WAVE_WPB + wid >= cnt) return;  // (an empty class costs its launch only)
-    SwSmem<KPT, KV> &sm = sm_all[wid];
-    const uint32_t sentinel = ~flip;
-    const bool atomic_rank = lds_lane_ordered(sm.probe, lane);
-    for (uint32_t it = blockIdx.x * SEG_WAVE_WPB + wid; it < cnt; it += gridDim.x * SEG_WAVE_WPB) {
-        const uint32_t seg = __builtin_amdgcn_readfirstlane(list[it]);
-        const uint32_t b = __builtin_amdgcn_readfirstlane(off[seg]);
-        const uint32_t len = __builtin_amdgcn_readfirstlane(off[seg + 1]) - b;
-        if (len == 0u || len > CAP) continue;
-        if (len <= (uint32_t)WAVE) {
-            // one key per lane: its stable rank is the count of keys before it in (key, lane) order
-            const bool ok = lane < len;
-            const uint32_t x = ok ? (in[b + lane] ^ flip) : 0xFFFFFFFFu;
-            uint32_t v = 0u;
-            if constexpr (KV) v = ok ? vin[b + lane] : 0u;
-            uint32_t r = 0u;
-            for (uint32_t i = 0; i < len; ++i) {
-                const uint32_t xi = __builtin_amdgcn_readlane(x, (int)i);
-                r += (xi < x || (xi == x && i < lane)) ? 1u : 0u;
-            }
-            if (ok) {  // r < len: fewer than len keys come before one of them
-                out[b + r] = x ^ flip;
-                if constexpr (KV) vout[b + r] = v;
-            }
-            continue;
-        }
-        const uint32_t jn = (len + WAVE - 1u) / WAVE;  // 64-key groups that hold keys (<= KPT)
-        uint32_t k[KPT];
-        uint32_t v[KV ? KPT : 1];
-        uint32_t a = ~0u, o = 0u;
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const uint32_t idx = (uint32_t)j * WAVE + lane;
-            const bool ok = idx < len;
-            k[j] = ok ? in[b + idx] : sentinel;
-            if constexpr (KV) v[j] = ok ? vin[b + idx] : 0u;
-            const uint32_t x = k[j] ^ flip;
-            a &= ok ? x : ~0u;
-            o |= ok ? x : 0u;
-        }
-        wave_and_or(a, o);
-        const uint32_t diff = __builtin_amdgcn_readfirstlane(a ^ o);
-        for (int pass = 0; pass < 4; ++pass) {
-            const uint32_t shift = pass * 8;
-            if (((diff >> shift) & 0xFFu) == 0u) continue;  // uniform over the segment
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sm.hist[q * WAVE + lane] = 0u;
-            __builtin_amdgcn_wave_barrier();
-            uint32_t rank[KPT];
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                rank[j] = 0u;
-                if ((uint32_t)j < jn)  // wave-uniform; a group past the end holds padding only
-                    rank[j] = rank8(sm.hist, ((k[j] ^ flip) >> shift) & 0xFFu, lane, atomic_rank);
-            }
-            __builtin_amdgcn_wave_barrier();
-            {  // exclusive scan of the 256 counters: four per lane, then across the wave
-                uint32_t c[4], s = 0u;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    c[q] = sm.hist[4u * lane + q];
-                    s += c[q];
-                }
-                uint32_t xs = s;
-#pragma unroll
-                for (int offx = 1; offx < 64; offx <<= 1) {
-                    const uint32_t t = __shfl_up(xs, offx);
-                    if (lane >= (uint32_t)offx) xs += t;
-                }
-                uint32_t run = xs - s;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    sm.hist[4u * lane + q] = run;
-                    run += c[q];
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int j = 0; j < KPT; ++j)
-                if ((uint32_t)j < jn) rank[j] += sm.hist[((k[j] ^ flip) >> shift) & 0xFFu];  // < 64 jn <= CAP
-#pragma unroll
-            for (int j = 0; j < KPT; ++j)
-                if ((uint32_t)j < jn) {
-                    sm.keys[rank[j]] = k[j];
-                    if constexpr (KV) sm.vals[rank[j]] = v[j];
-                }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int j = 0; j < KPT; ++j)
-                if ((uint32_t)j < jn) {
-                    k[j] = sm.keys[(uint32_t)j * WAVE + lane];
-                    if constexpr (KV) v[j] = sm.vals[(uint32_t)j * WAVE + lane];
-                }
-            __builtin_amdgcn_wave_barrier();
-        }
-        // padding sorts behind every key (stable, largest digits), so slots < len hold the keys
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const uint32_t idx = (uint32_t)j * WAVE + lane;
-            if (idx < len) {
-                out[b + idx] = k[j];
-                if constexpr (KV) vout[b + idx] = v[j];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// block and tile classes: the passes k_tile_sort runs (lds_sort_passes, lds_pass.h) on one
-// segment per workgroup.  The segment is striped over the waves in runs of
-// S = 64 ceil(len / (64 W)) slots, so a short segment of the class costs every wave the same
-// few 64-key groups; groups that start past the end are neither ranked nor read back
-// (LeadingGroups).
-// ---------------------------------------------------------------------------------
-template <int BLOCK, int KPT, bool KV, int WPE = 4>
-__global__ __launch_bounds__(BLOCK, WPE) void k_seg_block(const uint32_t *in, uint32_t *out, const uint32_t *vin,
-                                                           uint32_t *vout, const uint32_t *__restrict__ off,
-                                                           const uint32_t *__restrict__ hdr,
-                                                           const uint32_t *__restrict__ list, int cls, uint32_t flip,
-                                                           HySel hy) {
-    using S = TsSmem<BLOCK, KPT, KV>;
-    constexpr int W = S::W;
-    constexpr uint32_t TILE = S::TILE;
-    __shared__ S sm;
-    if (hy.plan) {  // the radix sort's finish: the plan's choice first, and the buffer it names
-        if (hy.plan->hybrid == 0u) return;
-        in = hy.buf[hy.plan->fin_src];
-    }
-    if (ld_agent(hdr) != 0u) return;  // rejected offsets: touch nothing
-    const uint32_t cnt = hdr[SEG_HDR_CNT + cls];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t sentinel = ~flip;
-    if (blockIdx.x >= cnt) return;  // (an empty class costs its launch only; uniform over the workgroup)
-    probe_lane_order(sm.probe, &sm.ordered, lane, wid);
-    __syncthreads();
-    const bool atomic_rank = lane_order_probed(&sm.ordered);
-    // the list entry and the two offsets are three dependent loads: those of the next segment
-    // are issued before this one is sorted
-    uint32_t nb = 0u, ne = 0u;
-    if (blockIdx.x < cnt) {
-        const uint32_t seg = __builtin_amdgcn_readfirstlane(list[blockIdx.x]);
-        nb = __builtin_amdgcn_readfirstlane(off[seg]);
-        ne = __builtin_amdgcn_readfirstlane(off[seg + 1]);
-    }
-    for (uint32_t it = blockIdx.x; it < cnt; it += gridDim.x) {
-        const uint32_t b = nb, len = ne - nb;
-        if (it + gridDim.x < cnt) {
-            const uint32_t seg = __builtin_amdgcn_readfirstlane(list[it + gridDim.x]);
-            nb = __builtin_amdgcn_readfirstlane(off[seg]);
-            ne = __builtin_amdgcn_readfirstlane(off[seg + 1]);
-        }
-        if (len == 0u || len > TILE) continue;  // (uniform over the workgroup)
-        const uint32_t jn = (len + (uint32_t)(W * WAVE) - 1u) / (uint32_t)(W * WAVE);  // groups per wave, <= KPT
-        const uint32_t ws0 = wid * jn * WAVE;  // first slot of this wave's stripe
-        // this wave's keys: nf whole 64-key groups and a last group of `tail` keys (wave-uniform),
-        // so whole groups load and store under scalar branches and one lane mask serves the last
-        const uint32_t rem = ws0 < len ? len - ws0 : 0u;
-        const uint32_t nf = min(jn, rem / WAVE);
-        const uint32_t tail = nf < jn ? rem - nf * WAVE : 0u;  // < 64
-        const uint32_t ng = nf + (tail ? 1u : 0u);             // groups that hold keys
-        const bool tail_ok = lane < tail;
-        // scalar base + 32-bit lane offset per access: the lane offsets pass through empty asms so no
-        // 64-bit per-lane address of in / out is formed outside the segment loop and held across it
-        const size_t sb = (size_t)b + ws0;
-        uint32_t lin = lane;
-        asm volatile("" : "+v"(lin));
-        uint32_t k[KPT];
-        uint32_t v[KV ? KPT : 1];
-        uint32_t a = ~0u, o = 0u;
-        // every load first, so all of them are in flight together (a use inside the scalar
-        // branches would wait for each load in turn), then the bits the keys differ in
-        if (nf == (uint32_t)KPT) {  // a whole tile: straight-line loads, as k_tile_sort
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) k[j] = ld_stream<NT_TILE>(in + sb + ((uint32_t)(j * WAVE) + lin));
-            if constexpr (KV) {
-#pragma unroll
-                for (int j = 0; j < KPT; ++j) v[j] = vin[sb + ((uint32_t)(j * WAVE) + lin)];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                k[j] = sentinel;
-                if constexpr (KV) v[j] = 0u;
-                if ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) {
-                    k[j] = ld_stream<NT_TILE>(in + sb + ((uint32_t)(j * WAVE) + lin));
-                    if constexpr (KV) v[j] = vin[sb + ((uint32_t)(j * WAVE) + lin)];
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const uint32_t x = k[j] ^ flip;  // padding: all ones
-            a &= x;
-            o |= ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) ? x : 0u;
-        }
-        const uint32_t diff = __builtin_amdgcn_readfirstlane(block_diff_bits<W>(a, o, sm.red_and, sm.red_or, lane, wid));
-        lds_sort_passes(sm, k, v, diff, flip, ws0, atomic_rank, LeadingGroups{ng}, lane, wid);
-        uint32_t nfs = nf, lout = lane;
-        asm volatile("" : "+s"(nfs), "+v"(lout));
-        if (nfs == (uint32_t)KPT) {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) out[sb + ((uint32_t)(j * WAVE) + lout)] = k[j];
-            if constexpr (KV) {
-#pragma unroll
-                for (int j = 0; j < KPT; ++j) vout[sb + ((uint32_t)(j * WAVE) + lout)] = v[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                if ((uint32_t)j < nfs || ((uint32_t)j == nfs && tail_ok)) {
-                    out[sb + ((uint32_t)(j * WAVE) + lout)] = k[j];
-                    if constexpr (KV) vout[sb + ((uint32_t)(j * WAVE) + lout)] = v[j];
-                }
-            }
-        }
-        __syncthreads();  // the next segment reuses red_and / red_or and the key slots
-    }
-}
-
-// ---------------------------------------------------------------------------------
 // general path glue
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_seg_ids(const uint32_t *__restrict__ off, uint32_t nseg, uint32_t n,
@@ -376,17 +133,6 @@ __global__ void k_seg_err_acc(uint32_t *hdr, uint32_t *inner) {
     }
 }
 
-int cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
 unsigned stream_blocks(size_t n) {
     size_t b = (n + 256 * 8 - 1) / (256 * 8);
     return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
@@ -395,29 +141,9 @@ unsigned stream_blocks(size_t n) {
 // The sort kernel of class c (0-2 wave, 3 block, 4 tile) over its list; vin/vout nullptr: keys only.
 hipError_t launch_seg_sort(int c, const uint32_t *in, uint32_t *out, const uint32_t *vin, uint32_t *vout,
                            const uint32_t *off, const uint32_t *hdr, const uint32_t *list, uint32_t flip,
-                           hipStream_t s, const HySel &hy = HySel{}) {
-    const bool kv = vin != nullptr;
-    const unsigned cus = (unsigned)cu_count();
-    // fixed grids, multiples of the CU count: what stays resident per CU by LDS
-    if (c == 0) {
-        if (kv) k_seg_wave<SEG_WAVE_KPT, true><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip, hy);
-        else k_seg_wave<SEG_WAVE_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 0, flip, hy);
-    } else if (c == 1) {
-        if (kv) k_seg_wave<SEG_WAVE2_KPT, true><<<cus * 6u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip, hy);
-        else k_seg_wave<SEG_WAVE2_KPT, false><<<cus * 8u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 1, flip, hy);
-    } else if (c == 2) {  // 110-127 VGPRs: four waves per SIMD
-        if (kv) k_seg_wave<SEG_WAVE3_KPT, true><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip, hy);
-        else k_seg_wave<SEG_WAVE3_KPT, false><<<cus * 4u, SEG_WAVE_WPB * WAVE, 0, s>>>(in, out, vin, vout, off, hdr, list, 2, flip, hy);
-    } else if (c == 3) {
-        if (kv) k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, true, SEG_BLOCK_WPE><<<cus * 4u, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip, hy);
-        else k_seg_block<SEG_BLOCK, SEG_BLOCK_KPT, false, SEG_BLOCK_WPE><<<cus * (unsigned)SEG_BLOCK_WGS, SEG_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 3, flip, hy);
-    } else if (c == 4) {
-        if (kv) k_seg_block<TS_BLOCK, TS_KPT_KV, true><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip, hy);
-        else k_seg_block<TS_BLOCK, TS_KPT, false><<<cus, TS_BLOCK, 0, s>>>(in, out, vin, vout, off, hdr, list, 4, flip, hy);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+                           hipStream_t s, const HySel &hy = HySel{}, bool f32 = false) {
+    return f32 ? launch_seg_sort_f32(c, in, out, vin, vout, off, hdr, list, flip, s, hy)
+               : launch_seg_sort_t<false>(c, in, out, vin, vout, off, hdr, list, flip, s, hy);
 }
 
 // general path helpers (all return at once when hdr word 0 is set)
@@ -455,13 +181,13 @@ hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max
 
 hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in, uint32_t *out, const uint32_t *vin,
                                   uint32_t *vout, const uint32_t *off, const uint32_t *hdr, const uint32_t *lists,
-                                  size_t stride, uint32_t flip, hipStream_t s) {
+                                  size_t stride, uint32_t flip, bool f32, hipStream_t s) {
     size_t edges[SEG_CLASSES];
     labsort_segment_class_edges(pairs ? 1 : 0, edges, SEG_CLASSES);
     int ncls = 1;
     while (ncls < SEG_CLASSES && max_len > edges[ncls - 1]) ++ncls;
     for (int c = 0; c < ncls; ++c) {
-        const hipError_t e = launch_seg_sort(c, in, out, vin, vout, off, hdr, lists + (size_t)c * stride, flip, s);
+        const hipError_t e = launch_seg_sort(c, in, out, vin, vout, off, hdr, lists + (size_t)c * stride, flip, s, HySel{}, f32);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -616,7 +342,7 @@ int sort_segments(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t
     const bool pairs = vi != nullptr || vo != nullptr;
     if (n == 0) return LABSORT_OK;
     if (!ki || !ko || !off || (pairs && (!vi || !vo))) return LABSORT_ERR_ARG;
-    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (!device_key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (nseg == 0 || n > (size_t)0x7FFFFFFFu || nseg > (size_t)0x7FFFFFFFu) return LABSORT_ERR_ARG;
     if (pairs && !pairs_alias_ok(ki, vi, ko, vo)) return LABSORT_ERR_ARG;
     const bool lds = seg_lds_path(max_len, pairs ? 1 : 0);
@@ -633,7 +359,8 @@ int sort_segments(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t
         uint32_t *lists = reinterpret_cast<uint32_t *>(ws + L.off_lists);
         TimingScope ts(LABSORT_K_SEGSORT, s);
         HIP_TRY(launch_seg_bin(off, nseg, n, max_len, pairs, !inplace, hdr, lists, L.list_stride, s));
-        HIP_TRY(launch_seg_lds_classes(max_len, pairs, ki, ko, vi, vo, off, hdr, lists, L.list_stride, flip, s));
+        HIP_TRY(launch_seg_lds_classes(max_len, pairs, ki, ko, vi, vo, off, hdr, lists, L.list_stride, flip,
+                                       key_type == LABSORT_KEY_F32, s));
         return LABSORT_OK;
     }
     // general path: two stable pair sorts (by key, then by segment id) on workspace buffers;

@@ -1,6 +1,7 @@
 // topk.hip -- top-k selection: the k smallest or largest keys of every row, with their positions
 // (labsort_topk_device).  All kernels work on u = key ^ xr, where plain uint32 order is the
-// order asked for.
+// order asked for; for float32 keys (the F32 instantiations) u = f32_ord(key) ^ xr, formed where
+// the raw input is read and undone where the keys are written.
 //
 // Rows longer than the segmented sort's pair tile are selected by an MSD radix select with 8-bit
 // digits.  A row is cut into chunks of TK_CHUNK keys; per level:
@@ -84,12 +85,21 @@ __device__ __forceinline__ uint32_t tk_mis(const uint32_t *base, uint32_t beg) {
 }
 __device__ __forceinline__ uint32_t tk_quads(uint32_t beg, uint32_t end, uint32_t mis) { return (end - beg + mis + 3u) / 4u; }
 
+// F32: a word of the raw input (raw, uniform over the row) becomes its order image first; the
+// candidate buffer already holds u.
+template <bool F32>
+__device__ __forceinline__ uint32_t tk_word(uint32_t w, bool raw) {
+    if constexpr (F32) return raw ? f32_ord(w) : w;
+    else return w;
+}
+template <bool F32>
 __device__ __forceinline__ uint32_t tk_load_quad(const uint32_t *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
-                                                 uint32_t xr, uint32_t (&u)[4], int64_t &i0) {
+                                                 uint32_t xr, bool raw, uint32_t (&u)[4], int64_t &i0) {
     i0 = (int64_t)beg - (int64_t)mis + 4 * (int64_t)q;
     if (i0 >= (int64_t)beg && i0 + 4 <= (int64_t)end) {
         const uint4 v = *reinterpret_cast<const uint4 *>(base + i0);
-        u[0] = v.x ^ xr; u[1] = v.y ^ xr; u[2] = v.z ^ xr; u[3] = v.w ^ xr;
+        u[0] = tk_word<F32>(v.x, raw) ^ xr; u[1] = tk_word<F32>(v.y, raw) ^ xr;
+        u[2] = tk_word<F32>(v.z, raw) ^ xr; u[3] = tk_word<F32>(v.w, raw) ^ xr;
         return 15u;
     }
     uint32_t vm = 0u;
@@ -98,7 +108,7 @@ __device__ __forceinline__ uint32_t tk_load_quad(const uint32_t *base, uint32_t 
         const int64_t i = i0 + j;
         u[j] = 0u;
         if (i >= (int64_t)beg && i < (int64_t)end) {
-            u[j] = base[i] ^ xr;
+            u[j] = tk_word<F32>(base[i], raw) ^ xr;
             vm |= 1u << j;
         }
     }
@@ -142,6 +152,7 @@ __device__ __forceinline__ TkPick tk_pick(const uint32_t *hrow, uint32_t krem, u
     return p;
 }
 
+template <bool F32>
 __global__ __launch_bounds__(TK_BLOCK) void k_tk_hist(TkArgs a, int level, uint32_t nx, uint32_t g) {
     __shared__ uint32_t h[256 * TK_SLOTS];
     const uint32_t tid = threadIdx.x, slot = tid & (TK_SLOTS - 1u);
@@ -166,7 +177,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_hist(TkArgs a, int level, uint3
             for (int t = 0; t < 4; ++t) {
                 const uint32_t q = q0 + (uint32_t)t * TK_BLOCK + tid;
                 int64_t i0;
-                vm[t] = q < nq ? tk_load_quad(s.u, beg, end, mis, q, s.xr, u[t], i0) : 0u;
+                vm[t] = q < nq ? tk_load_quad<F32>(s.u, beg, end, mis, q, s.xr, s.p == nullptr, u[t], i0) : 0u;
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -267,7 +278,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_scan(TkArgs a, int level) {
 // whose top digits lie below the new prefix go to the survivor list, those that match it to the
 // candidate buffer.  FINAL = true: the keys below the threshold and the first krem keys equal to
 // it go to the survivor list.  Every store is bounds-checked against its list.
-template <bool FINAL>
+template <bool FINAL, bool F32>
 __global__ __launch_bounds__(TK_BLOCK) void k_tk_compact(TkArgs a, int level) {
     __shared__ uint32_t wsum[TK_BLOCK / WAVE], tot;
     const uint32_t tid = threadIdx.x;
@@ -295,7 +306,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_compact(TkArgs a, int level) {
         const uint32_t q = q0 + tid;
         uint32_t u[4], pos[4], vm = 0u;
         int64_t i0 = 0;
-        if (q < nq) vm = tk_load_quad(s.u, beg, end, mis, q, s.xr, u, i0);
+        if (q < nq) vm = tk_load_quad<F32>(s.u, beg, end, mis, q, s.xr, s.p == nullptr, u, i0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) pos[j] = (uint32_t)(i0 + j);
         if (s.p) {
@@ -351,11 +362,12 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_compact(TkArgs a, int level) {
     }
 }
 
+template <bool F32>
 __global__ __launch_bounds__(256) void k_tk_prep(const uint32_t *__restrict__ keys, uint32_t *__restrict__ u,
                                                  uint32_t *__restrict__ pos, size_t n, uint32_t cols, uint32_t xr) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (u) u[i] = keys[i] ^ xr;
+        if (u) u[i] = tk_word<F32>(keys[i], true) ^ xr;
         pos[i] = (uint32_t)i % cols;  // (n <= 2^31 - 1)
     }
 }
@@ -374,13 +386,16 @@ __global__ void k_tk_err_acc(uint32_t *hdr, const uint32_t *inner, int nw) {
 }
 
 // grid: x over the k outputs of a row, rows folded into x as well (row = block / bpr)
+template <bool F32>
 __global__ __launch_bounds__(256) void k_tk_write(const uint32_t *__restrict__ su, const uint32_t *__restrict__ sp,
                                                   uint32_t *__restrict__ ko, uint32_t *__restrict__ io, uint32_t m,
                                                   uint32_t k, uint32_t bpr, uint32_t xr) {
     const uint32_t row = blockIdx.x / bpr, bx = blockIdx.x - row * bpr;
     const size_t src = (size_t)row * m, dst = (size_t)row * k;
     for (uint32_t j = bx * 256u + threadIdx.x; j < k; j += bpr * 256u) {
-        ko[dst + j] = su[src + j] ^ xr;
+        const uint32_t w = su[src + j] ^ xr;
+        if constexpr (F32) ko[dst + j] = f32_unord(w);
+        else ko[dst + j] = w;
         if (io) io[dst + j] = sp[src + j];
     }
 }
@@ -390,10 +405,11 @@ unsigned tk_stream_blocks(size_t n) {
     return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
 }
 
-hipError_t launch_topk_hist(const TkArgs &a, size_t rows, int level, hipStream_t s) {
+hipError_t launch_topk_hist(const TkArgs &a, size_t rows, int level, bool f32, hipStream_t s) {
     const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
     const uint32_t nx = (a.nch + g - 1u) / g;
-    k_tk_hist<<<(unsigned)(rows * nx), TK_BLOCK, 0, s>>>(a, level, nx, g);
+    if (f32) k_tk_hist<true><<<(unsigned)(rows * nx), TK_BLOCK, 0, s>>>(a, level, nx, g);
+    else k_tk_hist<false><<<(unsigned)(rows * nx), TK_BLOCK, 0, s>>>(a, level, nx, g);
     return hipGetLastError();
 }
 
@@ -408,20 +424,23 @@ hipError_t launch_topk_scan(const TkArgs &a, size_t rows, int level, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_topk_narrow(const TkArgs &a, size_t rows, int level, hipStream_t s) {
-    k_tk_compact<false><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, level);
+hipError_t launch_topk_narrow(const TkArgs &a, size_t rows, int level, bool f32, hipStream_t s) {
+    if (f32) k_tk_compact<false, true><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, level);
+    else k_tk_compact<false, false><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, level);
     return hipGetLastError();
 }
 
-hipError_t launch_topk_final(const TkArgs &a, size_t rows, hipStream_t s) {
-    k_tk_compact<true><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, TK_LEVELS - 1);
+hipError_t launch_topk_final(const TkArgs &a, size_t rows, bool f32, hipStream_t s) {
+    if (f32) k_tk_compact<true, true><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, TK_LEVELS - 1);
+    else k_tk_compact<true, false><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, TK_LEVELS - 1);
     return hipGetLastError();
 }
 
-// u[i] = keys[i] ^ xr (u may be nullptr), pos[i] = i % cols
+// u[i] = keys[i] ^ xr (f32: f32_ord(keys[i]) ^ xr; u may be nullptr), pos[i] = i % cols
 hipError_t launch_topk_prep(const uint32_t *keys, uint32_t *u, uint32_t *pos, size_t n, size_t cols, uint32_t xr,
-                            hipStream_t s) {
-    k_tk_prep<<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
+                            bool f32, hipStream_t s) {
+    if (f32) k_tk_prep<true><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
+    else k_tk_prep<false><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
     return hipGetLastError();
 }
 
@@ -437,14 +456,16 @@ hipError_t launch_topk_err_acc(uint32_t *hdr, const uint32_t *inner, int nw, hip
     return hipGetLastError();
 }
 
-// keys_out[r][j] = su[r * m + j] ^ xr, idx_out[r][j] = sp[r * m + j] for j < k (idx_out may be nullptr)
+// keys_out[r][j] = su[r * m + j] ^ xr (f32: f32_unord of it), idx_out[r][j] = sp[r * m + j] for j < k
+// (idx_out may be nullptr)
 hipError_t launch_topk_write(const uint32_t *su, const uint32_t *sp, uint32_t *keys_out, uint32_t *idx_out, size_t rows,
-                             size_t m, size_t k, uint32_t xr, hipStream_t s) {
+                             size_t m, size_t k, uint32_t xr, bool f32, hipStream_t s) {
     // blocks per row: enough for one key per thread, fewer when there are many rows
     size_t bpr = (k + 255) / 256;
     const size_t room = ((size_t)1 << 20) / rows;
     if (bpr > room) bpr = room ? room : 1;
-    k_tk_write<<<(unsigned)(rows * bpr), 256, 0, s>>>(su, sp, keys_out, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    if (f32) k_tk_write<true><<<(unsigned)(rows * bpr), 256, 0, s>>>(su, sp, keys_out, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    else k_tk_write<false><<<(unsigned)(rows * bpr), 256, 0, s>>>(su, sp, keys_out, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
     return hipGetLastError();
 }
 
@@ -550,7 +571,7 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
                         void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
     if (rows == 0 || k == 0) return LABSORT_OK;
     if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
-    if (!key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (!device_key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
     if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
     if (ranges_overlap(d_keys, rows * cols * 4, d_keys_out, rows * k * 4)) return LABSORT_ERR_ARG;
@@ -561,6 +582,7 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
     if (!d_ws || ws_bytes < labsort_topk_workspace_bytes(rows, cols, k)) return LABSORT_ERR_ARG;
     const TopkLayout L = topk_layout_path(rows, cols, k, path);
     const uint32_t xr = flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
+    const bool f32 = key_type == LABSORT_KEY_F32;  // u = f32_ord(key) ^ xr
     hipStream_t s = as_stream(stream);
     char *ws = static_cast<char *>(d_ws);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t *>(ws + off); };
@@ -574,10 +596,10 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
         TimingScope ts(LABSORT_K_TOPK, s);
         uint32_t *lists = W(L.off_lists);
         HIP_TRY(launch_topk_offsets(offs, rows, cols, s));
-        HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, s));
+        HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, false, s));
         HIP_TRY(launch_seg_bin(offs, rows, n, cols, true, true, hdr, lists, L.list_stride, s));
-        HIP_TRY(launch_seg_lds_classes(cols, true, keys, SU, B, SP, offs, hdr, lists, L.list_stride, xr, s));
-        HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, cols, k, 0u, s));  // (the class kernels wrote keys, not u)
+        HIP_TRY(launch_seg_lds_classes(cols, true, keys, SU, B, SP, offs, hdr, lists, L.list_stride, xr, f32, s));
+        HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, cols, k, 0u, false, s));  // (the class kernels wrote keys, not u)
         return LABSORT_OK;
     }
     if (path == TK_PATH_SELECT) {
@@ -602,15 +624,15 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
         a.cap = (uint32_t)L.cap;
         a.xr = xr;
         for (int level = 0; level < TK_LEVELS; ++level) {
-            HIP_TRY(launch_topk_hist(a, rows, level, s));
+            HIP_TRY(launch_topk_hist(a, rows, level, f32, s));
             HIP_TRY(launch_topk_reduce(a, rows, level, s));
             HIP_TRY(launch_topk_scan(a, rows, level, s));
-            if (level < TK_LEVELS - 1 && L.cap > 0) HIP_TRY(launch_topk_narrow(a, rows, level, s));
+            if (level < TK_LEVELS - 1 && L.cap > 0) HIP_TRY(launch_topk_narrow(a, rows, level, f32, s));
         }
-        HIP_TRY(launch_topk_final(a, rows, s));
+        HIP_TRY(launch_topk_final(a, rows, f32, s));
     } else {
         TimingScope ts(LABSORT_K_TOPK, s);
-        HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, s));
+        HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, f32, s));
     }
     // order the m pairs of every row on u (stable): one pair sort, or the segmented pair sort
     char *iws = ws + L.off_inner;
@@ -631,7 +653,7 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
     }
     TimingScope ts(LABSORT_K_TOPK, s);
     HIP_TRY(launch_topk_err_acc(hdr, ierr, 2, s));
-    HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, L.m, k, xr, s));
+    HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, L.m, k, xr, f32, s));
     return LABSORT_OK;
 }
 

@@ -13,6 +13,17 @@ as it would for a caller with float data:
 Every variant of a shape is timed in turn, repetition by repetition (device events around one
 call), after one warm-up each; median [min, max] ms over the repetitions.
 
+--key bf16 / f16 (output kept in profiles/f16_keys.txt): standard-normal values
+rounded to the type, on the three shapes 1 x n k 1024, n/2^16 x 2^16 k 64, n/4096 x 4096 k 8:
+  topk      labsort_topk_device on the 16-bit tensor
+  f32       the float32 call on the same values widened beforehand: the yardstick
+  widen     x.float(), the pass a caller without 16-bit keys pays before it
+  torch     torch.topk on the 16-bit tensor
+  copy      labsort_copy of the input's bytes
+--parent PATH (--key i32 / f32): the same top-k call through another build of liblabsort.so,
+alternating with this one (the regression check of a change to topk.hip).
+--largest: the k largest, as torch.topk's default.
+
 --sweep: the large-k threshold.  One row of 2^logn keys, k from 2^10 up to the whole row, with the
 path forced either way (LABSORT_TOPK_PATH=select / sort, read at every call), alternating."""
 import argparse
@@ -74,6 +85,88 @@ def check(keys, rows, cols, k, ko, io):
     assert torch.equal(ko.view(rows, k), exp), (rows, cols, k)
     assert torch.equal(torch.gather(x, 1, io.view(rows, k).long()), exp), (rows, cols, k)
     del exp
+
+
+def parent_topk(path):
+    """labsort_topk_device of another build of the library (same signature), as a callable."""
+    import ctypes
+    L = ctypes.CDLL(path)
+    p, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    L.labsort_topk_device.argtypes = [p, sz, sz, sz, i, i, p, p, p, sz, p]
+
+    def call(keys, rows, cols, k, ko, io, largest, key, ws):
+        st = L.labsort_topk_device(keys.data_ptr(), rows, cols, k, 1 if largest else 0, ls.KEY[key], ko.data_ptr(), io.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        assert st == 0, st
+    return call
+
+
+def f16_main(logn, reps, out, with_torch, key, largest):
+    """16-bit keys against the float32 call on the same values (module docstring)."""
+    n = 1 << logn
+    dt = torch.bfloat16 if key == "bf16" else torch.float16
+    x32 = torch.empty(n, dtype=torch.float32, device="cuda")
+    x32.normal_(generator=torch.Generator(device="cuda").manual_seed(0x70C0EED))
+    x = x32.to(dt)       # rounded to the type
+    x32.copy_(x)         # the same values, widened beforehand
+    cp = torch.empty_like(x)
+    print(f"# top-k, {key} keys (standard normal, rounded to the type), {'largest' if largest else 'smallest'} k with positions, "
+          f"n = 2^{logn}, {reps} alternating repetitions, ms: median [min, max]", file=out)
+    print(f"# device: {torch.cuda.get_device_name(0)}; {ls.version()}", file=out)
+    for rows, cols, k in [(1, n, 1024), (n >> 16, 1 << 16, 64), (n >> 12, 4096, 8)]:
+        ko = torch.empty(rows * k, dtype=dt, device="cuda")
+        ko32 = torch.empty(rows * k, dtype=torch.float32, device="cuda")
+        io = torch.empty(rows * k, dtype=torch.int32, device="cuda")
+        io32 = torch.empty_like(io)
+        ws = torch.full((ls.topk_workspace_bytes(rows, cols, k),), 0xFF, dtype=torch.uint8, device="cuda")
+        v = {"topk": lambda: ls.topk_device(x, rows, cols, k, ko, io, largest=largest, key=key, workspace=ws),
+             "f32": lambda: ls.topk_device(x32, rows, cols, k, ko32, io32, largest=largest, key="f32", workspace=ws),
+             "widen": lambda: x.float(),
+             "copy": lambda: ls.copy(x, cp, n // 2)}
+        if with_torch:
+            v["torch"] = lambda: torch.topk(x.view(rows, cols), k, dim=1, largest=largest, sorted=True)
+        t = alternate(v, reps)
+        ko.zero_()
+        v["topk"]()
+        ls.topk_workspace_status(ws)
+        v["f32"]()
+        ls.topk_workspace_status(ws)
+        # the same values and, the order maps agreeing, the same positions as the float32 call
+        assert torch.equal(ko.float(), ko32) and torch.equal(io, io32), (rows, cols, k)
+        assert torch.equal(torch.gather(x.view(rows, cols), 1, io.view(rows, k).long()), ko.view(rows, k)), (rows, cols, k)
+        path = "short" if cols <= ls.segment_pair_tile_keys() else ("sort" if k * ls.TOPK_SORT_DIV > cols else "select")
+        print(f"{key:<6}{rows:>6} x {cols:<10} k {k:<6} {path:<7}" + "  ".join(f"{name} {fmt(ts)}" for name, ts in t.items()) +
+              f"  topk/f32 {med(t['topk']) / med(t['f32']):.3f}  topk/(f32+widen) {med(t['topk']) / (med(t['f32']) + med(t['widen'])):.3f}"
+              f"  topk/copy {med(t['topk']) / med(t['copy']):.2f}", file=out)
+        out.flush()
+        del ws, ko, ko32, io, io32
+
+
+def parent_main(logn, reps, out, key, largest, path):
+    """This build against another one (--parent) on the 16-bit shapes, int32 or float32 keys."""
+    n = 1 << logn
+    other = parent_topk(path)
+    keys = torch.empty(n, dtype=torch.float32 if key == "f32" else torch.int32, device="cuda")
+    if key == "f32":
+        keys.normal_(generator=torch.Generator(device="cuda").manual_seed(0x70C0EED))
+    else:
+        ls.fill(keys, n, seed=0x70C0EED, dist="u32")
+    print(f"# top-k, {key} keys, {'largest' if largest else 'smallest'} k with positions, n = 2^{logn}: this build (new) against "
+          f"{path} (parent), {reps} alternating repetitions, ms: median [min, max]", file=out)
+    print(f"# device: {torch.cuda.get_device_name(0)}; {ls.version()}", file=out)
+    for rows, cols, k in [(1, n, 1024), (n >> 16, 1 << 16, 64), (n >> 12, 4096, 8)]:
+        ko, ko2 = (torch.empty(rows * k, dtype=keys.dtype, device="cuda") for _ in range(2))
+        io, io2 = (torch.empty(rows * k, dtype=torch.int32, device="cuda") for _ in range(2))
+        ws = torch.full((ls.topk_workspace_bytes(rows, cols, k),), 0xFF, dtype=torch.uint8, device="cuda")
+        v = {"new": lambda: ls.topk_device(keys, rows, cols, k, ko, io, largest=largest, key=key, workspace=ws),
+             "parent": lambda: other(keys, rows, cols, k, ko2, io2, largest, key, ws)}
+        t = alternate(v, reps)
+        torch.cuda.synchronize()
+        assert torch.equal(ko.view(torch.int32), ko2.view(torch.int32)) and torch.equal(io, io2), (rows, cols, k)
+        print(f"{key:<6}{rows:>6} x {cols:<10} k {k:<6}" + "  ".join(f"{name} {fmt(ts)}" for name, ts in t.items()) +
+              f"  new/parent {med(t['new']) / med(t['parent']):.3f}", file=out)
+        out.flush()
+        del ws, ko, ko2, io, io2
 
 
 def shapes_main(logn, reps, out, with_torch, key="i32"):
@@ -151,7 +244,10 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--no-torch", action="store_true")
-    ap.add_argument("--key", choices=["i32", "f32"], default="i32", help="f32: standard-normal float32 keys")
+    ap.add_argument("--key", choices=["i32", "f32", "bf16", "f16"], default="i32",
+                    help="f32: standard-normal float32 keys; bf16 / f16: the same rounded to the type, against the f32 call")
+    ap.add_argument("--largest", action="store_true", help="bf16 / f16 and --parent runs: the k largest")
+    ap.add_argument("--parent", default="", help="another build of liblabsort.so to alternate with (i32 / f32)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -159,5 +255,9 @@ if __name__ == "__main__":
     out = open(a.out, "a") if a.out else sys.stdout
     if a.sweep:
         sweep_main(a.logn, a.reps, out)
+    elif a.key in ("bf16", "f16"):
+        f16_main(a.logn, a.reps, out, not a.no_torch, a.key, a.largest)
+    elif a.parent:
+        parent_main(a.logn, a.reps, out, a.key, a.largest, a.parent)
     else:
         shapes_main(a.logn, a.reps, out, not a.no_torch, a.key)

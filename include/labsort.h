@@ -80,9 +80,22 @@ extern "C" {
  * sorts, labsort_merge_runs, labsort_upper_bound, the C++ drop-ins).  The building blocks
  * that take a key type without checking it order U32 / I32 words only. */
 #define LABSORT_KEY_F32 2
+/* bfloat16 and IEEE-754 binary16: 16-bit elements, accepted by labsort_topk_device ONLY (every
+ * other entry that checks its key type returns LABSORT_ERR_ARG for them, the segmented and
+ * whole-array device sorts included).  The float32 contract at 16 bits: with T = 0x7F80 (bfloat16)
+ * or 0x7C00 (binary16), an element x is ordered by
+ *   ord16(x) = 0xFFFF         if (x & 0x7FFF) > T   (every NaN, either sign)
+ *            = ~x & 0xFFFF    if x & 0x8000
+ *            = x | 0x8000     otherwise
+ * so -inf < ... < -0.0 < +0.0 < ... < +inf < NaN, every NaN equal and last, ties (NaNs included)
+ * by position; non-NaN keys come back bit-exact and a NaN as 0x7FFF, a NaN in both formats, by
+ *   unord16(o) = (o & 0x8000) ? (o & 0x7FFF) : (~o & 0xFFFF). */
+#define LABSORT_KEY_BF16 3
+#define LABSORT_KEY_F16 4
 /* The order image of a key word, and its inverse (host functions; the kernels compile the same
- * definition): U32 word, I32 word ^ 0x80000000, F32 ord(word) / unord(bits) as above.  An
- * unknown key type gives the word back. */
+ * definition): U32 word, I32 word ^ 0x80000000, F32 ord(word) / unord(bits) as above; BF16 / F16
+ * ord16 / unord16 of the argument's low 16 bits, a result in [0, 0xFFFF].  An unknown key type
+ * gives the word back. */
 uint32_t labsort_key_order_bits(uint32_t word, int key_type);
 uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type);
 
@@ -346,6 +359,13 @@ int labsort_segments_workspace_status(const void *d_workspace, void *stream);
  * LABSORT_KEY_F32 above: NaNs are the largest keys, -0.0 is below +0.0, ties (NaNs among
  * themselves included) go by position.  The image is taken where the select's kernels read the
  * input and undone where the k keys are written (no extra pass); NaNs come back as 0x7FFFFFFF.
+ * key_type LABSORT_KEY_BF16 / LABSORT_KEY_F16: d_keys is rows x cols and d_keys_out rows x k
+ * 16-bit elements (both 2-byte aligned, else LABSORT_ERR_ARG; the overlap checks use these
+ * sizes), d_idx_out stays uint32.  u(x) = ord16(x) ^ (largest ? 0xFFFF : 0), ord16 as at
+ * LABSORT_KEY_BF16 above; NaNs come back as 0x7FFF.  The kernels that read the input load eight
+ * keys per 16 bytes and widen each to (ord16(x) << 16): the select runs two digit levels, not
+ * four, and everything behind the input reads keeps its 32-bit layout.  Paths, thresholds,
+ * limits and the workspace size are those of the 32-bit key types.
  * 1 <= k <= cols, rows * cols <= 2^31 - 1; rows == 0 or k == 0 launches nothing.
  * LABSORT_ERR_ARG before any launch: NULL d_keys / d_keys_out, a bad key type, k > cols, a
  * missing or short workspace, an output that overlaps the input, d_idx_out == d_keys_out, and

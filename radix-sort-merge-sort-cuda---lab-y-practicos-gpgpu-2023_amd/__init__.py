@@ -30,7 +30,8 @@ OK, ERR_ARG, ERR_HIP, ERR_DEVICE, ERR_PEER = 0, 1, 2, 3, 4
 ALGO = {"radix": 0, "merge": 1, "radix1": 2, "auto": 3}
 # "f32": IEEE-754 order with -0.0 < +0.0 and every NaN equal and last; the device sorts, the segmented
 # sorts and top-k take it, the host-pointer and multi-GPU entries do not (labsort.h)
-KEY = {"u32": 0, "i32": 1, "f32": 2}
+# "bf16", "f16": 16-bit elements, the same order at 16 bits; top-k alone takes them
+KEY = {"u32": 0, "i32": 1, "f32": 2, "bf16": 3, "f16": 4}
 DIST = {"u32": 0, "u31": 1, "mod100": 2, "mod1000": 3, "sorted": 4, "reversed": 5, "const": 6, "lowbits": 7}
 KCLASS = {"histogram": 0, "onesweep": 1, "tile_sort": 2, "merge": 3, "partition": 4, "gsweep": 5, "gcopy": 6,
           "copy": 7, "merge4": 8, "segsort": 9, "topk": 10}
@@ -664,7 +665,9 @@ def topk_device(d_keys, rows: int, cols: int, k: int, d_keys_out, d_idx_out=None
     first, into d_keys_out (rows x k), and their positions within the row into d_idx_out (rows x k
     int32 / uint32 words, or None): torch.topk(x, k, largest=..., sorted=True) with the tie order
     fixed (equal keys in order of position; of the k-th key's ties the lowest positions).  key="f32":
-    float32 tensors as they are, NaNs the largest keys and equal to each other, -0.0 below +0.0.  With a
+    float32 tensors as they are, NaNs the largest keys and equal to each other, -0.0 below +0.0;
+    key="bf16" / "f16": the same for torch.bfloat16 / torch.float16 tensors (d_keys and d_keys_out hold
+    16-bit elements, d_idx_out stays 32-bit).  With a
     caller-owned `workspace` the call stays asynchronous (check topk_workspace_status when the
     result is needed); without one it allocates, synchronises and checks."""
     workspace, wsb, own = _workspace(workspace, lambda: topk_workspace_bytes(rows, cols, k))
@@ -673,6 +676,27 @@ def topk_device(d_keys, rows: int, cols: int, k: int, d_keys_out, d_idx_out=None
                                    _stream(stream)), "topk_device")
     if own:
         topk_workspace_status(workspace, stream)
+
+
+def topk(x, k: int, largest: bool = True, workspace=None, stream=None):
+    """(values, indices) of the k largest (smallest) keys of every row of x, best first: topk_device
+    with its outputs allocated.  x: a contiguous 1-D (one row) or 2-D CUDA tensor of dtype int32,
+    float32, bfloat16 or float16; values has x's dtype and shape (rows, k), indices is int32 (rows, k).
+    TypeError for another dtype or a non-contiguous tensor, before the device is touched.  Workspace
+    and status as topk_device."""
+    import torch
+    keys = {torch.int32: "i32", torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+    if not isinstance(x, torch.Tensor) or x.dtype not in keys:
+        raise TypeError(f"topk: int32, float32, bfloat16 or float16 tensor expected, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() not in (1, 2) or not x.is_contiguous():
+        raise TypeError("topk: a contiguous 1-D or 2-D tensor expected")
+    if not x.is_cuda:
+        raise TypeError("topk: a CUDA tensor expected")
+    rows, cols = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    values = torch.empty((rows, k), dtype=x.dtype, device=x.device)
+    indices = torch.empty((rows, k), dtype=torch.int32, device=x.device)
+    topk_device(x, rows, cols, k, values, indices, largest=largest, key=keys[x.dtype], workspace=workspace, stream=stream)
+    return values, indices
 
 
 def topk_workspace_status(workspace, stream=None) -> None:

@@ -478,9 +478,11 @@ size_t labsort_max_keys(int algo) {
     return RADIX_MAX_N;
 }
 uint32_t labsort_key_order_bits(uint32_t word, int key_type) {
+    if (key_type_is16(key_type)) return ord16(word, nan_t16(key_type));
     return key_type == LABSORT_KEY_F32 ? f32_ord(word) : word ^ flip_of(key_type);
 }
 uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type) {
+    if (key_type_is16(key_type)) return unord16(bits & 0xFFFFu);
     return key_type == LABSORT_KEY_F32 ? f32_unord(bits) : bits ^ flip_of(key_type);
 }
 

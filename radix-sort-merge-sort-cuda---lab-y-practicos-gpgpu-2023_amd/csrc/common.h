@@ -18,6 +18,18 @@ __host__ __device__ inline uint32_t f32_ord(uint32_t x) {
 }
 __host__ __device__ inline uint32_t f32_unord(uint32_t o) { return (o & 0x80000000u) ? o & 0x7FFFFFFFu : ~o; }
 
+// ---- 16-bit float keys (LABSORT_KEY_BF16, LABSORT_KEY_F16; top-k only): the float32 contract at
+// 16 bits.  nan_t is the word of +inf, above which (sign cleared) a word is a NaN: 0x7F80 for
+// bfloat16, 0x7C00 for float16.  The image lies in [0, 0xFFFF], every NaN at 0xFFFF; unord16
+// gives the NaN image back as 0x7FFF, a NaN in both formats.  Only the low 16 bits of x count.
+constexpr uint32_t BF16_NAN_T = 0x7F80u, F16_NAN_T = 0x7C00u;
+__host__ __device__ inline uint32_t ord16(uint32_t x, uint32_t nan_t) {
+    x &= 0xFFFFu;
+    if ((x & 0x7FFFu) > nan_t) return 0xFFFFu;
+    return (x & 0x8000u) ? ~x & 0xFFFFu : x | 0x8000u;
+}
+__host__ __device__ inline uint32_t unord16(uint32_t o) { return (o & 0x8000u) ? o & 0x7FFFu : ~o & 0xFFFFu; }
+
 // ---- radix configuration (8-bit digits, onesweep) ----
 constexpr int RADIX_BITS = 8;
 constexpr int OS_BLOCK = 512;     // threads per onesweep workgroup (8 waves)

@@ -25,6 +25,11 @@ inline bool key_type_ok(int key_type) { return key_type == LABSORT_KEY_U32 || ke
 // has no uniform flip (flip_of gives 0): those entries apply f32_ord / f32_unord (common.h)
 // where a key enters and leaves, and everything between orders the image as uint32.
 inline bool device_key_type_ok(int key_type) { return key_type_ok(key_type) || key_type == LABSORT_KEY_F32; }
+// Top-k alone also takes 16-bit float keys (2-byte elements): it widens them to
+// ord16(key) << 16 where it reads the input, so everything behind that orders uint32 as before.
+inline bool key_type_is16(int key_type) { return key_type == LABSORT_KEY_BF16 || key_type == LABSORT_KEY_F16; }
+inline uint32_t nan_t16(int key_type) { return key_type == LABSORT_KEY_BF16 ? BF16_NAN_T : F16_NAN_T; }
+inline bool topk_key_type_ok(int key_type) { return device_key_type_ok(key_type) || key_type_is16(key_type); }
 // Key/value calls are in place only as a whole: one side aliased and the other not would
 // read payloads that the key side's passes already overwrote.  Keys and payloads never
 // share their output.

@@ -1,7 +1,11 @@
 // topk.hip -- top-k selection: the k smallest or largest keys of every row, with their positions
 // (labsort_topk_device).  All kernels work on u = key ^ xr, where plain uint32 order is the
 // order asked for; for float32 keys (the F32 instantiations) u = f32_ord(key) ^ xr, formed where
-// the raw input is read and undone where the keys are written.
+// the raw input is read and undone where the keys are written.  For the 16-bit float key types
+// (the k_tk_*16 kernels) the input is 2-byte elements and u = (ord16(key) << 16) ^ xr with
+// xr = largest ? 0xFFFF0000 : 0: the kernels that read the raw input load eight keys per 16 bytes
+// and widen them, two digit levels decide the threshold, and everything behind the input reads
+// (candidate buffer, survivor list, the inner sorts) keeps its 32-bit layout.
 //
 // Rows longer than the segmented sort's pair tile are selected by an MSD radix select with 8-bit
 // digits.  A row is cut into chunks of TK_CHUNK keys; per level:
@@ -12,10 +16,10 @@
 //                 levels) and at d (eq)
 //   k_tk_scan     one workgroup per row: exclusive scans of low and eq over the chunks, the next
 //                 level's state, and whether the row narrows
-//   k_tk_compact  <false>, levels 0-2, rows that narrow: one ordered pass over the input writes
-//                 the keys below the bucket to the survivor list and the bucket to the candidate
-//                 buffer; <true>, after level 3: the keys below the threshold and the first krem
-//                 keys equal to it go to the survivor list
+//   k_tk_compact  <false>, every level but the last, rows that narrow: one ordered pass over the
+//                 input writes the keys below the bucket to the survivor list and the bucket to the
+//                 candidate buffer; <true>, after the last level (3; 1 for 16-bit keys): the keys
+//                 below the threshold and the first krem keys equal to it go to the survivor list
 // Chunks are contiguous and every compaction places a chunk's keys at the chunk's scanned base in
 // thread order, so keys of one value reach the survivor list in position order: the stable sort
 // of the survivors that follows gives the tie rule for nothing.
@@ -25,6 +29,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "devutil.h"
 #include "host.h"
@@ -46,7 +51,7 @@ struct TkState {
 };
 
 struct TkArgs {
-    const uint32_t *keys;                    // rows x cols, as the caller gave them
+    const uint32_t *keys;                    // rows x cols, as the caller gave them (16-bit key types: 2-byte elements)
     uint32_t *hist;                          // [rows][TK_LEVELS][256]
     uint32_t *cnt;                           // [rows][nch][256]: each chunk's counts of the current level
     uint32_t *low, *eq, *lowbase, *eqbase;   // [rows][nch]: keys below the prefix / in the bucket, and their exclusive scans
@@ -58,8 +63,15 @@ struct TkArgs {
 
 namespace {
 
+// What the raw input holds: the launchers pick the kernels by it.
+enum TkKey : int { TK_INT, TK_F32, TK_BF16, TK_F16 };
+constexpr bool tk_is16(int kt) { return kt == TK_BF16 || kt == TK_F16; }
+constexpr uint32_t tk_nan_t(int kt) { return kt == TK_BF16 ? BF16_NAN_T : F16_NAN_T; }
+
 struct TkSrc {
-    const uint32_t *u, *p;  // p == nullptr: the input (position = index, u = word ^ xr)
+    // p == nullptr: the input (position = index, u = word ^ xr).  Of a 16-bit input only count
+    // and xr are used: its elements are addressed through tk_raw16
+    const uint32_t *u, *p;
     uint32_t count, xr;
 };
 
@@ -109,6 +121,48 @@ __device__ __forceinline__ uint32_t tk_load_quad(const uint32_t *base, uint32_t 
         u[j] = 0u;
         if (i >= (int64_t)beg && i < (int64_t)end) {
             u[j] = tk_word<F32>(base[i], raw) ^ xr;
+            vm |= 1u << j;
+        }
+    }
+    return vm;
+}
+
+// The same for a raw input of 16-bit elements: octs of eight keys that start 16-byte aligned, so
+// mis is 0 .. 7 elements (the base is 2-byte aligned, a row of odd length starts anywhere).  An
+// oct inside the range is one 16-byte load, the head and the tail are read element by element;
+// every key is widened to u = (ord16(key) << 16) ^ xr.
+__device__ __forceinline__ const uint16_t *tk_raw16(const TkArgs &a, uint32_t row) {
+    return reinterpret_cast<const uint16_t *>(a.keys) + (size_t)row * a.cols;
+}
+__device__ __forceinline__ uint32_t tk_mis16(const uint16_t *base, uint32_t beg) {
+    return (uint32_t)(((uintptr_t)(base + beg) >> 1) & 7u);
+}
+__device__ __forceinline__ uint32_t tk_octs(uint32_t beg, uint32_t end, uint32_t mis) { return (end - beg + mis + 7u) / 8u; }
+template <int KT>
+__device__ __forceinline__ uint32_t tk_u16(uint32_t x, uint32_t xr) {
+    return (ord16(x, tk_nan_t(KT)) << 16) ^ xr;
+}
+template <int KT>
+__device__ __forceinline__ uint32_t tk_load_oct(const uint16_t *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
+                                                uint32_t xr, uint32_t (&u)[8], int64_t &i0) {
+    i0 = (int64_t)beg - (int64_t)mis + 8 * (int64_t)q;
+    if (i0 >= (int64_t)beg && i0 + 8 <= (int64_t)end) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(base + i0);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            u[2 * j] = tk_u16<KT>(w[j], xr);  // (ord16 reads the low half)
+            u[2 * j + 1] = tk_u16<KT>(w[j] >> 16, xr);
+        }
+        return 255u;
+    }
+    uint32_t vm = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int64_t i = i0 + j;
+        u[j] = 0u;
+        if (i >= (int64_t)beg && i < (int64_t)end) {
+            u[j] = tk_u16<KT>(base[i], xr);
             vm |= 1u << j;
         }
     }
@@ -199,6 +253,79 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_hist(TkArgs a, int level, uint3
     if (tid < 256u && acc) atomicAdd(&a.hist[((size_t)row * TK_LEVELS + level) * 256u + tid], acc);
 }
 
+// ---- the 16-bit call's kernels (KT = TK_BF16 / TK_F16).  They are kernels of their own, and the
+// 32-bit kernels keep their text: written once for both key widths, k_tk_hist and k_tk_compact
+// came out with other register counts for the 32-bit key types. ----
+
+// Counts into h (LDS) the level's digit of the keys of [beg, end) that match the prefix.  E keys
+// per load: 8 keys of the raw 16-bit input (raw16), or 4 words of the candidate buffer; either
+// way a thread has 16 keys in flight.
+template <int E, int KT>
+__device__ __forceinline__ void tk_hist_chunk(uint32_t *h, const TkSrc &s, const uint16_t *raw16, uint32_t beg, uint32_t end,
+                                              uint32_t prefix, uint32_t mask, uint32_t shift, uint32_t tid, uint32_t slot) {
+    constexpr int T = 16 / E;
+    uint32_t mis, nq;
+    if constexpr (E == 8) {
+        mis = tk_mis16(raw16, beg);
+        nq = tk_octs(beg, end, mis);
+    } else {
+        mis = tk_mis(s.u, beg);
+        nq = tk_quads(beg, end, mis);
+    }
+    for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)T * TK_BLOCK) {
+        uint32_t u[T][E], vm[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint32_t q = q0 + (uint32_t)t * TK_BLOCK + tid;
+            int64_t i0;
+            if constexpr (E == 8) vm[t] = q < nq ? tk_load_oct<KT>(raw16, beg, end, mis, q, s.xr, u[t], i0) : 0u;
+            else vm[t] = q < nq ? tk_load_quad<false>(s.u, beg, end, mis, q, s.xr, false, u[t], i0) : 0u;
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u)
+                    atomicAdd(&h[((u[t][j] >> shift) & 255u) * TK_SLOTS + slot], 1u);
+    }
+}
+
+// k_tk_hist: a row that has not narrowed is read from the raw input, eight keys per load; a
+// narrowed one from its candidate buffer of 32-bit u.
+template <int KT>
+__global__ __launch_bounds__(TK_BLOCK) void k_tk_hist16(TkArgs a, int level, uint32_t nx, uint32_t g) {
+    __shared__ uint32_t h[256 * TK_SLOTS];
+    const uint32_t tid = threadIdx.x, slot = tid & (TK_SLOTS - 1u);
+    const uint32_t row = blockIdx.x / nx, bx = blockIdx.x - row * nx;
+    const TkState st = tk_state(a, row, level);
+    const TkSrc s = tk_src(a, row, st);
+    const uint16_t *raw16 = tk_raw16(a, row);
+    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
+    const uint32_t c0 = bx * g;
+    if (c0 >= nact) return;
+    const uint32_t c1 = c0 + g < nact ? c0 + g : nact;
+    const uint32_t shift = 24u - 8u * (uint32_t)level;
+    const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+    uint32_t acc = 0u;
+    for (uint32_t c = c0; c < c1; ++c) {
+        for (uint32_t i = tid; i < 256u * TK_SLOTS; i += TK_BLOCK) h[i] = 0u;
+        __syncthreads();
+        const uint32_t beg = c * TK_CHUNK, end = beg + TK_CHUNK < s.count ? beg + TK_CHUNK : s.count;
+        if (s.p == nullptr) tk_hist_chunk<8, KT>(h, s, raw16, beg, end, st.prefix, mask, shift, tid, slot);  // (uniform over the workgroup)
+        else tk_hist_chunk<4, KT>(h, s, raw16, beg, end, st.prefix, mask, shift, tid, slot);
+        __syncthreads();
+        if (tid < 256u) {
+            uint32_t sum = 0u;
+#pragma unroll 8
+            for (uint32_t q = 0; q < (uint32_t)TK_SLOTS; ++q) sum += h[tid * TK_SLOTS + ((q + tid) & (TK_SLOTS - 1u))];
+            a.cnt[((size_t)row * a.nch + c) * 256u + tid] = sum;
+            acc += sum;
+        }
+        __syncthreads();
+    }
+    if (tid < 256u && acc) atomicAdd(&a.hist[((size_t)row * TK_LEVELS + level) * 256u + tid], acc);
+}
+
 constexpr int TK_RED_WAVES = 4;
 
 __global__ __launch_bounds__(TK_RED_WAVES * WAVE) void k_tk_reduce(TkArgs a, int level, uint32_t nx) {
@@ -231,6 +358,8 @@ __global__ __launch_bounds__(TK_RED_WAVES * WAVE) void k_tk_reduce(TkArgs a, int
     }
 }
 
+// NLEV: the call's digit levels (4; 2 for 16-bit keys): no row narrows after the last one
+template <int NLEV>
 __global__ __launch_bounds__(TK_BLOCK) void k_tk_scan(TkArgs a, int level) {
     __shared__ uint32_t wsum[TK_BLOCK / WAVE], tot[2];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
@@ -260,7 +389,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_scan(TkArgs a, int level) {
         __syncthreads();
     }
     if (tid == 0u) {
-        const bool narrow = !st.narrowed && level < TK_LEVELS - 1 && p.bucket <= a.cap;
+        const bool narrow = !st.narrowed && level < NLEV - 1 && p.bucket <= a.cap;
         TkState ns;
         ns.prefix = st.prefix | (p.d << (24u - 8u * (uint32_t)level));
         ns.krem = st.krem - p.below;
@@ -362,6 +491,112 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_compact(TkArgs a, int level) {
     }
 }
 
+// k_tk_compact for a 16-bit call (KT = TK_BF16 / TK_F16).  The pass is written once for E keys per
+// thread and batch (ec): octs of the raw 16-bit input (every narrowing pass, and the final one of
+// a row that never narrowed), or quads of the candidate buffer.
+template <bool FINAL, int KT>
+__global__ __launch_bounds__(TK_BLOCK) void k_tk_compact16(TkArgs a, int level) {
+    __shared__ uint32_t wsum[TK_BLOCK / WAVE], tot;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = blockIdx.x / a.nch, chunk = blockIdx.x - row * a.nch;
+    const TkState ns = a.st[(size_t)row * (TK_LEVELS + 1) + level + 1];
+    if (!FINAL && !ns.jn) return;
+    TkState from = ns;
+    if (!FINAL) from.narrowed = 0u;  // a row narrows once, from the input
+    const TkSrc s = tk_src(a, row, from);
+    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
+    if (chunk >= nact) return;
+    const size_t idx = (size_t)row * a.nch + chunk;
+    const uint32_t eqb = a.eqbase[idx];
+    // (FINAL: nothing of this chunk is taken: no key below the threshold, its equals past the last one taken)
+    if (FINAL && a.low[idx] == 0u && eqb >= ns.krem) return;
+    const uint32_t lob = a.lowbase[idx] + (FINAL ? ns.sbase : 0u);
+    const uint32_t mask = FINAL ? 0xFFFFFFFFu : 0xFFFFFFFFu << (24u - 8u * (uint32_t)level);
+    const uint32_t P = ns.prefix;
+    uint32_t *su = a.surv_u + (size_t)row * a.k, *sp = a.surv_p + (size_t)row * a.k;
+    uint32_t *cu = a.cand_u + (size_t)row * a.capa, *cp = a.cand_p + (size_t)row * a.capa;
+    const uint32_t beg = chunk * TK_CHUNK, end = beg + TK_CHUNK < s.count ? beg + TK_CHUNK : s.count;
+    const uint16_t *raw16 = tk_raw16(a, row);
+    auto pass = [&](auto ec) {
+        constexpr int E = decltype(ec)::value;
+        // one scan for both counts, 16 bits each: a batch holds at most 8192 keys
+        static_assert(E * TK_BLOCK <= 65535, "the packed scan holds two 16-bit counts per batch");
+        uint32_t mis, nq;
+        if constexpr (E == 8) {
+            mis = tk_mis16(raw16, beg);
+            nq = tk_octs(beg, end, mis);
+        } else {
+            mis = tk_mis(s.u, beg);
+            nq = tk_quads(beg, end, mis);
+        }
+        uint32_t carry_l = 0u, carry_e = 0u;
+        for (uint32_t q0 = 0; q0 < nq; q0 += TK_BLOCK) {
+            const uint32_t q = q0 + tid;
+            uint32_t u[E], pos[E], vm = 0u;
+            int64_t i0 = 0;
+            if (q < nq) {
+                if constexpr (E == 8) vm = tk_load_oct<KT>(raw16, beg, end, mis, q, s.xr, u, i0);
+                else vm = tk_load_quad<false>(s.u, beg, end, mis, q, s.xr, false, u, i0);
+            }
+#pragma unroll
+            for (int j = 0; j < E; ++j) pos[j] = (uint32_t)(i0 + j);
+            if constexpr (E == 4) {
+                if (s.p) {
+                    if (vm == 15u) {
+                        const uint4 v = *reinterpret_cast<const uint4 *>(s.p + i0);
+                        pos[0] = v.x; pos[1] = v.y; pos[2] = v.z; pos[3] = v.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if ((vm >> j) & 1u) pos[j] = s.p[i0 + j];
+                    }
+                }
+            }
+            uint32_t lm = 0u, em = 0u;
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if ((vm >> j) & 1u) {
+                    const uint32_t t = u[j] & mask;
+                    lm |= (t < P ? 1u : 0u) << j;
+                    em |= (t == P ? 1u : 0u) << j;
+                }
+            const uint32_t packed = (uint32_t)__popc(lm) | ((uint32_t)__popc(em) << 16);
+            const uint32_t ex = block_excl_scan<TK_BLOCK, TK_BLOCK>(packed, wsum);
+            if (tid == TK_BLOCK - 1u) tot = ex + packed;
+            __syncthreads();
+            uint32_t l = lob + carry_l + (ex & 0xFFFFu), e = eqb + carry_e + (ex >> 16);
+            carry_l += tot & 0xFFFFu;
+            carry_e += tot >> 16;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                if ((lm >> j) & 1u) {
+                    if (l < a.k) {
+                        su[l] = u[j];
+                        sp[l] = pos[j];
+                    }
+                    ++l;
+                }
+                if ((em >> j) & 1u) {
+                    if (FINAL) {
+                        const uint32_t t = ns.sbase + ns.tlow + e;
+                        if (e < ns.krem && t < a.k) {
+                            su[t] = u[j];
+                            sp[t] = pos[j];
+                        }
+                    } else if (e < a.cap) {
+                        cu[e] = u[j];
+                        cp[e] = pos[j];
+                    }
+                    ++e;
+                }
+            }
+            __syncthreads();  // wsum and tot are reused by the next batch
+        }
+    };
+    if (!FINAL || s.p == nullptr) pass(std::integral_constant<int, 8>{});  // (uniform over the workgroup)
+    else pass(std::integral_constant<int, 4>{});
+}
+
 template <bool F32>
 __global__ __launch_bounds__(256) void k_tk_prep(const uint32_t *__restrict__ keys, uint32_t *__restrict__ u,
                                                  uint32_t *__restrict__ pos, size_t n, uint32_t cols, uint32_t xr) {
@@ -369,6 +604,17 @@ __global__ __launch_bounds__(256) void k_tk_prep(const uint32_t *__restrict__ ke
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         if (u) u[i] = tk_word<F32>(keys[i], true) ^ xr;
         pos[i] = (uint32_t)i % cols;  // (n <= 2^31 - 1)
+    }
+}
+
+// 16-bit keys, for the paths that sort whole rows (not the hot path: one key per thread and load)
+template <int KT>
+__global__ __launch_bounds__(256) void k_tk_prep16(const uint16_t *__restrict__ keys, uint32_t *__restrict__ u,
+                                                   uint32_t *__restrict__ pos, size_t n, uint32_t cols, uint32_t xr) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        u[i] = tk_u16<KT>(keys[i], xr);
+        pos[i] = (uint32_t)i % cols;
     }
 }
 
@@ -400,16 +646,32 @@ __global__ __launch_bounds__(256) void k_tk_write(const uint32_t *__restrict__ s
     }
 }
 
+// 16-bit keys (either format: unord16 is the same for both): 2-byte elements out
+__global__ __launch_bounds__(256) void k_tk_write16(const uint32_t *__restrict__ su, const uint32_t *__restrict__ sp,
+                                                    uint16_t *__restrict__ ko, uint32_t *__restrict__ io, uint32_t m,
+                                                    uint32_t k, uint32_t bpr, uint32_t xr) {
+    const uint32_t row = blockIdx.x / bpr, bx = blockIdx.x - row * bpr;
+    const size_t src = (size_t)row * m, dst = (size_t)row * k;
+    for (uint32_t j = bx * 256u + threadIdx.x; j < k; j += bpr * 256u) {
+        ko[dst + j] = (uint16_t)unord16((su[src + j] ^ xr) >> 16);
+        if (io) io[dst + j] = sp[src + j];
+    }
+}
+
 unsigned tk_stream_blocks(size_t n) {
     const size_t b = (n + 256 * 8 - 1) / (256 * 8);
     return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
 }
 
-hipError_t launch_topk_hist(const TkArgs &a, size_t rows, int level, bool f32, hipStream_t s) {
+// kt: TkKey.  The 32-bit kinds run the kernels instantiated on F32, the 16-bit kinds their own.
+hipError_t launch_topk_hist(const TkArgs &a, size_t rows, int level, int kt, hipStream_t s) {
     const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
     const uint32_t nx = (a.nch + g - 1u) / g;
-    if (f32) k_tk_hist<true><<<(unsigned)(rows * nx), TK_BLOCK, 0, s>>>(a, level, nx, g);
-    else k_tk_hist<false><<<(unsigned)(rows * nx), TK_BLOCK, 0, s>>>(a, level, nx, g);
+    const unsigned grid = (unsigned)(rows * nx);
+    if (kt == TK_BF16) k_tk_hist16<TK_BF16><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
+    else if (kt == TK_F16) k_tk_hist16<TK_F16><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
+    else if (kt == TK_F32) k_tk_hist<true><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
+    else k_tk_hist<false><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
     return hipGetLastError();
 }
 
@@ -419,21 +681,30 @@ hipError_t launch_topk_reduce(const TkArgs &a, size_t rows, int level, hipStream
     return hipGetLastError();
 }
 
-hipError_t launch_topk_scan(const TkArgs &a, size_t rows, int level, hipStream_t s) {
-    k_tk_scan<<<(unsigned)rows, TK_BLOCK, 0, s>>>(a, level);
+// the digit levels of a call: two decide a 16-bit key
+constexpr int TK_LEVELS16 = 2;
+int tk_levels(int kt) { return tk_is16(kt) ? TK_LEVELS16 : TK_LEVELS; }
+
+hipError_t launch_topk_scan(const TkArgs &a, size_t rows, int level, int kt, hipStream_t s) {
+    if (tk_is16(kt)) k_tk_scan<TK_LEVELS16><<<(unsigned)rows, TK_BLOCK, 0, s>>>(a, level);
+    else k_tk_scan<TK_LEVELS><<<(unsigned)rows, TK_BLOCK, 0, s>>>(a, level);
     return hipGetLastError();
 }
 
-hipError_t launch_topk_narrow(const TkArgs &a, size_t rows, int level, bool f32, hipStream_t s) {
-    if (f32) k_tk_compact<false, true><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, level);
-    else k_tk_compact<false, false><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, level);
+template <bool FINAL>
+hipError_t launch_topk_compact(const TkArgs &a, size_t rows, int level, int kt, hipStream_t s) {
+    const unsigned grid = (unsigned)(rows * a.nch);
+    if (kt == TK_BF16) k_tk_compact16<FINAL, TK_BF16><<<grid, TK_BLOCK, 0, s>>>(a, level);
+    else if (kt == TK_F16) k_tk_compact16<FINAL, TK_F16><<<grid, TK_BLOCK, 0, s>>>(a, level);
+    else if (kt == TK_F32) k_tk_compact<FINAL, true><<<grid, TK_BLOCK, 0, s>>>(a, level);
+    else k_tk_compact<FINAL, false><<<grid, TK_BLOCK, 0, s>>>(a, level);
     return hipGetLastError();
 }
-
-hipError_t launch_topk_final(const TkArgs &a, size_t rows, bool f32, hipStream_t s) {
-    if (f32) k_tk_compact<true, true><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, TK_LEVELS - 1);
-    else k_tk_compact<true, false><<<(unsigned)(rows * a.nch), TK_BLOCK, 0, s>>>(a, TK_LEVELS - 1);
-    return hipGetLastError();
+hipError_t launch_topk_narrow(const TkArgs &a, size_t rows, int level, int kt, hipStream_t s) {
+    return launch_topk_compact<false>(a, rows, level, kt, s);
+}
+hipError_t launch_topk_final(const TkArgs &a, size_t rows, int kt, hipStream_t s) {
+    return launch_topk_compact<true>(a, rows, tk_levels(kt) - 1, kt, s);
 }
 
 // u[i] = keys[i] ^ xr (f32: f32_ord(keys[i]) ^ xr; u may be nullptr), pos[i] = i % cols
@@ -441,6 +712,13 @@ hipError_t launch_topk_prep(const uint32_t *keys, uint32_t *u, uint32_t *pos, si
                             bool f32, hipStream_t s) {
     if (f32) k_tk_prep<true><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
     else k_tk_prep<false><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
+    return hipGetLastError();
+}
+// the same for 16-bit keys (kt: TK_BF16 / TK_F16): u[i] = (ord16(keys[i]) << 16) ^ xr
+hipError_t launch_topk_prep16(const uint16_t *keys, uint32_t *u, uint32_t *pos, size_t n, size_t cols, uint32_t xr,
+                              int kt, hipStream_t s) {
+    if (kt == TK_BF16) k_tk_prep16<TK_BF16><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
+    else k_tk_prep16<TK_F16><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
     return hipGetLastError();
 }
 
@@ -456,16 +734,19 @@ hipError_t launch_topk_err_acc(uint32_t *hdr, const uint32_t *inner, int nw, hip
     return hipGetLastError();
 }
 
-// keys_out[r][j] = su[r * m + j] ^ xr (f32: f32_unord of it), idx_out[r][j] = sp[r * m + j] for j < k
-// (idx_out may be nullptr)
-hipError_t launch_topk_write(const uint32_t *su, const uint32_t *sp, uint32_t *keys_out, uint32_t *idx_out, size_t rows,
-                             size_t m, size_t k, uint32_t xr, bool f32, hipStream_t s) {
+// keys_out[r][j] = su[r * m + j] ^ xr (f32: f32_unord of it; 16-bit keys: unord16 of its top half, a
+// 2-byte element), idx_out[r][j] = sp[r * m + j] for j < k (idx_out may be nullptr)
+hipError_t launch_topk_write(const uint32_t *su, const uint32_t *sp, void *keys_out, uint32_t *idx_out, size_t rows,
+                             size_t m, size_t k, uint32_t xr, int kt, hipStream_t s) {
     // blocks per row: enough for one key per thread, fewer when there are many rows
     size_t bpr = (k + 255) / 256;
     const size_t room = ((size_t)1 << 20) / rows;
     if (bpr > room) bpr = room ? room : 1;
-    if (f32) k_tk_write<true><<<(unsigned)(rows * bpr), 256, 0, s>>>(su, sp, keys_out, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
-    else k_tk_write<false><<<(unsigned)(rows * bpr), 256, 0, s>>>(su, sp, keys_out, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    const unsigned grid = (unsigned)(rows * bpr);
+    uint32_t *ko = static_cast<uint32_t *>(keys_out);
+    if (tk_is16(kt)) k_tk_write16<<<grid, 256, 0, s>>>(su, sp, static_cast<uint16_t *>(keys_out), idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    else if (kt == TK_F32) k_tk_write<true><<<grid, 256, 0, s>>>(su, sp, ko, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    else k_tk_write<false><<<grid, 256, 0, s>>>(su, sp, ko, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
     return hipGetLastError();
 }
 
@@ -571,24 +852,30 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
                         void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
     if (rows == 0 || k == 0) return LABSORT_OK;
     if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
-    if (!device_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    const bool k16 = key_type_is16(key_type);
+    const size_t esz = k16 ? 2 : 4;  // bytes per key
+    if (k16 && (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u)) return LABSORT_ERR_ARG;
     if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
     if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
-    if (ranges_overlap(d_keys, rows * cols * 4, d_keys_out, rows * k * 4)) return LABSORT_ERR_ARG;
-    if (d_idx_out && ranges_overlap(d_keys, rows * cols * 4, d_idx_out, rows * k * 4)) return LABSORT_ERR_ARG;
+    if (ranges_overlap(d_keys, rows * cols * esz, d_keys_out, rows * k * esz)) return LABSORT_ERR_ARG;
+    if (d_idx_out && ranges_overlap(d_keys, rows * cols * esz, d_idx_out, rows * k * 4)) return LABSORT_ERR_ARG;
     const int path = topk_path(rows, cols, k);
     // the survivors of several long rows are ordered by the segmented sort: past its LDS tile, its general path
     if (path == TK_PATH_SELECT && rows > 1 && k > (size_t)SEG_TILE_PAIRS && rows * k > RADIX_MAX_N) return LABSORT_ERR_ARG;
     if (!d_ws || ws_bytes < labsort_topk_workspace_bytes(rows, cols, k)) return LABSORT_ERR_ARG;
     const TopkLayout L = topk_layout_path(rows, cols, k, path);
-    const uint32_t xr = flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
+    // 16-bit keys: u = (ord16(key) << 16) ^ xr, its low half clear
+    const uint32_t xr = k16 ? (largest ? 0xFFFF0000u : 0u) : flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
     const bool f32 = key_type == LABSORT_KEY_F32;  // u = f32_ord(key) ^ xr
+    const int kt = f32 ? TK_F32 : key_type == LABSORT_KEY_BF16 ? TK_BF16 : key_type == LABSORT_KEY_F16 ? TK_F16 : TK_INT;
     hipStream_t s = as_stream(stream);
     char *ws = static_cast<char *>(d_ws);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t *>(ws + off); };
     const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
+    const uint16_t *keys16 = static_cast<const uint16_t *>(d_keys);  // (what a 16-bit call reads: k_tk_prep16, tk_raw16)
     uint32_t *hdr = W(0), *A = W(L.off_a), *B = W(L.off_b), *SU = W(L.off_su), *SP = W(L.off_sp), *offs = W(L.off_offs);
-    uint32_t *ko = static_cast<uint32_t *>(d_keys_out);
+    void *ko = d_keys_out;
     const size_t n = rows * L.m;
     HIP_TRY(launch_zero(ws, L.zero_bytes, s));  // (a kernel: graph-replayable)
     if (path == TK_PATH_SHORT) {
@@ -596,10 +883,15 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
         TimingScope ts(LABSORT_K_TOPK, s);
         uint32_t *lists = W(L.off_lists);
         HIP_TRY(launch_topk_offsets(offs, rows, cols, s));
-        HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, false, s));
+        // 16-bit keys: the class kernels load 32-bit words, so the keys are first widened to
+        // ord16(key) << 16 into SU and sorted there in place (a class kernel holds its whole segment in
+        // registers before its first store, as the in-place segmented sort relies on)
+        if (k16) HIP_TRY(launch_topk_prep16(keys16, SU, B, n, cols, 0u, kt, s));
+        else HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, false, s));
         HIP_TRY(launch_seg_bin(offs, rows, n, cols, true, true, hdr, lists, L.list_stride, s));
-        HIP_TRY(launch_seg_lds_classes(cols, true, keys, SU, B, SP, offs, hdr, lists, L.list_stride, xr, f32, s));
-        HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, cols, k, 0u, false, s));  // (the class kernels wrote keys, not u)
+        HIP_TRY(launch_seg_lds_classes(cols, true, k16 ? SU : keys, SU, B, SP, offs, hdr, lists, L.list_stride, xr, f32, s));
+        // (the class kernels wrote keys, not u: nothing to undo but, for 16-bit keys, ord16)
+        HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, cols, k, 0u, k16 ? kt : TK_INT, s));
         return LABSORT_OK;
     }
     if (path == TK_PATH_SELECT) {
@@ -623,16 +915,18 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
         a.capa = (uint32_t)L.capa;
         a.cap = (uint32_t)L.cap;
         a.xr = xr;
-        for (int level = 0; level < TK_LEVELS; ++level) {
-            HIP_TRY(launch_topk_hist(a, rows, level, f32, s));
+        const int nlev = tk_levels(kt);
+        for (int level = 0; level < nlev; ++level) {
+            HIP_TRY(launch_topk_hist(a, rows, level, kt, s));
             HIP_TRY(launch_topk_reduce(a, rows, level, s));
-            HIP_TRY(launch_topk_scan(a, rows, level, s));
-            if (level < TK_LEVELS - 1 && L.cap > 0) HIP_TRY(launch_topk_narrow(a, rows, level, f32, s));
+            HIP_TRY(launch_topk_scan(a, rows, level, kt, s));
+            if (level < nlev - 1 && L.cap > 0) HIP_TRY(launch_topk_narrow(a, rows, level, kt, s));
         }
-        HIP_TRY(launch_topk_final(a, rows, f32, s));
+        HIP_TRY(launch_topk_final(a, rows, kt, s));
     } else {
         TimingScope ts(LABSORT_K_TOPK, s);
-        HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, f32, s));
+        if (k16) HIP_TRY(launch_topk_prep16(keys16, A, B, n, cols, xr, kt, s));
+        else HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, f32, s));
     }
     // order the m pairs of every row on u (stable): one pair sort, or the segmented pair sort
     char *iws = ws + L.off_inner;
@@ -653,7 +947,7 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
     }
     TimingScope ts(LABSORT_K_TOPK, s);
     HIP_TRY(launch_topk_err_acc(hdr, ierr, 2, s));
-    HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, L.m, k, xr, f32, s));
+    HIP_TRY(launch_topk_write(SU, SP, ko, d_idx_out, rows, L.m, k, xr, kt, s));
     return LABSORT_OK;
 }
 

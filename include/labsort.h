@@ -75,14 +75,14 @@ extern "C" {
  * input write the original word (the segmented sorts' general path in its pairs form), where
  *   unord(o) = (o & 0x80000000) ? (o & 0x7FFFFFFF) : ~o.
  * Accepted by labsort_sort_device, labsort_sort_pairs_device, labsort_sort_segments_device,
- * labsort_sort_segments_pairs_device and labsort_topk_device only; every other entry that
+ * labsort_sort_segments_pairs_device, labsort_topk_device and labsort_sort_rows_device only; every other entry that
  * checks its key type returns LABSORT_ERR_ARG for it (host-pointer, multi-GPU and distributed
  * sorts, labsort_merge_runs, labsort_upper_bound, the C++ drop-ins).  The building blocks
  * that take a key type without checking it order U32 / I32 words only. */
 #define LABSORT_KEY_F32 2
-/* bfloat16 and IEEE-754 binary16: 16-bit elements, accepted by labsort_topk_device ONLY (every
- * other entry that checks its key type returns LABSORT_ERR_ARG for them, the segmented and
- * whole-array device sorts included).  The float32 contract at 16 bits: with T = 0x7F80 (bfloat16)
+/* bfloat16 and IEEE-754 binary16: 16-bit elements, accepted by labsort_topk_device and
+ * labsort_sort_rows_device ONLY (every other entry that checks its key type returns
+ * LABSORT_ERR_ARG for them, the segmented and whole-array device sorts included).  The float32 contract at 16 bits: with T = 0x7F80 (bfloat16)
  * or 0x7C00 (binary16), an element x is ordered by
  *   ord16(x) = 0xFFFF         if (x & 0x7FFF) > T   (every NaN, either sign)
  *            = ~x & 0xFFFF    if x & 0x8000
@@ -389,6 +389,45 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
                         void *d_keys_out, uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes,
                         void *stream);
 int labsort_topk_workspace_status(const void *d_workspace, void *stream);
+
+/* ---- dense row sort: every row of a matrix sorted, stably, with positions
+ * (torch.sort(x, dim=-1, descending=..., stable=True); no lab.cu counterpart) ----
+ * labsort_topk_device's contract with k = cols and `descending` in place of `largest`: d_keys is a
+ * dense rows x cols matrix, never written; d_keys_out is rows x cols; d_idx_out is rows x cols
+ * 32-bit positions within the row, or NULL (the keys written are the same either way).  With u
+ * as defined at labsort_topk_device, row r of the output is the stable ascending sort of the
+ * row's (u(key), position) pairs, keys written back untransformed: equal keys stay in order of
+ * position in both directions, NaNs are the largest keys and come back as 0x7FFFFFFF / 0x7FFF,
+ * -0.0 is below +0.0.  key_type: all five (U32, I32, F32, BF16, F16); for the 16-bit types d_keys
+ * and d_keys_out hold 2-byte elements and need 2-byte alignment only.  This is the one sorting
+ * entry that takes the 16-bit types.
+ * rows * cols <= 2^31 - 1; rows == 0 or cols == 0 launches nothing (LABSORT_OK before anything
+ * else is looked at).  LABSORT_ERR_ARG before any launch: NULL d_keys / d_keys_out, a bad key
+ * type, rows > (2^31 - 1) / cols, an odd d_keys / d_keys_out address with a 16-bit type,
+ * d_idx_out == d_keys_out, an output that overlaps the input (by the real element sizes), a
+ * missing or short workspace.
+ * Rows that fit an LDS tile -- cols <= labsort_segment_tile_keys() for the 16-bit types and for
+ * 32-bit keys without positions, cols <= labsort_segment_pair_tile_keys() for 32-bit keys with
+ * positions -- are sorted by one kernel launch (after the header's clearing): the length class
+ * of the segmented sort (labsort_segment_class_edges) is chosen on the host from cols, a row is
+ * read once, sorted in LDS and written once, and a key's position is the slot it was loaded into,
+ * never read from memory.  A 16-bit key travels as one word, (u(key) << 16) | position, through the
+ * keys-only kernels, which sort it on its top two digits only.  Every other shape calls
+ * labsort_topk_device with k = cols on the same workspace: the result is the same by contract, the
+ * limits and error returns are that call's.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on the
+ * host arguments only, so a captured call may be replayed on new keys in the same buffers.
+ * labsort_sort_rows_workspace_bytes takes no key type: 256 bytes (the header) for
+ * cols <= labsort_segment_pair_tile_keys(), labsort_topk_workspace_bytes(rows, cols, cols) above.
+ * labsort_sort_rows_workspace_status synchronises `stream` and returns what
+ * labsort_topk_workspace_status returns: LABSORT_OK after an LDS-path call (the header is cleared
+ * and nothing sets it), top-k's report after a long-path call.
+ * Timing hooks: the LDS path's kernels count under LABSORT_K_SEGSORT. */
+size_t labsort_sort_rows_workspace_bytes(size_t rows, size_t cols);
+int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int descending, int key_type,
+                             void *d_keys_out, uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes,
+                             void *stream);
+int labsort_sort_rows_workspace_status(const void *d_workspace, void *stream);
 
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +

@@ -30,7 +30,7 @@ OK, ERR_ARG, ERR_HIP, ERR_DEVICE, ERR_PEER = 0, 1, 2, 3, 4
 ALGO = {"radix": 0, "merge": 1, "radix1": 2, "auto": 3}
 # "f32": IEEE-754 order with -0.0 < +0.0 and every NaN equal and last; the device sorts, the segmented
 # sorts and top-k take it, the host-pointer and multi-GPU entries do not (labsort.h)
-# "bf16", "f16": 16-bit elements, the same order at 16 bits; top-k alone takes them
+# "bf16", "f16": 16-bit elements, the same order at 16 bits; top-k and the row sort alone take them
 KEY = {"u32": 0, "i32": 1, "f32": 2, "bf16": 3, "f16": 4}
 DIST = {"u32": 0, "u31": 1, "mod100": 2, "mod1000": 3, "sorted": 4, "reversed": 5, "const": 6, "lowbits": 7}
 KCLASS = {"histogram": 0, "onesweep": 1, "tile_sort": 2, "merge": 3, "partition": 4, "gsweep": 5, "gcopy": 6,
@@ -58,6 +58,7 @@ C_SYMBOLS = [
     "labsort_segments_workspace_bytes", "labsort_sort_segments_device", "labsort_sort_segments_pairs_device",
     "labsort_segments_workspace_status",
     "labsort_topk_workspace_bytes", "labsort_topk_device", "labsort_topk_workspace_status",
+    "labsort_sort_rows_workspace_bytes", "labsort_sort_rows_device", "labsort_sort_rows_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
 ]
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
@@ -192,6 +193,11 @@ def _load() -> ctypes.CDLL:
     L.labsort_topk_workspace_bytes.argtypes = [sz, sz, sz]
     L.labsort_topk_device.argtypes = [p, sz, sz, sz, i, i, p, p, p, sz, p]
     L.labsort_topk_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_sort_rows_device"):  # (as labsort_radix_path above)
+        L.labsort_sort_rows_workspace_bytes.restype = sz
+        L.labsort_sort_rows_workspace_bytes.argtypes = [sz, sz]
+        L.labsort_sort_rows_device.argtypes = [p, sz, sz, i, i, p, p, p, sz, p]
+        L.labsort_sort_rows_workspace_status.argtypes = [p, p]
     if hasattr(L, "labsort_key_order_bits"):  # (as labsort_radix_path above)
         for f in ("labsort_key_order_bits", "labsort_key_from_order_bits"):
             getattr(L, f).restype = ctypes.c_uint32
@@ -703,6 +709,61 @@ def topk_workspace_status(workspace, stream=None) -> None:
     """Synchronise `stream`; raise LabsortError with ERR_DEVICE if an inner sort of the last
     topk_device call on `workspace` reported a failure."""
     _check(lib.labsort_topk_workspace_status(_ptr(workspace), _stream(stream)), "topk (status)")
+
+
+def sort_rows_workspace_bytes(rows: int, cols: int) -> int:
+    return int(lib.labsort_sort_rows_workspace_bytes(rows, cols))
+
+
+def sort_rows_device(d_keys, rows: int, cols: int, d_keys_out, d_idx_out=None, descending: bool = False,
+                     key: str = "u32", workspace=None, stream=None) -> None:
+    """Every row of the dense rows x cols matrix d_keys sorted into d_keys_out (rows x cols), stably,
+    ascending or descending, and the keys' positions within their row into d_idx_out (rows x cols
+    int32 / uint32 words, or None): torch.sort(x, dim=-1, descending=..., stable=True), topk_device's
+    contract with k = cols.  key: "u32", "i32", "f32", "bf16" or "f16" (16-bit elements in d_keys and
+    d_keys_out, d_idx_out stays 32-bit); NaNs are the largest keys and equal to each other, -0.0 is
+    below +0.0.  Workspace and status as topk_device: with a caller-owned `workspace` the call stays
+    asynchronous (check sort_rows_workspace_status when the result is needed); without one it
+    allocates, synchronises and checks."""
+    workspace, wsb, own = _workspace(workspace, lambda: sort_rows_workspace_bytes(rows, cols))
+    _check(lib.labsort_sort_rows_device(_ptr(d_keys), rows, cols, 1 if descending else 0, KEY[key], _ptr(d_keys_out),
+                                        None if d_idx_out is None else _ptr(d_idx_out), _ptr(workspace), wsb,
+                                        _stream(stream)), "sort_rows_device")
+    if own:
+        sort_rows_workspace_status(workspace, stream)
+
+
+def sort_rows_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_DEVICE if an inner sort of the last
+    sort_rows_device call on `workspace` reported a failure (rows past the LDS tile only)."""
+    _check(lib.labsort_sort_rows_workspace_status(_ptr(workspace), _stream(stream)), "sort_rows (status)")
+
+
+def sort(x, descending: bool = False, workspace=None, stream=None):
+    """(values, indices) of every row of x sorted, stably: sort_rows_device with its outputs allocated.
+    x: a contiguous 1-D (one row) or 2-D CUDA tensor of dtype int32, float32, bfloat16 or float16;
+    values has x's dtype and shape, indices is int32 of the same shape.  TypeError for another dtype,
+    a non-contiguous or a CPU tensor, before the device is touched.  Workspace and status as
+    sort_rows_device."""
+    import torch
+    keys = {torch.int32: "i32", torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+    if not isinstance(x, torch.Tensor) or x.dtype not in keys:
+        raise TypeError(f"sort: int32, float32, bfloat16 or float16 tensor expected, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() not in (1, 2) or not x.is_contiguous():
+        raise TypeError("sort: a contiguous 1-D or 2-D tensor expected")
+    if not x.is_cuda:
+        raise TypeError("sort: a CUDA tensor expected")
+    rows, cols = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    values = torch.empty_like(x)
+    indices = torch.empty(x.shape, dtype=torch.int32, device=x.device)
+    sort_rows_device(x, rows, cols, values, indices, descending=descending, key=keys[x.dtype], workspace=workspace,
+                     stream=stream)
+    return values, indices
+
+
+def argsort(x, descending: bool = False, workspace=None, stream=None):
+    """The indices of sort(x, descending): the stable argsort of every row."""
+    return sort(x, descending=descending, workspace=workspace, stream=stream)[1]
 
 
 def key_order_bits(word: int, key: str = "u32") -> int:

@@ -1,0 +1,391 @@
+// rowsort.hip -- dense row sort with positions (labsort_sort_rows_device): every row of a
+// rows x cols matrix sorted stably, ascending or descending, keys of 32 or 16 bits, with or
+// without the positions within the row (torch.sort(x, dim=-1)).  Top-k's contract with k = cols.
+//
+// Every row has the same length, so the segmented sort's length class is a host decision and the
+// row index gives the base: no offsets, no class lists, no binning.  A row that fits the LDS tile
+// is read once, sorted by the 8-bit LSD passes of lds_pass.h and written once; a key's position is
+// the slot it was loaded into, never read from memory:
+//   32-bit keys with positions   the key/value shapes, v[j] = slot, carried through LDS as a payload
+//   32-bit keys alone            the keys-only shapes
+//   16-bit keys                  one packed word per key in the keys-only shapes,
+//                                w = ((ord16(key) ^ x16) << 16) | slot with x16 = descending ? 0xFFFF : 0,
+//                                sorted with flip = 0 on digits 2 and 3 only: the passes are stable LSD
+//                                and the slots start in position order, so the low half needs no pass.
+//                                Padding is 0xFFFFFFFF: it starts behind every key and ties at most with
+//                                NaN images (ascending) on both digits, so it stays behind them.
+// Longer rows (and 32-bit keys with positions past the pair tile) go to labsort_topk_device with
+// k = cols on the caller's workspace.
+#include <cstdlib>
+#include <cstring>
+
+#include "devutil.h"
+#include "host.h"
+#include "lds_pass.h"
+#include "segsort.h"
+#include "topk.h"
+
+namespace labsort {
+
+namespace {
+
+// What a key is: a 32-bit word ordered by (word ^ flip), a float32 word ordered by
+// (f32_ord(word) ^ flip), or a 16-bit float packed with its position (above).
+enum RsMode : int { RS_K32, RS_F32, RS_P16 };
+
+// The sorted word of the element at index i (position pos within its row).
+template <int MODE>
+__device__ __forceinline__ uint32_t rs_load(const void *in, size_t i, uint32_t pos, uint32_t x16, uint32_t nan_t) {
+    if constexpr (MODE == RS_P16) return ((ord16(static_cast<const uint16_t *>(in)[i], nan_t) ^ x16) << 16) | pos;
+    else if constexpr (MODE == RS_F32) return f32_ord(static_cast<const uint32_t *>(in)[i]);
+    else return static_cast<const uint32_t *>(in)[i];
+}
+// Element i of the outputs from the sorted word k (and its payload v): the key untransformed,
+// the position as a 32-bit word (iout == nullptr for a 16-bit call: keys only).
+template <int MODE, bool KV>
+__device__ __forceinline__ void rs_store(void *out, uint32_t *iout, size_t i, uint32_t k, uint32_t v, uint32_t x16) {
+    if constexpr (MODE == RS_P16) {
+        static_cast<uint16_t *>(out)[i] = (uint16_t)unord16((k >> 16) ^ x16);
+        if (iout) iout[i] = k & 0xFFFFu;  // (uniform over the launch)
+    } else {
+        static_cast<uint32_t *>(out)[i] = MODE == RS_F32 ? f32_unord(k) : k;
+        if constexpr (KV) iout[i] = v;
+    }
+}
+// The digits that can differ: a packed word's position half never starts a pass.
+template <int MODE>
+__device__ __forceinline__ uint32_t rs_diff(uint32_t diff) {
+    return MODE == RS_P16 ? diff & 0xFFFF0000u : diff;
+}
+
+// ---------------------------------------------------------------------------------
+// wave classes: one wave64 per row, no workgroup barrier (k_seg_wave on row = unit)
+// ---------------------------------------------------------------------------------
+template <int KPT, bool KV>
+struct RsWaveSmem {
+    uint32_t keys[WAVE * KPT];
+    uint32_t vals[KV ? WAVE * KPT : 1];
+    uint32_t hist[256];
+    uint32_t probe[WAVE];
+};
+
+// fx: the flip of a 32-bit call, x16 of a 16-bit one (which sorts with flip = 0)
+template <int KPT, bool KV, int MODE>
+__global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_rs_wave(const void *in, void *out, uint32_t *iout, uint32_t rows,
+                                                                 uint32_t len, uint32_t fx, uint32_t nan_t) {
+    static_assert(!(MODE == RS_P16 && KV), "a packed word carries its position");
+    constexpr uint32_t CAP = WAVE * KPT;
+    __shared__ RsWaveSmem<KPT, KV> sm_all[SEG_WAVE_WPB];
+    const uint32_t lane = threadIdx.x & 63u, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t first = blockIdx.x * SEG_WAVE_WPB + wid;
+    if (first >= rows || len == 0u || len > CAP) return;  // (wave-uniform; the host picks the class by len)
+    RsWaveSmem<KPT, KV> &sm = sm_all[wid];
+    const uint32_t flip = MODE == RS_P16 ? 0u : fx, x16 = MODE == RS_P16 ? fx : 0u;
+    const uint32_t sentinel = ~flip;
+    const bool atomic_rank = lds_lane_ordered(sm.probe, lane);
+    const uint32_t jn = (len + WAVE - 1u) / WAVE;  // 64-key groups that hold keys (<= KPT)
+    for (uint32_t row = first; row < rows; row += gridDim.x * SEG_WAVE_WPB) {
+        const size_t b = (size_t)row * len;
+        if (len <= (uint32_t)WAVE) {
+            // one key per lane: its stable rank is the count of keys before it in (key, lane) order
+            const bool ok = lane < len;
+            const uint32_t x = ok ? (rs_load<MODE>(in, b + (ok ? lane : 0u), lane, x16, nan_t) ^ flip) : 0xFFFFFFFFu;
+            uint32_t r = 0u;
+            for (uint32_t i = 0; i < len; ++i) {
+                const uint32_t xi = __builtin_amdgcn_readlane(x, (int)i);
+                r += (xi < x || (xi == x && i < lane)) ? 1u : 0u;
+            }
+            if (ok) rs_store<MODE, KV>(out, iout, b + r, x ^ flip, lane, x16);  // r < len
+            continue;
+        }
+        uint32_t k[KPT];
+        uint32_t v[KV ? KPT : 1];
+        uint32_t a = ~0u, o = 0u;
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const uint32_t idx = (uint32_t)j * WAVE + lane;
+            const bool ok = idx < len;
+            k[j] = sentinel;
+            if (ok) k[j] = rs_load<MODE>(in, b + idx, idx, x16, nan_t);
+            if constexpr (KV) v[j] = idx;
+            const uint32_t x = k[j] ^ flip;
+            a &= ok ? x : ~0u;
+            o |= ok ? x : 0u;
+        }
+        wave_and_or(a, o);
+        const uint32_t diff = rs_diff<MODE>(__builtin_amdgcn_readfirstlane(a ^ o));
+        for (int pass = 0; pass < 4; ++pass) {
+            const uint32_t shift = pass * 8;
+            if (((diff >> shift) & 0xFFu) == 0u) continue;  // uniform over the row
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sm.hist[q * WAVE + lane] = 0u;
+            __builtin_amdgcn_wave_barrier();
+            uint32_t rank[KPT];
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                rank[j] = 0u;
+                if ((uint32_t)j < jn)  // wave-uniform; a group past the end holds padding only
+                    rank[j] = rank8(sm.hist, ((k[j] ^ flip) >> shift) & 0xFFu, lane, atomic_rank);
+            }
+            __builtin_amdgcn_wave_barrier();
+            {  // exclusive scan of the 256 counters: four per lane, then across the wave
+                uint32_t c[4], s = 0u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    c[q] = sm.hist[4u * lane + q];
+                    s += c[q];
+                }
+                uint32_t xs = s;
+#pragma unroll
+                for (int offx = 1; offx < 64; offx <<= 1) {
+                    const uint32_t t = __shfl_up(xs, offx);
+                    if (lane >= (uint32_t)offx) xs += t;
+                }
+                uint32_t run = xs - s;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    sm.hist[4u * lane + q] = run;
+                    run += c[q];
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < jn) rank[j] += sm.hist[((k[j] ^ flip) >> shift) & 0xFFu];  // < 64 jn <= CAP
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < jn) {
+                    sm.keys[rank[j]] = k[j];
+                    if constexpr (KV) sm.vals[rank[j]] = v[j];
+                }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int j = 0; j < KPT; ++j)
+                if ((uint32_t)j < jn) {
+                    k[j] = sm.keys[(uint32_t)j * WAVE + lane];
+                    if constexpr (KV) v[j] = sm.vals[(uint32_t)j * WAVE + lane];
+                }
+            __builtin_amdgcn_wave_barrier();
+        }
+        // padding sorts behind every key (stable, largest digits), so slots < len hold the keys
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const uint32_t idx = (uint32_t)j * WAVE + lane;
+            uint32_t vj = 0u;
+            if constexpr (KV) vj = v[j];
+            if (idx < len) rs_store<MODE, KV>(out, iout, b + idx, k[j], vj, x16);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// block and tile classes: one row per workgroup, striped over the waves in runs of
+// S = 64 ceil(len / (64 W)) slots (k_seg_block on row = unit).
+// ---------------------------------------------------------------------------------
+template <int BLOCK, int KPT, bool KV, int WPE, int MODE>
+__global__ __launch_bounds__(BLOCK, WPE) void k_rs_block(const void *in, void *out, uint32_t *iout, uint32_t rows, uint32_t len,
+                                                          uint32_t fx, uint32_t nan_t) {
+    static_assert(!(MODE == RS_P16 && KV), "a packed word carries its position");
+    using S = TsSmem<BLOCK, KPT, KV>;
+    constexpr int W = S::W;
+    constexpr uint32_t TILE = S::TILE;
+    static_assert(MODE != RS_P16 || TILE <= 65536u, "a position fits the packed word's low half");
+    __shared__ S sm;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (blockIdx.x >= rows || len == 0u || len > TILE) return;  // (uniform; the host picks the class by len)
+    const uint32_t flip = MODE == RS_P16 ? 0u : fx, x16 = MODE == RS_P16 ? fx : 0u;
+    const uint32_t sentinel = ~flip;
+    probe_lane_order(sm.probe, &sm.ordered, lane, wid);
+    __syncthreads();
+    const bool atomic_rank = lane_order_probed(&sm.ordered);
+    for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        // (the row's shape is formed again for every row, from a copy of len the compiler cannot
+        // see through: hoisted out of the loop these values were held in SGPRs across it and spilled)
+        uint32_t rl = len;
+        asm volatile("" : "+s"(rl));
+        const uint32_t jn = (rl + (uint32_t)(W * WAVE) - 1u) / (uint32_t)(W * WAVE);  // groups per wave, <= KPT
+        const uint32_t ws0 = wid * jn * WAVE;  // first slot of this wave's stripe
+        // this wave's keys: nf whole 64-key groups and a last group of `tail` keys (wave-uniform)
+        const uint32_t rem = ws0 < rl ? rl - ws0 : 0u;
+        const uint32_t nf = min(jn, rem / WAVE);
+        const uint32_t tail = nf < jn ? rem - nf * WAVE : 0u;  // < 64
+        const uint32_t ng = nf + (tail ? 1u : 0u);             // groups that hold keys
+        const bool tail_ok = lane < tail;
+        // scalar base + 32-bit lane offset per access (the lane offsets pass through empty asms, as in k_seg_block)
+        const size_t sb = (size_t)row * len + ws0;
+        uint32_t lin = lane;
+        asm volatile("" : "+v"(lin));
+        uint32_t k[KPT];
+        uint32_t v[KV ? KPT : 1];
+        uint32_t a = ~0u, o = 0u;
+        // every load first, so all of them are in flight together, then the bits the keys differ in
+        if (nf == (uint32_t)KPT) {  // a whole tile: straight-line loads
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                const uint32_t sl = (uint32_t)(j * WAVE) + lin;
+                k[j] = rs_load<MODE>(in, sb + sl, ws0 + sl, x16, nan_t);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                k[j] = sentinel;
+                if ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) {
+                    const uint32_t sl = (uint32_t)(j * WAVE) + lin;
+                    k[j] = rs_load<MODE>(in, sb + sl, ws0 + sl, x16, nan_t);
+                }
+            }
+        }
+        if constexpr (KV) {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) v[j] = ws0 + (uint32_t)(j * WAVE) + lane;  // the position is the slot
+        }
+#pragma unroll
+        for (int j = 0; j < KPT; ++j) {
+            const uint32_t x = k[j] ^ flip;  // padding: all ones
+            a &= x;
+            o |= ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) ? x : 0u;
+        }
+        const uint32_t diff =
+            rs_diff<MODE>(__builtin_amdgcn_readfirstlane(block_diff_bits<W>(a, o, sm.red_and, sm.red_or, lane, wid)));
+        lds_sort_passes(sm, k, v, diff, flip, ws0, atomic_rank, LeadingGroups{ng}, lane, wid);
+        uint32_t nfs = nf, lout = lane;
+        asm volatile("" : "+s"(nfs), "+v"(lout));
+        if (nfs == (uint32_t)KPT) {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                uint32_t vj = 0u;
+                if constexpr (KV) vj = v[j];
+                rs_store<MODE, KV>(out, iout, sb + ((uint32_t)(j * WAVE) + lout), k[j], vj, x16);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KPT; ++j) {
+                uint32_t vj = 0u;
+                if constexpr (KV) vj = v[j];
+                if ((uint32_t)j < nfs || ((uint32_t)j == nfs && tail_ok))
+                    rs_store<MODE, KV>(out, iout, sb + ((uint32_t)(j * WAVE) + lout), k[j], vj, x16);
+            }
+        }
+        __syncthreads();  // the next row reuses red_and / red_or and the key slots
+    }
+}
+
+int rs_cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+    }
+    return cus;
+}
+
+// The class of a row length: 0-2 wave, 3 block, 4 tile; the edges of SegEdges (segsort.h).
+int rs_class(size_t cols) {
+    return cols <= (size_t)SEG_WAVE_KEYS ? 0 : cols <= (size_t)SEG_WAVE2_KEYS ? 1 : cols <= (size_t)SEG_WAVE3_KEYS ? 2
+         : cols <= (size_t)SEG_BLOCK_KEYS ? 3 : 4;
+}
+
+// One launch: the kernel of class c over all rows.  Two grid forms: the segmented sort's fixed
+// multiples of the CU count (what stays resident per CU) with a row loop, never more units than
+// rows; or one wave / workgroup per row.  By measurement at 2^28 keys with positions (DESIGN.md
+// §3.12, profiles/rowsort.txt; time of a unit per row over time of the fixed grid): the 512-key
+// wave class (0.79-0.98) and the block class (0.89-0.94) take a unit per row, the 256-key wave
+// class (1.01-1.09) and the tile class (1.01-1.04) the fixed grid; the 1024-key wave class showed
+// no consistent winner (0.94-1.03) and keeps the fixed grid.  LABSORT_ROWSORT_GRID=rows / fixed
+// forces one form for every class (harness/rowsort_bench.py's A/B, tests).
+enum RsGrid : int { RS_GRID_AUTO, RS_GRID_ROWS, RS_GRID_FIXED };
+template <int MODE, bool KV>
+hipError_t launch_rs(int c, const void *in, void *out, uint32_t *iout, size_t rows, size_t cols, uint32_t fx,
+                     uint32_t nan_t, int form, hipStream_t s) {
+    const bool per_row = form == RS_GRID_ROWS || (form == RS_GRID_AUTO && (c == 1 || c == 3));
+    const size_t cus = (size_t)rs_cu_count();
+    const uint32_t r = (uint32_t)rows, n = (uint32_t)cols;
+    const size_t wgs = c < 3 ? (rows + SEG_WAVE_WPB - 1) / SEG_WAVE_WPB : rows;  // workgroups that have a row
+    auto grid = [&](size_t fixed) { return (unsigned)((per_row || wgs < fixed) ? wgs : fixed); };
+    constexpr int WB = SEG_WAVE_WPB * WAVE;
+    if (c == 0) k_rs_wave<SEG_WAVE_KPT, KV, MODE><<<grid(cus * 8), WB, 0, s>>>(in, out, iout, r, n, fx, nan_t);
+    else if (c == 1) k_rs_wave<SEG_WAVE2_KPT, KV, MODE><<<grid(cus * (KV ? 6 : 8)), WB, 0, s>>>(in, out, iout, r, n, fx, nan_t);
+    else if (c == 2) k_rs_wave<SEG_WAVE3_KPT, KV, MODE><<<grid(cus * 4), WB, 0, s>>>(in, out, iout, r, n, fx, nan_t);
+    else if (c == 3)
+        k_rs_block<SEG_BLOCK, SEG_BLOCK_KPT, KV, SEG_BLOCK_WPE, MODE>
+            <<<grid(cus * (KV ? 4 : (size_t)SEG_BLOCK_WGS)), SEG_BLOCK, 0, s>>>(in, out, iout, r, n, fx, nan_t);
+    else if (c == 4)
+        k_rs_block<TS_BLOCK, KV ? TS_KPT_KV : TS_KPT, KV, 4, MODE><<<grid(cus), TS_BLOCK, 0, s>>>(in, out, iout, r, n, fx, nan_t);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+bool rs_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+// Which rows the LDS kernels take: the keys-only tile for packed 16-bit keys and for 32-bit keys
+// without positions, the pair tile for 32-bit keys with positions.
+bool rs_lds_path(size_t cols, bool k16, bool idx) {
+    return cols <= ((k16 || !idx) ? (size_t)SEG_TILE_KEYS : (size_t)SEG_TILE_PAIRS);
+}
+
+}  // namespace
+
+}  // namespace labsort
+
+using namespace labsort;
+
+extern "C" {
+
+size_t labsort_sort_rows_workspace_bytes(size_t rows, size_t cols) {
+    if (rows == 0 || cols <= (size_t)SEG_TILE_PAIRS) return SEG_HDR_BYTES;
+    return labsort_topk_workspace_bytes(rows, cols, cols);
+}
+
+int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int descending, int key_type, void *d_keys_out,
+                             uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
+    static_assert(TK_HDR_BYTES == SEG_HDR_BYTES, "one header, one status word, on both paths");
+    if (rows == 0 || cols == 0) return LABSORT_OK;
+    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
+    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    const bool k16 = key_type_is16(key_type);
+    const size_t esz = k16 ? 2 : 4;  // bytes per key
+    if (k16 && (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u)) return LABSORT_ERR_ARG;
+    if (rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
+    const size_t n = rows * cols;
+    if (rs_overlap(d_keys, n * esz, d_keys_out, n * esz)) return LABSORT_ERR_ARG;
+    if (d_idx_out && rs_overlap(d_keys, n * esz, d_idx_out, n * 4)) return LABSORT_ERR_ARG;
+    if (!d_ws || ws_bytes < labsort_sort_rows_workspace_bytes(rows, cols)) return LABSORT_ERR_ARG;
+    if (!rs_lds_path(cols, k16, d_idx_out != nullptr))
+        return labsort_topk_device(d_keys, rows, cols, cols, descending, key_type, d_keys_out, d_idx_out, d_ws, ws_bytes,
+                                   stream);
+    hipStream_t s = as_stream(stream);
+    HIP_TRY(launch_zero(d_ws, SEG_HDR_BYTES, s));  // (a kernel: graph-replayable; nothing sets the header after it)
+    TimingScope ts(LABSORT_K_SEGSORT, s);
+    const int c = rs_class(cols);
+    int form = RS_GRID_AUTO;  // the grid form: per class, unless forced
+    if (const char *e = std::getenv("LABSORT_ROWSORT_GRID"))
+        form = !std::strcmp(e, "rows") ? RS_GRID_ROWS : !std::strcmp(e, "fixed") ? RS_GRID_FIXED : RS_GRID_AUTO;
+    if (k16) {
+        HIP_TRY((launch_rs<RS_P16, false>(c, d_keys, d_keys_out, d_idx_out, rows, cols, descending ? 0xFFFFu : 0u,
+                                          nan_t16(key_type), form, s)));
+        return LABSORT_OK;
+    }
+    const uint32_t flip = flip_of(key_type) ^ (descending ? 0xFFFFFFFFu : 0u);
+    const bool f32 = key_type == LABSORT_KEY_F32;
+    if (d_idx_out) {
+        if (f32) HIP_TRY((launch_rs<RS_F32, true>(c, d_keys, d_keys_out, d_idx_out, rows, cols, flip, 0u, form, s)));
+        else HIP_TRY((launch_rs<RS_K32, true>(c, d_keys, d_keys_out, d_idx_out, rows, cols, flip, 0u, form, s)));
+    } else {
+        if (f32) HIP_TRY((launch_rs<RS_F32, false>(c, d_keys, d_keys_out, nullptr, rows, cols, flip, 0u, form, s)));
+        else HIP_TRY((launch_rs<RS_K32, false>(c, d_keys, d_keys_out, nullptr, rows, cols, flip, 0u, form, s)));
+    }
+    return LABSORT_OK;
+}
+
+int labsort_sort_rows_workspace_status(const void *d_ws, void *stream) {
+    // word 0 of the header: cleared and never set on the LDS path, top-k's error word on the long one
+    return labsort_topk_workspace_status(d_ws, stream);
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 //                LSD passes (4, 8 or 16 keys per lane)
 //   k_seg_block  block and tile classes: k_tile_sort's LDS passes on a [start, end) range,
 //                one workgroup per segment, grid-stride over the class list
+//   k_fin_block  (fin_block.h) the block class of the hybrid radix sort's finish
 //   k_seg_ids, k_seg_gather, k_seg_err_acc   the general path's glue around the pair sorts
 // k_seg_wave and k_seg_block live in seg_kernels.h: this file compiles their integer-key
 // instantiations, segsort_f32.hip the float32 ones.
@@ -20,6 +21,7 @@
 #include <algorithm>
 
 #include "devutil.h"
+#include "fin_block.h"
 #include "host.h"
 #include "seg_kernels.h"
 
@@ -271,8 +273,7 @@ hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t fli
     for (int c = 0; c < SEG_CLASSES; ++c) {
         const uint32_t *list = lists + (size_t)c * stride;
         if (c == 3) {  // the finish's own block class
-            k_seg_block<HY_BLOCK, HY_BLOCK_KPT, false, HY_BLOCK_WPE><<<cus * (unsigned)HY_BLOCK_WPE, HY_BLOCK, 0, s>>>(
-                out, out, nullptr, nullptr, off, hdr, list, 3, flip, hy);
+            k_fin_block<HY_BLOCK, HY_BLOCK_KPT, HY_BLOCK_WPE><<<cus * (unsigned)HY_BLOCK_WPE, HY_BLOCK, 0, s>>>(out, off, hdr, list, hy);
             e = hipGetLastError();
         } else {
             e = launch_seg_sort(c, out, out, nullptr, nullptr, off, hdr, list, flip, s, hy);

@@ -684,6 +684,20 @@ def topk_device(d_keys, rows: int, cols: int, k: int, d_keys_out, d_idx_out=None
         topk_workspace_status(workspace, stream)
 
 
+def _dense_rows(what: str, x):
+    """(rows, cols, key) of the tensor topk() and sort() take, or their TypeError."""
+    import torch
+    keys = {torch.int32: "i32", torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+    if not isinstance(x, torch.Tensor) or x.dtype not in keys:
+        raise TypeError(f"{what}: int32, float32, bfloat16 or float16 tensor expected, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() not in (1, 2) or not x.is_contiguous():
+        raise TypeError(f"{what}: a contiguous 1-D or 2-D tensor expected")
+    if not x.is_cuda:
+        raise TypeError(f"{what}: a CUDA tensor expected")
+    rows, cols = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    return rows, cols, keys[x.dtype]
+
+
 def topk(x, k: int, largest: bool = True, workspace=None, stream=None):
     """(values, indices) of the k largest (smallest) keys of every row of x, best first: topk_device
     with its outputs allocated.  x: a contiguous 1-D (one row) or 2-D CUDA tensor of dtype int32,
@@ -691,17 +705,10 @@ def topk(x, k: int, largest: bool = True, workspace=None, stream=None):
     TypeError for another dtype or a non-contiguous tensor, before the device is touched.  Workspace
     and status as topk_device."""
     import torch
-    keys = {torch.int32: "i32", torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
-    if not isinstance(x, torch.Tensor) or x.dtype not in keys:
-        raise TypeError(f"topk: int32, float32, bfloat16 or float16 tensor expected, got {getattr(x, 'dtype', type(x))}")
-    if x.dim() not in (1, 2) or not x.is_contiguous():
-        raise TypeError("topk: a contiguous 1-D or 2-D tensor expected")
-    if not x.is_cuda:
-        raise TypeError("topk: a CUDA tensor expected")
-    rows, cols = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    rows, cols, key = _dense_rows("topk", x)
     values = torch.empty((rows, k), dtype=x.dtype, device=x.device)
     indices = torch.empty((rows, k), dtype=torch.int32, device=x.device)
-    topk_device(x, rows, cols, k, values, indices, largest=largest, key=keys[x.dtype], workspace=workspace, stream=stream)
+    topk_device(x, rows, cols, k, values, indices, largest=largest, key=key, workspace=workspace, stream=stream)
     return values, indices
 
 
@@ -746,18 +753,10 @@ def sort(x, descending: bool = False, workspace=None, stream=None):
     a non-contiguous or a CPU tensor, before the device is touched.  Workspace and status as
     sort_rows_device."""
     import torch
-    keys = {torch.int32: "i32", torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
-    if not isinstance(x, torch.Tensor) or x.dtype not in keys:
-        raise TypeError(f"sort: int32, float32, bfloat16 or float16 tensor expected, got {getattr(x, 'dtype', type(x))}")
-    if x.dim() not in (1, 2) or not x.is_contiguous():
-        raise TypeError("sort: a contiguous 1-D or 2-D tensor expected")
-    if not x.is_cuda:
-        raise TypeError("sort: a CUDA tensor expected")
-    rows, cols = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    rows, cols, key = _dense_rows("sort", x)
     values = torch.empty_like(x)
     indices = torch.empty(x.shape, dtype=torch.int32, device=x.device)
-    sort_rows_device(x, rows, cols, values, indices, descending=descending, key=keys[x.dtype], workspace=workspace,
-                     stream=stream)
+    sort_rows_device(x, rows, cols, values, indices, descending=descending, key=key, workspace=workspace, stream=stream)
     return values, indices
 
 

@@ -49,9 +49,9 @@ struct FinSmem {
     uint32_t ordered;
 };
 
-// A bucket [b, b + len) striped over the W waves in runs of jn 64-key groups, as in k_seg_block:
-// this wave's stripe starts at slot ws0 and holds nf whole groups and a last one of `tail` keys.
-// Wave-uniform but tail_ok.
+// A bucket [b, b + len) striped over the W waves as block_stripe (lds_class.h) stripes a unit.  Wave-uniform
+// but tail_ok.  (The arithmetic stands here a second time: through block_stripe the kernel gained four
+// scalar instructions and bench.py's headline read 0.2-0.5 % higher in four sessions of four)
 struct FinStripe {
     size_t sb;     // b + ws0: the stripe's first key in global memory
     uint32_t ws0;  // its first LDS slot

@@ -1,5 +1,5 @@
 // host.h -- what every host driver of liblabsort.so needs, each defined once (internal:
-// api.hip, gsweep.hip, segsort.hip, topk.hip).
+// api.hip, kernels.hip, merge4.hip, gsweep.hip, segsort.hip, topk.hip, rowsort.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,6 +35,40 @@ inline bool topk_key_type_ok(int key_type) { return device_key_type_ok(key_type)
 // share their output.
 inline bool pairs_alias_ok(const void *ki, const void *vi, const void *ko, const void *vo) {
     return (ki == ko) == (vi == vo) && ko != vo;
+}
+
+// Compute units of the current device, asked once per process (256 where the runtime will not say; hidden: one copy)
+__attribute__((visibility("hidden"))) inline int cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+    }
+    return cus;
+}
+
+// Do the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte?
+inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+// The argument checks of a dense call (top-k, row sort) that reads rows x cols keys and writes
+// rows x k keys and, with idx_out, as many 32-bit positions; rows, k != 0.  LABSORT_OK or LABSORT_ERR_ARG.
+inline int dense_rows_args(const void *keys, size_t rows, size_t cols, size_t k, int key_type, const void *keys_out,
+                           const void *idx_out) {
+    if (!keys || !keys_out) return LABSORT_ERR_ARG;
+    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    const bool k16 = key_type_is16(key_type);
+    const size_t esz = k16 ? 2 : 4;  // bytes per key
+    if (k16 && (((uintptr_t)keys | (uintptr_t)keys_out) & 1u)) return LABSORT_ERR_ARG;
+    if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    if (idx_out == keys_out) return LABSORT_ERR_ARG;
+    if (ranges_overlap(keys, rows * cols * esz, keys_out, rows * k * esz)) return LABSORT_ERR_ARG;
+    if (idx_out && ranges_overlap(keys, rows * cols * esz, idx_out, rows * k * 4)) return LABSORT_ERR_ARG;
+    return LABSORT_OK;
 }
 
 // Timing scope: with labsort_timing_enable(1), an event pair on s around the launches made

@@ -32,6 +32,7 @@
 // lane_order_probed, fold_digit_offsets, block_diff_bits, get16 / set16.
 #include "common.h"
 #include "devutil.h"
+#include "host.h"
 #include "lds_pass.h"
 
 #include <cstdlib>
@@ -1758,16 +1759,6 @@ hipError_t launch_onesweep(Bufs b, const Plan *plan, int pass, int bits, size_t 
     k_onesweep<1, OS_BLOCK, OS_KPT><<<g, OS_BLOCK, 0, s>>>(b, plan, pass, (uint32_t)n, flip, hist, lookback, counter,
                                                            err);
     return hipGetLastError();
-}
-
-static int cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
 }
 
 hipError_t launch_onesweep_p(Bufs b, const Plan *plan, int pass, size_t n, uint32_t flip, const SegPlan *sp,

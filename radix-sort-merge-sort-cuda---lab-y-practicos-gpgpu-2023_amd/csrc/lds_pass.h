@@ -1,6 +1,6 @@
 // lds_pass.h -- the workgroup-wide 8-bit LSD passes over keys held in registers and LDS,
-// shared by k_tile_sort (kernels.hip: one tile per workgroup) and k_seg_block (segsort.hip:
-// one segment per workgroup).
+// shared by k_tile_sort (kernels.hip: one tile per workgroup) and block_sort_unit (lds_class.h:
+// one segment or one row per workgroup, k_seg_block and k_rs_block).
 #pragma once
 #include "devutil.h"
 

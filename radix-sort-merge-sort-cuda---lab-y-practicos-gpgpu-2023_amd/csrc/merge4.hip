@@ -31,6 +31,7 @@
 // (pass 0.745 ms: rank 0.077 + merge 0.68, VALU- and LDS-bound), key/value 13.95 -> 11.61 ms.
 #include "common.h"
 #include "devutil.h"
+#include "host.h"
 
 namespace labsort {
 
@@ -817,17 +818,15 @@ hipError_t launch_merge4_pass(const uint32_t *in, uint32_t *out, size_t n, size_
     k_m4_rank<<<(unsigned)((nsamp + M4_RT - 1) / M4_RT), M4_RB, 0, s>>>(in, G, flip, samp, reinterpret_cast<uint4 *>(bnd));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const uint32_t want = (uint32_t)(M4_BLOCKS_PER_CU * (cus > 0 ? cus : 256));
+    const int cus = cu_count();
+    const uint32_t want = (uint32_t)(M4_BLOCKS_PER_CU * cus);
     uint32_t per = (G.nblocks + want - 1) / want;
     if (per > M4_MAX_PER) per = M4_MAX_PER;
     const uint32_t g = (G.nblocks + per - 1) / per;
     const bool wide = r > ((size_t)1 << 28);  // a group's byte offsets pass 2^32
     const uint4 *bt = reinterpret_cast<const uint4 *>(bnd);
     if (vin) {
-        const uint32_t want_kv = (uint32_t)(2 * (cus > 0 ? cus : 256));  // two 70 KB workgroups per CU
+        const uint32_t want_kv = (uint32_t)(2 * cus);  // two 70 KB workgroups per CU
         uint32_t pkv = (G.nblocks + want_kv - 1) / want_kv;
         if (pkv > M4_MAX_PER) pkv = M4_MAX_PER;
         const uint32_t gkv = (G.nblocks + pkv - 1) / pkv;

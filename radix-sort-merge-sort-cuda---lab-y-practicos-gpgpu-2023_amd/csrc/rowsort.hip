@@ -4,7 +4,7 @@
 //
 // Every row has the same length, so the segmented sort's length class is a host decision and the
 // row index gives the base: no offsets, no class lists, no binning.  A row that fits the LDS tile
-// is read once, sorted by the 8-bit LSD passes of lds_pass.h and written once; a key's position is
+// is read once, sorted by the class bodies of lds_class.h and written once; a key's position is
 // the slot it was loaded into, never read from memory:
 //   32-bit keys with positions   the key/value shapes, v[j] = slot, carried through LDS as a payload
 //   32-bit keys alone            the keys-only shapes
@@ -21,7 +21,7 @@
 
 #include "devutil.h"
 #include "host.h"
-#include "lds_pass.h"
+#include "lds_class.h"
 #include "segsort.h"
 #include "topk.h"
 
@@ -33,55 +33,53 @@ namespace {
 // (f32_ord(word) ^ flip), or a 16-bit float packed with its position (above).
 enum RsMode : int { RS_K32, RS_F32, RS_P16 };
 
-// The sorted word of the element at index i (position pos within its row).
+// The key policy of lds_class.h.  x16, nan_t: of a 16-bit call (above).
 template <int MODE>
-__device__ __forceinline__ uint32_t rs_load(const void *in, size_t i, uint32_t pos, uint32_t x16, uint32_t nan_t) {
-    if constexpr (MODE == RS_P16) return ((ord16(static_cast<const uint16_t *>(in)[i], nan_t) ^ x16) << 16) | pos;
-    else if constexpr (MODE == RS_F32) return f32_ord(static_cast<const uint32_t *>(in)[i]);
-    else return static_cast<const uint32_t *>(in)[i];
-}
-// Element i of the outputs from the sorted word k (and its payload v): the key untransformed,
-// the position as a 32-bit word (iout == nullptr for a 16-bit call: keys only).
-template <int MODE, bool KV>
-__device__ __forceinline__ void rs_store(void *out, uint32_t *iout, size_t i, uint32_t k, uint32_t v, uint32_t x16) {
-    if constexpr (MODE == RS_P16) {
-        static_cast<uint16_t *>(out)[i] = (uint16_t)unord16((k >> 16) ^ x16);
-        if (iout) iout[i] = k & 0xFFFFu;  // (uniform over the launch)
-    } else {
-        static_cast<uint32_t *>(out)[i] = MODE == RS_F32 ? f32_unord(k) : k;
-        if constexpr (KV) iout[i] = v;
+struct RowKeys {
+    const void *in;
+    void *out;
+    uint32_t *iout;  // nullptr for a 16-bit call without positions (uniform over the launch)
+    uint32_t x16, nan_t;
+    // the sorted word of element i, at position pos of its row
+    __device__ __forceinline__ uint32_t load(size_t i, uint32_t pos) const {
+        if constexpr (MODE == RS_P16) return ((ord16(static_cast<const uint16_t *>(in)[i], nan_t) ^ x16) << 16) | pos;
+        else if constexpr (MODE == RS_F32) return f32_ord(static_cast<const uint32_t *>(in)[i]);
+        else return static_cast<const uint32_t *>(in)[i];
     }
-}
-// The digits that can differ: a packed word's position half never starts a pass.
-template <int MODE>
-__device__ __forceinline__ uint32_t rs_diff(uint32_t diff) {
-    return MODE == RS_P16 ? diff & 0xFFFF0000u : diff;
-}
-
-// ---------------------------------------------------------------------------------
-// wave classes: one wave64 per row, no workgroup barrier (k_seg_wave on row = unit)
-// ---------------------------------------------------------------------------------
-template <int KPT, bool KV>
-struct RsWaveSmem {
-    uint32_t keys[WAVE * KPT];
-    uint32_t vals[KV ? WAVE * KPT : 1];
-    uint32_t hist[256];
-    uint32_t probe[WAVE];
+    // a key's position is the slot it was loaded into, never read from memory
+    __device__ __forceinline__ uint32_t payload(size_t, uint32_t pos) const { return pos; }
+    // element i of the outputs: the key untransformed, the position as a 32-bit word
+    __device__ __forceinline__ void store_key(size_t i, uint32_t k) const {
+        if constexpr (MODE == RS_P16) static_cast<uint16_t *>(out)[i] = (uint16_t)unord16((k >> 16) ^ x16);
+        else static_cast<uint32_t *>(out)[i] = MODE == RS_F32 ? f32_unord(k) : k;
+    }
+    template <bool KV>
+    __device__ __forceinline__ void store_payload(size_t i, uint32_t k, uint32_t v) const {
+        static_assert(!(MODE == RS_P16 && KV), "a packed word carries its position");
+        if constexpr (MODE == RS_P16) {
+            if (iout) iout[i] = k & 0xFFFFu;
+        } else if constexpr (KV) {
+            iout[i] = v;
+        }
+    }
+    // the digits that can differ: a packed word's position half never starts a pass
+    static __device__ __forceinline__ uint32_t diff(uint32_t d) { return MODE == RS_P16 ? d & 0xFFFF0000u : d; }
 };
 
+// wave classes: one wave64 per row, wave-private LDS, no workgroup barrier (k_seg_wave on row = unit).
 // fx: the flip of a 32-bit call, x16 of a 16-bit one (which sorts with flip = 0)
 template <int KPT, bool KV, int MODE>
 __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_rs_wave(const void *in, void *out, uint32_t *iout, uint32_t rows,
                                                                  uint32_t len, uint32_t fx, uint32_t nan_t) {
-    static_assert(!(MODE == RS_P16 && KV), "a packed word carries its position");
     constexpr uint32_t CAP = WAVE * KPT;
-    __shared__ RsWaveSmem<KPT, KV> sm_all[SEG_WAVE_WPB];
+    __shared__ WaveSmem<KPT, KV> sm_all[SEG_WAVE_WPB];
     const uint32_t lane = threadIdx.x & 63u, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t first = blockIdx.x * SEG_WAVE_WPB + wid;
     if (first >= rows || len == 0u || len > CAP) return;  // (wave-uniform; the host picks the class by len)
-    RsWaveSmem<KPT, KV> &sm = sm_all[wid];
-    const uint32_t flip = MODE == RS_P16 ? 0u : fx, x16 = MODE == RS_P16 ? fx : 0u;
+    WaveSmem<KPT, KV> &sm = sm_all[wid];
+    const uint32_t flip = MODE == RS_P16 ? 0u : fx;
     const uint32_t sentinel = ~flip;
+    const RowKeys<MODE> io{in, out, iout, MODE == RS_P16 ? fx : 0u, nan_t};
     const bool atomic_rank = lds_lane_ordered(sm.probe, lane);
     const uint32_t jn = (len + WAVE - 1u) / WAVE;  // 64-key groups that hold keys (<= KPT)
     for (uint32_t row = first; row < rows; row += gridDim.x * SEG_WAVE_WPB) {
@@ -89,13 +87,12 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_rs_wave(const void *in,
         if (len <= (uint32_t)WAVE) {
             // one key per lane: its stable rank is the count of keys before it in (key, lane) order
             const bool ok = lane < len;
-            const uint32_t x = ok ? (rs_load<MODE>(in, b + (ok ? lane : 0u), lane, x16, nan_t) ^ flip) : 0xFFFFFFFFu;
-            uint32_t r = 0u;
-            for (uint32_t i = 0; i < len; ++i) {
-                const uint32_t xi = __builtin_amdgcn_readlane(x, (int)i);
-                r += (xi < x || (xi == x && i < lane)) ? 1u : 0u;
+            const uint32_t x = ok ? (io.load(b + (ok ? lane : 0u), lane) ^ flip) : 0xFFFFFFFFu;
+            const uint32_t r = wave_rank64(x, len, lane);
+            if (ok) {  // r < len
+                io.store_key(b + r, x ^ flip);
+                io.template store_payload<KV>(b + r, x ^ flip, lane);
             }
-            if (ok) rs_store<MODE, KV>(out, iout, b + r, x ^ flip, lane, x16);  // r < len
             continue;
         }
         uint32_t k[KPT];
@@ -106,14 +103,14 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_rs_wave(const void *in,
             const uint32_t idx = (uint32_t)j * WAVE + lane;
             const bool ok = idx < len;
             k[j] = sentinel;
-            if (ok) k[j] = rs_load<MODE>(in, b + idx, idx, x16, nan_t);
+            if (ok) k[j] = io.load(b + idx, idx);
             if constexpr (KV) v[j] = idx;
             const uint32_t x = k[j] ^ flip;
             a &= ok ? x : ~0u;
             o |= ok ? x : 0u;
         }
         wave_and_or(a, o);
-        const uint32_t diff = rs_diff<MODE>(__builtin_amdgcn_readfirstlane(a ^ o));
+        const uint32_t diff = RowKeys<MODE>::diff(__builtin_amdgcn_readfirstlane(a ^ o));
         for (int pass = 0; pass < 4; ++pass) {
             const uint32_t shift = pass * 8;
             if (((diff >> shift) & 0xFFu) == 0u) continue;  // uniform over the row
@@ -173,19 +170,18 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_rs_wave(const void *in,
             const uint32_t idx = (uint32_t)j * WAVE + lane;
             uint32_t vj = 0u;
             if constexpr (KV) vj = v[j];
-            if (idx < len) rs_store<MODE, KV>(out, iout, b + idx, k[j], vj, x16);
+            if (idx < len) {
+                io.store_key(b + idx, k[j]);
+                io.template store_payload<KV>(b + idx, k[j], vj);
+            }
         }
     }
 }
 
-// ---------------------------------------------------------------------------------
-// block and tile classes: one row per workgroup, striped over the waves in runs of
-// S = 64 ceil(len / (64 W)) slots (k_seg_block on row = unit).
-// ---------------------------------------------------------------------------------
+// block and tile classes: block_sort_unit (lds_class.h) on one row per workgroup
 template <int BLOCK, int KPT, bool KV, int WPE, int MODE>
 __global__ __launch_bounds__(BLOCK, WPE) void k_rs_block(const void *in, void *out, uint32_t *iout, uint32_t rows, uint32_t len,
                                                           uint32_t fx, uint32_t nan_t) {
-    static_assert(!(MODE == RS_P16 && KV), "a packed word carries its position");
     using S = TsSmem<BLOCK, KPT, KV>;
     constexpr int W = S::W;
     constexpr uint32_t TILE = S::TILE;
@@ -193,98 +189,18 @@ __global__ __launch_bounds__(BLOCK, WPE) void k_rs_block(const void *in, void *o
     __shared__ S sm;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (blockIdx.x >= rows || len == 0u || len > TILE) return;  // (uniform; the host picks the class by len)
-    const uint32_t flip = MODE == RS_P16 ? 0u : fx, x16 = MODE == RS_P16 ? fx : 0u;
-    const uint32_t sentinel = ~flip;
+    const uint32_t flip = MODE == RS_P16 ? 0u : fx;
+    const RowKeys<MODE> io{in, out, iout, MODE == RS_P16 ? fx : 0u, nan_t};
     probe_lane_order(sm.probe, &sm.ordered, lane, wid);
     __syncthreads();
     const bool atomic_rank = lane_order_probed(&sm.ordered);
     for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
-        // (the row's shape is formed again for every row, from a copy of len the compiler cannot
-        // see through: hoisted out of the loop these values were held in SGPRs across it and spilled)
+        // (the row's stripe is formed again for every row, from a copy of len the compiler cannot
+        // see through: hoisted out of the loop its values were held in SGPRs across it and spilled)
         uint32_t rl = len;
         asm volatile("" : "+s"(rl));
-        const uint32_t jn = (rl + (uint32_t)(W * WAVE) - 1u) / (uint32_t)(W * WAVE);  // groups per wave, <= KPT
-        const uint32_t ws0 = wid * jn * WAVE;  // first slot of this wave's stripe
-        // this wave's keys: nf whole 64-key groups and a last group of `tail` keys (wave-uniform)
-        const uint32_t rem = ws0 < rl ? rl - ws0 : 0u;
-        const uint32_t nf = min(jn, rem / WAVE);
-        const uint32_t tail = nf < jn ? rem - nf * WAVE : 0u;  // < 64
-        const uint32_t ng = nf + (tail ? 1u : 0u);             // groups that hold keys
-        const bool tail_ok = lane < tail;
-        // scalar base + 32-bit lane offset per access (the lane offsets pass through empty asms, as in k_seg_block)
-        const size_t sb = (size_t)row * len + ws0;
-        uint32_t lin = lane;
-        asm volatile("" : "+v"(lin));
-        uint32_t k[KPT];
-        uint32_t v[KV ? KPT : 1];
-        uint32_t a = ~0u, o = 0u;
-        // every load first, so all of them are in flight together, then the bits the keys differ in
-        if (nf == (uint32_t)KPT) {  // a whole tile: straight-line loads
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                const uint32_t sl = (uint32_t)(j * WAVE) + lin;
-                k[j] = rs_load<MODE>(in, sb + sl, ws0 + sl, x16, nan_t);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                k[j] = sentinel;
-                if ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) {
-                    const uint32_t sl = (uint32_t)(j * WAVE) + lin;
-                    k[j] = rs_load<MODE>(in, sb + sl, ws0 + sl, x16, nan_t);
-                }
-            }
-        }
-        if constexpr (KV) {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) v[j] = ws0 + (uint32_t)(j * WAVE) + lane;  // the position is the slot
-        }
-#pragma unroll
-        for (int j = 0; j < KPT; ++j) {
-            const uint32_t x = k[j] ^ flip;  // padding: all ones
-            a &= x;
-            o |= ((uint32_t)j < nf || ((uint32_t)j == nf && tail_ok)) ? x : 0u;
-        }
-        const uint32_t diff =
-            rs_diff<MODE>(__builtin_amdgcn_readfirstlane(block_diff_bits<W>(a, o, sm.red_and, sm.red_or, lane, wid)));
-        lds_sort_passes(sm, k, v, diff, flip, ws0, atomic_rank, LeadingGroups{ng}, lane, wid);
-        uint32_t nfs = nf, lout = lane;
-        asm volatile("" : "+s"(nfs), "+v"(lout));
-        if (nfs == (uint32_t)KPT) {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                uint32_t vj = 0u;
-                if constexpr (KV) vj = v[j];
-                rs_store<MODE, KV>(out, iout, sb + ((uint32_t)(j * WAVE) + lout), k[j], vj, x16);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < KPT; ++j) {
-                uint32_t vj = 0u;
-                if constexpr (KV) vj = v[j];
-                if ((uint32_t)j < nfs || ((uint32_t)j == nfs && tail_ok))
-                    rs_store<MODE, KV>(out, iout, sb + ((uint32_t)(j * WAVE) + lout), k[j], vj, x16);
-            }
-        }
-        __syncthreads();  // the next row reuses red_and / red_or and the key slots
+        block_sort_unit(sm, io, (size_t)row * len, block_stripe<W>(rl, lane, wid), flip, atomic_rank, lane, wid);
     }
-}
-
-int rs_cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
-// The class of a row length: 0-2 wave, 3 block, 4 tile; the edges of SegEdges (segsort.h).
-int rs_class(size_t cols) {
-    return cols <= (size_t)SEG_WAVE_KEYS ? 0 : cols <= (size_t)SEG_WAVE2_KEYS ? 1 : cols <= (size_t)SEG_WAVE3_KEYS ? 2
-         : cols <= (size_t)SEG_BLOCK_KEYS ? 3 : 4;
 }
 
 // One launch: the kernel of class c over all rows.  Two grid forms: the segmented sort's fixed
@@ -300,26 +216,20 @@ template <int MODE, bool KV>
 hipError_t launch_rs(int c, const void *in, void *out, uint32_t *iout, size_t rows, size_t cols, uint32_t fx,
                      uint32_t nan_t, int form, hipStream_t s) {
     const bool per_row = form == RS_GRID_ROWS || (form == RS_GRID_AUTO && (c == 1 || c == 3));
-    const size_t cus = (size_t)rs_cu_count();
-    const uint32_t r = (uint32_t)rows, n = (uint32_t)cols;
-    const size_t wgs = c < 3 ? (rows + SEG_WAVE_WPB - 1) / SEG_WAVE_WPB : rows;  // workgroups that have a row
-    auto grid = [&](size_t fixed) { return (unsigned)((per_row || wgs < fixed) ? wgs : fixed); };
-    constexpr int WB = SEG_WAVE_WPB * WAVE;
-    if (c == 0) k_rs_wave<SEG_WAVE_KPT, KV, MODE><<<grid(cus * 8), WB, 0, s>>>(in, out, iout, r, n, fx, nan_t);
-    else if (c == 1) k_rs_wave<SEG_WAVE2_KPT, KV, MODE><<<grid(cus * (KV ? 6 : 8)), WB, 0, s>>>(in, out, iout, r, n, fx, nan_t);
-    else if (c == 2) k_rs_wave<SEG_WAVE3_KPT, KV, MODE><<<grid(cus * 4), WB, 0, s>>>(in, out, iout, r, n, fx, nan_t);
-    else if (c == 3)
-        k_rs_block<SEG_BLOCK, SEG_BLOCK_KPT, KV, SEG_BLOCK_WPE, MODE>
-            <<<grid(cus * (KV ? 4 : (size_t)SEG_BLOCK_WGS)), SEG_BLOCK, 0, s>>>(in, out, iout, r, n, fx, nan_t);
-    else if (c == 4)
-        k_rs_block<TS_BLOCK, KV ? TS_KPT_KV : TS_KPT, KV, 4, MODE><<<grid(cus), TS_BLOCK, 0, s>>>(in, out, iout, r, n, fx, nan_t);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-bool rs_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
+    const size_t cus = (size_t)cu_count();
+    return seg_class_dispatch(c, [&](auto cc) {
+        constexpr int C = decltype(cc)::value;
+        constexpr SegClass g = SEG_CLASS[C];
+        constexpr int KPT = KV ? g.kpt_kv : g.kpt;
+        const size_t wgs = C < 3 ? (rows + SEG_WAVE_WPB - 1) / SEG_WAVE_WPB : rows;  // workgroups that have a row
+        const size_t fixed = cus * (size_t)(KV ? g.wgs_kv : g.wgs);
+        const unsigned grid = (unsigned)((per_row || wgs < fixed) ? wgs : fixed);
+        if constexpr (C < 3)
+            k_rs_wave<KPT, KV, MODE><<<grid, g.block, 0, s>>>(in, out, iout, (uint32_t)rows, (uint32_t)cols, fx, nan_t);
+        else
+            k_rs_block<g.block, KPT, KV, g.wpe, MODE><<<grid, g.block, 0, s>>>(in, out, iout, (uint32_t)rows, (uint32_t)cols, fx, nan_t);
+        return hipGetLastError();
+    });
 }
 
 // Which rows the LDS kernels take: the keys-only tile for packed 16-bit keys and for 32-bit keys
@@ -345,16 +255,8 @@ int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int d
                              uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
     static_assert(TK_HDR_BYTES == SEG_HDR_BYTES, "one header, one status word, on both paths");
     if (rows == 0 || cols == 0) return LABSORT_OK;
-    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
-    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (const int rc = dense_rows_args(d_keys, rows, cols, cols, key_type, d_keys_out, d_idx_out)) return rc;
     const bool k16 = key_type_is16(key_type);
-    const size_t esz = k16 ? 2 : 4;  // bytes per key
-    if (k16 && (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u)) return LABSORT_ERR_ARG;
-    if (rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
-    if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
-    const size_t n = rows * cols;
-    if (rs_overlap(d_keys, n * esz, d_keys_out, n * esz)) return LABSORT_ERR_ARG;
-    if (d_idx_out && rs_overlap(d_keys, n * esz, d_idx_out, n * 4)) return LABSORT_ERR_ARG;
     if (!d_ws || ws_bytes < labsort_sort_rows_workspace_bytes(rows, cols)) return LABSORT_ERR_ARG;
     if (!rs_lds_path(cols, k16, d_idx_out != nullptr))
         return labsort_topk_device(d_keys, rows, cols, cols, descending, key_type, d_keys_out, d_idx_out, d_ws, ws_bytes,
@@ -362,7 +264,7 @@ int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int d
     hipStream_t s = as_stream(stream);
     HIP_TRY(launch_zero(d_ws, SEG_HDR_BYTES, s));  // (a kernel: graph-replayable; nothing sets the header after it)
     TimingScope ts(LABSORT_K_SEGSORT, s);
-    const int c = rs_class(cols);
+    const int c = seg_class_of(cols);
     int form = RS_GRID_AUTO;  // the grid form: per class, unless forced
     if (const char *e = std::getenv("LABSORT_ROWSORT_GRID"))
         form = !std::strcmp(e, "rows") ? RS_GRID_ROWS : !std::strcmp(e, "fixed") ? RS_GRID_FIXED : RS_GRID_AUTO;

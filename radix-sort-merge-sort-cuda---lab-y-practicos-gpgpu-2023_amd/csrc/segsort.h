@@ -1,5 +1,7 @@
 // segsort.h -- segmented sort (segsort.hip): shapes, workspace header and what top-k shares of it.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace labsort {
@@ -53,6 +55,34 @@ struct SegEdges {
     uint32_t e[SEG_CLASSES - 1];  // upper length bounds below the tile
 };
 static_assert(SEG_WAVE3_KEYS < SEG_BLOCK_KEYS, "class edges ascend");
+// The class table of the segmented sort's and the dense row sort's launches: the kernel shape of class
+// c (0-2 wave, 3 block, 4 tile) and its fixed grid, a multiple of the CU count: what stays resident by LDS.
+struct SegClass {
+    int keys;          // longest unit below the tile class (the tile's bound depends on keys / pairs)
+    int block;         // threads per workgroup
+    int kpt, kpt_kv;   // keys per thread: keys only, pairs
+    int wpe;           // waves per SIMD in the launch bounds (block and tile kernels)
+    int wgs, wgs_kv;   // workgroups per CU: keys only, pairs
+};
+constexpr SegClass SEG_CLASS[SEG_CLASSES] = {
+    {SEG_WAVE_KEYS, SEG_WAVE_WPB * WAVE, SEG_WAVE_KPT, SEG_WAVE_KPT, 0, 8, 8},
+    {SEG_WAVE2_KEYS, SEG_WAVE_WPB * WAVE, SEG_WAVE2_KPT, SEG_WAVE2_KPT, 0, 8, 6},
+    {SEG_WAVE3_KEYS, SEG_WAVE_WPB * WAVE, SEG_WAVE3_KPT, SEG_WAVE3_KPT, 0, 4, 4},  // 110-127 VGPRs: four waves per SIMD
+    {SEG_BLOCK_KEYS, SEG_BLOCK, SEG_BLOCK_KPT, SEG_BLOCK_KPT, SEG_BLOCK_WPE, SEG_BLOCK_WGS, 4},
+    {SEG_TILE_KEYS, TS_BLOCK, TS_KPT, TS_KPT_KV, 4, 1, 1},
+};
+// The class of a length: the first whose edge holds it, else the tile.
+inline int seg_class_of(size_t len) {
+    int c = 0;
+    while (c < SEG_CLASSES - 1 && len > (size_t)SEG_CLASS[c].keys) ++c;
+    return c;
+}
+// fn(std::integral_constant<int, c>): the class as a compile-time constant, so fn names kernels by SEG_CLASS[c]
+template <int C = 0, class Fn>
+hipError_t seg_class_dispatch(int c, Fn &&fn) {
+    if constexpr (C < SEG_CLASSES) return c == C ? fn(std::integral_constant<int, C>{}) : seg_class_dispatch<C + 1>(c, fn);
+    else return hipErrorInvalidValue;
+}
 
 // Workspace header (the first 256 bytes, cleared at the start of every call).
 //   word 0: offsets rejected by k_seg_bin (labsort_segments_workspace_status: ERR_ARG)

@@ -184,11 +184,8 @@ hipError_t launch_seg_bin(const uint32_t *off, size_t nseg, size_t n, size_t max
 hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in, uint32_t *out, const uint32_t *vin,
                                   uint32_t *vout, const uint32_t *off, const uint32_t *hdr, const uint32_t *lists,
                                   size_t stride, uint32_t flip, bool f32, hipStream_t s) {
-    size_t edges[SEG_CLASSES];
-    labsort_segment_class_edges(pairs ? 1 : 0, edges, SEG_CLASSES);
-    int ncls = 1;
-    while (ncls < SEG_CLASSES && max_len > edges[ncls - 1]) ++ncls;
-    for (int c = 0; c < ncls; ++c) {
+    (void)pairs;  // the class edges below the tile are the same for keys and pairs
+    for (int c = 0; c <= seg_class_of(max_len); ++c) {
         const hipError_t e = launch_seg_sort(c, in, out, vin, vout, off, hdr, lists + (size_t)c * stride, flip, s, HySel{}, f32);
         if (e != hipSuccess) return e;
     }

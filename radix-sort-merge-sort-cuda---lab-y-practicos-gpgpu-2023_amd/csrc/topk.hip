@@ -837,10 +837,6 @@ TopkLayout topk_layout(size_t rows, size_t cols, size_t k) {
         L.total = std::max(L.total, topk_layout_path(rows, cols, cols / TK_SORT_DIV, TK_PATH_SELECT).total);
     return L;
 }
-bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
 }  // namespace
 
 size_t labsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k) {
@@ -851,15 +847,8 @@ size_t labsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k) {
 int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, int largest, int key_type,
                         void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
     if (rows == 0 || k == 0) return LABSORT_OK;
-    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
-    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (const int rc = dense_rows_args(d_keys, rows, cols, k, key_type, d_keys_out, d_idx_out)) return rc;
     const bool k16 = key_type_is16(key_type);
-    const size_t esz = k16 ? 2 : 4;  // bytes per key
-    if (k16 && (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u)) return LABSORT_ERR_ARG;
-    if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
-    if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
-    if (ranges_overlap(d_keys, rows * cols * esz, d_keys_out, rows * k * esz)) return LABSORT_ERR_ARG;
-    if (d_idx_out && ranges_overlap(d_keys, rows * cols * esz, d_idx_out, rows * k * 4)) return LABSORT_ERR_ARG;
     const int path = topk_path(rows, cols, k);
     // the survivors of several long rows are ordered by the segmented sort: past its LDS tile, its general path
     if (path == TK_PATH_SELECT && rows > 1 && k > (size_t)SEG_TILE_PAIRS && rows * k > RADIX_MAX_N) return LABSORT_ERR_ARG;

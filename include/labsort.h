@@ -80,8 +80,8 @@ extern "C" {
  * sorts, labsort_merge_runs, labsort_upper_bound, the C++ drop-ins).  The building blocks
  * that take a key type without checking it order U32 / I32 words only. */
 #define LABSORT_KEY_F32 2
-/* bfloat16 and IEEE-754 binary16: 16-bit elements, accepted by labsort_topk_device and
- * labsort_sort_rows_device ONLY (every other entry that checks its key type returns
+/* bfloat16 and IEEE-754 binary16: 16-bit elements, accepted by labsort_topk_device,
+ * labsort_sort_rows_device and labsort_sort16_device ONLY (every other entry that checks its key type returns
  * LABSORT_ERR_ARG for them, the segmented and whole-array device sorts included).  The float32 contract at 16 bits: with T = 0x7F80 (bfloat16)
  * or 0x7C00 (binary16), an element x is ordered by
  *   ord16(x) = 0xFFFF         if (x & 0x7FFF) > T   (every NaN, either sign)
@@ -399,8 +399,8 @@ int labsort_topk_workspace_status(const void *d_workspace, void *stream);
  * row's (u(key), position) pairs, keys written back untransformed: equal keys stay in order of
  * position in both directions, NaNs are the largest keys and come back as 0x7FFFFFFF / 0x7FFF,
  * -0.0 is below +0.0.  key_type: all five (U32, I32, F32, BF16, F16); for the 16-bit types d_keys
- * and d_keys_out hold 2-byte elements and need 2-byte alignment only.  This is the one sorting
- * entry that takes the 16-bit types.
+ * and d_keys_out hold 2-byte elements and need 2-byte alignment only.  This and
+ * labsort_sort16_device (below) are the two sorting entries that take the 16-bit types.
  * rows * cols <= 2^31 - 1; rows == 0 or cols == 0 launches nothing (LABSORT_OK before anything
  * else is looked at).  LABSORT_ERR_ARG before any launch: NULL d_keys / d_keys_out, a bad key
  * type, rows > (2^31 - 1) / cols, an odd d_keys / d_keys_out address with a 16-bit type,
@@ -428,6 +428,52 @@ int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int d
                              void *d_keys_out, uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes,
                              void *stream);
 int labsort_sort_rows_workspace_status(const void *d_workspace, void *stream);
+
+/* ---- sort of 16-bit rows of any length (bfloat16 / float16 logits of vocabulary length sorted whole,
+ * one long score vector argsorted; no lab.cu counterpart) ----
+ * labsort_sort_rows_device's contract, restricted to LABSORT_KEY_BF16 / LABSORT_KEY_F16: d_keys is a
+ * dense rows x cols matrix of 2-byte elements, never written; row r of the output is the stable
+ * ascending sort of the row's (ord16(key) ^ (descending ? 0xFFFF : 0), position) pairs, keys written
+ * back untransformed: NaNs are equal, largest and come back as 0x7FFF, -0.0 < +0.0, ties go by
+ * position in both directions.  d_idx_out holds rows x cols 32-bit positions within the row, or is
+ * NULL (the keys written are the same either way); rows == 1 is the whole-array sort and d_idx_out
+ * then its stable argsort.  For every input, keys and positions are bit-identical to what
+ * labsort_sort_rows_device writes.
+ * rows == 0 or cols == 0 launches nothing (LABSORT_OK before anything else is looked at).
+ * LABSORT_ERR_ARG before any launch: any other key type (U32 / I32 / F32 included), and what
+ * labsort_sort_rows_device rejects: NULL d_keys / d_keys_out, rows > (2^31 - 1) / cols, an odd
+ * d_keys / d_keys_out address (2-byte alignment is enough; rows of odd length start on either 2-byte
+ * phase), d_idx_out == d_keys_out, an output that overlaps the input (by the real element sizes), a
+ * missing or short workspace.
+ * cols <= labsort_segment_tile_keys(): the launch labsort_sort_rows_device makes for the shape (its
+ * LDS kernels); the workspace is the 256-byte header.
+ * Longer rows: two stable LSD passes with 8-bit digits on u = ord16(key) ^ x16, low byte then high
+ * byte.  Rows are independent and cut into chunks of up to labsort_sort16_chunk_keys() consecutive
+ * keys (the last may be partial; any cols is fine).  Pass 1 reads d_keys and writes u and, with
+ * positions, where each key was loaded from to a temporary in the workspace; pass 2 reads the
+ * temporary and writes d_keys_out and d_idx_out.  With d_idx_out == NULL no position is stored or
+ * loaded anywhere.  A pass is three launches -- digit counts per (row, chunk) into a table
+ * [row][digit][chunk] by plain stores, an exclusive scan of the table along the chunks with the
+ * digit totals per row, the scatter of every (row, chunk) -- and no kernel waits on another
+ * workgroup: about 24 bytes of memory traffic per key with positions, 12 without.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on the
+ * host arguments only, so a captured call may be replayed on new keys in the same buffers.
+ * labsort_sort16_workspace_bytes: 256 bytes for cols <= labsort_segment_tile_keys(); above, the
+ * header (cleared by the call), the count table (rows x 256 x chunks-per-row words, one table for
+ * both passes), the totals, rows * cols * 2 bytes of temporary keys and, with positions,
+ * rows * cols * 4 bytes of temporary positions, each region 256-byte aligned.  It never shrinks as
+ * rows or cols grow, and a workspace sized with positions serves a call without them.  Garbage or
+ * a reused workspace is fine.
+ * labsort_sort16_workspace_status synchronises `stream` and reads the header's first word, as the
+ * row sort's does; nothing on either path sets it, so it returns LABSORT_OK (it exists so that
+ * callers treat every entry alike).
+ * Timing hooks: the kernels of both paths count under LABSORT_K_SEGSORT. */
+size_t labsort_sort16_chunk_keys(void);   /* keys per (row, chunk) workgroup of the long path; info for tests */
+size_t labsort_sort16_workspace_bytes(size_t rows, size_t cols, int with_positions);
+int labsort_sort16_device(const void *d_keys, size_t rows, size_t cols, int descending, int key_type,
+                          void *d_keys_out, uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes,
+                          void *stream);
+int labsort_sort16_workspace_status(const void *d_workspace, void *stream);
 
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +

@@ -30,7 +30,7 @@ OK, ERR_ARG, ERR_HIP, ERR_DEVICE, ERR_PEER = 0, 1, 2, 3, 4
 ALGO = {"radix": 0, "merge": 1, "radix1": 2, "auto": 3}
 # "f32": IEEE-754 order with -0.0 < +0.0 and every NaN equal and last; the device sorts, the segmented
 # sorts and top-k take it, the host-pointer and multi-GPU entries do not (labsort.h)
-# "bf16", "f16": 16-bit elements, the same order at 16 bits; top-k and the row sort alone take them
+# "bf16", "f16": 16-bit elements, the same order at 16 bits; top-k, the row sort and sort16 alone take them
 KEY = {"u32": 0, "i32": 1, "f32": 2, "bf16": 3, "f16": 4}
 DIST = {"u32": 0, "u31": 1, "mod100": 2, "mod1000": 3, "sorted": 4, "reversed": 5, "const": 6, "lowbits": 7}
 KCLASS = {"histogram": 0, "onesweep": 1, "tile_sort": 2, "merge": 3, "partition": 4, "gsweep": 5, "gcopy": 6,
@@ -59,6 +59,8 @@ C_SYMBOLS = [
     "labsort_segments_workspace_status",
     "labsort_topk_workspace_bytes", "labsort_topk_device", "labsort_topk_workspace_status",
     "labsort_sort_rows_workspace_bytes", "labsort_sort_rows_device", "labsort_sort_rows_workspace_status",
+    "labsort_sort16_chunk_keys", "labsort_sort16_workspace_bytes", "labsort_sort16_device",
+    "labsort_sort16_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
 ]
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
@@ -198,6 +200,13 @@ def _load() -> ctypes.CDLL:
         L.labsort_sort_rows_workspace_bytes.argtypes = [sz, sz]
         L.labsort_sort_rows_device.argtypes = [p, sz, sz, i, i, p, p, p, sz, p]
         L.labsort_sort_rows_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_sort16_device"):  # (as labsort_radix_path above)
+        L.labsort_sort16_chunk_keys.restype = sz
+        L.labsort_sort16_chunk_keys.argtypes = []
+        L.labsort_sort16_workspace_bytes.restype = sz
+        L.labsort_sort16_workspace_bytes.argtypes = [sz, sz, i]
+        L.labsort_sort16_device.argtypes = [p, sz, sz, i, i, p, p, p, sz, p]
+        L.labsort_sort16_workspace_status.argtypes = [p, p]
     if hasattr(L, "labsort_key_order_bits"):  # (as labsort_radix_path above)
         for f in ("labsort_key_order_bits", "labsort_key_from_order_bits"):
             getattr(L, f).restype = ctypes.c_uint32
@@ -746,17 +755,61 @@ def sort_rows_workspace_status(workspace, stream=None) -> None:
     _check(lib.labsort_sort_rows_workspace_status(_ptr(workspace), _stream(stream)), "sort_rows (status)")
 
 
+def sort16_chunk_keys() -> int:
+    """Keys per (row, chunk) workgroup of sort16_device's long path."""
+    return int(lib.labsort_sort16_chunk_keys())
+
+
+def sort16_workspace_bytes(rows: int, cols: int, positions: bool = True) -> int:
+    return int(lib.labsort_sort16_workspace_bytes(rows, cols, 1 if positions else 0))
+
+
+def sort16_device(d_keys, rows: int, cols: int, d_keys_out, d_idx_out=None, descending: bool = False,
+                  key: str = "bf16", workspace=None, stream=None) -> None:
+    """sort_rows_device for key="bf16" / "f16" alone, with a path of its own for rows longer than
+    segment_tile_keys(): two radix passes over the 16-bit keys and their positions on a workspace of
+    about 6 bytes per key (2 without positions) instead of top-k's whole-row sort.  Keys and positions
+    are bit-identical to sort_rows_device's.  Workspace and status as sort_rows_device: with a
+    caller-owned `workspace` (>= sort16_workspace_bytes(rows, cols, d_idx_out is not None)) the call
+    stays asynchronous; without one it allocates, synchronises and checks."""
+    workspace, wsb, own = _workspace(workspace, lambda: sort16_workspace_bytes(rows, cols, d_idx_out is not None))
+    _check(lib.labsort_sort16_device(_ptr(d_keys), rows, cols, 1 if descending else 0, KEY[key], _ptr(d_keys_out),
+                                     None if d_idx_out is None else _ptr(d_idx_out), _ptr(workspace), wsb,
+                                     _stream(stream)), "sort16_device")
+    if own:
+        sort16_workspace_status(workspace, stream)
+
+
+def sort16_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream` and check the workspace's status word, as sort_rows_workspace_status
+    (no kernel of sort16_device sets it)."""
+    _check(lib.labsort_sort16_workspace_status(_ptr(workspace), _stream(stream)), "sort16 (status)")
+
+
+def _sort16_routed(rows: int, cols: int, key: str, workspace) -> bool:
+    """Does sort() hand this call to sort16_device?  bfloat16 / float16 rows past the LDS tile, when
+    the caller passed no workspace (one sized by sort_rows_workspace_bytes belongs to
+    sort_rows_device's route, which stays for it)."""
+    return (key in ("bf16", "f16") and workspace is None and cols > segment_tile_keys()
+            and hasattr(lib, "labsort_sort16_device"))  # (an older build loaded through LABSORT_LIBRARY has none)
+
+
 def sort(x, descending: bool = False, workspace=None, stream=None):
     """(values, indices) of every row of x sorted, stably: sort_rows_device with its outputs allocated.
     x: a contiguous 1-D (one row) or 2-D CUDA tensor of dtype int32, float32, bfloat16 or float16;
     values has x's dtype and shape, indices is int32 of the same shape.  TypeError for another dtype,
     a non-contiguous or a CPU tensor, before the device is touched.  Workspace and status as
-    sort_rows_device."""
+    sort_rows_device.  bfloat16 / float16 rows longer than segment_tile_keys() without a caller's
+    workspace are sorted by sort16_device: the same result by contract."""
     import torch
     rows, cols, key = _dense_rows("sort", x)
     values = torch.empty_like(x)
     indices = torch.empty(x.shape, dtype=torch.int32, device=x.device)
-    sort_rows_device(x, rows, cols, values, indices, descending=descending, key=key, workspace=workspace, stream=stream)
+    if _sort16_routed(rows, cols, key, workspace):
+        sort16_device(x, rows, cols, values, indices, descending=descending, key=key, stream=stream)
+    else:
+        sort_rows_device(x, rows, cols, values, indices, descending=descending, key=key, workspace=workspace,
+                         stream=stream)
     return values, indices
 
 

@@ -23,6 +23,7 @@
 #include "host.h"
 #include "lds_class.h"
 #include "segsort.h"
+#include "sort16.h"
 #include "topk.h"
 
 namespace labsort {
@@ -240,28 +241,10 @@ bool rs_lds_path(size_t cols, bool k16, bool idx) {
 
 }  // namespace
 
-}  // namespace labsort
-
-using namespace labsort;
-
-extern "C" {
-
-size_t labsort_sort_rows_workspace_bytes(size_t rows, size_t cols) {
-    if (rows == 0 || cols <= (size_t)SEG_TILE_PAIRS) return SEG_HDR_BYTES;
-    return labsort_topk_workspace_bytes(rows, cols, cols);
-}
-
-int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int descending, int key_type, void *d_keys_out,
-                             uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
-    static_assert(TK_HDR_BYTES == SEG_HDR_BYTES, "one header, one status word, on both paths");
-    if (rows == 0 || cols == 0) return LABSORT_OK;
-    if (const int rc = dense_rows_args(d_keys, rows, cols, cols, key_type, d_keys_out, d_idx_out)) return rc;
+// The LDS path behind the entry's checks (also labsort_sort16_device's short rows, sort16.h)
+int sort_rows_lds(const void *d_keys, size_t rows, size_t cols, int descending, int key_type, void *d_keys_out,
+                  uint32_t *d_idx_out, void *d_ws, hipStream_t s) {
     const bool k16 = key_type_is16(key_type);
-    if (!d_ws || ws_bytes < labsort_sort_rows_workspace_bytes(rows, cols)) return LABSORT_ERR_ARG;
-    if (!rs_lds_path(cols, k16, d_idx_out != nullptr))
-        return labsort_topk_device(d_keys, rows, cols, cols, descending, key_type, d_keys_out, d_idx_out, d_ws, ws_bytes,
-                                   stream);
-    hipStream_t s = as_stream(stream);
     HIP_TRY(launch_zero(d_ws, SEG_HDR_BYTES, s));  // (a kernel: graph-replayable; nothing sets the header after it)
     TimingScope ts(LABSORT_K_SEGSORT, s);
     const int c = seg_class_of(cols);
@@ -283,6 +266,30 @@ int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int d
         else HIP_TRY((launch_rs<RS_K32, false>(c, d_keys, d_keys_out, nullptr, rows, cols, flip, 0u, form, s)));
     }
     return LABSORT_OK;
+}
+
+}  // namespace labsort
+
+using namespace labsort;
+
+extern "C" {
+
+size_t labsort_sort_rows_workspace_bytes(size_t rows, size_t cols) {
+    if (rows == 0 || cols <= (size_t)SEG_TILE_PAIRS) return SEG_HDR_BYTES;
+    return labsort_topk_workspace_bytes(rows, cols, cols);
+}
+
+int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int descending, int key_type, void *d_keys_out,
+                             uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
+    static_assert(TK_HDR_BYTES == SEG_HDR_BYTES, "one header, one status word, on both paths");
+    if (rows == 0 || cols == 0) return LABSORT_OK;
+    if (const int rc = dense_rows_args(d_keys, rows, cols, cols, key_type, d_keys_out, d_idx_out)) return rc;
+    const bool k16 = key_type_is16(key_type);
+    if (!d_ws || ws_bytes < labsort_sort_rows_workspace_bytes(rows, cols)) return LABSORT_ERR_ARG;
+    if (!rs_lds_path(cols, k16, d_idx_out != nullptr))
+        return labsort_topk_device(d_keys, rows, cols, cols, descending, key_type, d_keys_out, d_idx_out, d_ws, ws_bytes,
+                                   stream);
+    return sort_rows_lds(d_keys, rows, cols, descending, key_type, d_keys_out, d_idx_out, d_ws, as_stream(stream));
 }
 
 int labsort_sort_rows_workspace_status(const void *d_ws, void *stream) {

@@ -171,6 +171,15 @@ int labsort_workspace_status(const void *d_workspace, size_t n, int algo, void *
  * the onesweep passes holds the path's counters, bucket offsets and lists at every n.
  * A negative value: -LABSORT_ERR_HIP. */
 int labsort_radix_path(const void *d_workspace, size_t n, void *stream);
+/* Which upfront count the last keys-only LABSORT_ALGO_RADIX sort of n keys on d_workspace ran,
+ * after synchronising `stream`: 0 the full count only (also: host gate closed, key/value sorts,
+ * gathered passes, one tile, no workspace), 1 the hybrid path's lean count only (two counters per
+ * key, the path decided by its last workgroup), 2 the lean count, whose verdict was "classic", and
+ * then the full count.  With the host gate open a fixed sample of the keys chooses which count
+ * runs first; the path taken never depends on that choice.  LABSORT_HY_COUNT (read per call):
+ * unset or =auto the sample chooses, =lean the lean count always runs first, =full the full
+ * count only.  A negative value: -LABSORT_ERR_HIP. */
+int labsort_radix_counting(const void *d_workspace, size_t n, void *stream);
 /* The same for the last labsort_sort_pairs_device(n, algo) on d_workspace. */
 int labsort_pairs_workspace_status(const void *d_workspace, size_t n, int algo, void *stream);
 

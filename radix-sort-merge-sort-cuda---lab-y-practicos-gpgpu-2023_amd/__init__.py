@@ -48,6 +48,7 @@ C_SYMBOLS = [
     "labsort_merge_runs_workspace_bytes", "labsort_merge_runs",
     "labsort_pair_tile_keys", "labsort_pairs_workspace_bytes", "labsort_sort_pairs_device",
     "labsort_workspace_status", "labsort_pairs_workspace_status", "labsort_radix_path",
+    "labsort_radix_counting",
     "labsort_sort_host_multi", "labsort_sort_host_ranks", "labsort_multi_timing", "labsort_multi_last_hip_error",
     "labsort_multi_plan", "labsort_multi_error_detail", "labsort_multi_range_counts",
     "labsort_comm_unique_id", "labsort_comm_init_rccl", "labsort_comm_init_host", "labsort_comm_destroy",
@@ -161,6 +162,8 @@ def _load() -> ctypes.CDLL:
     L.labsort_workspace_status.argtypes = [p, sz, i, p]
     if hasattr(L, "labsort_radix_path"):  # (an older build loaded through LABSORT_LIBRARY for an A/B has none)
         L.labsort_radix_path.argtypes = [p, sz, p]
+    if hasattr(L, "labsort_radix_counting"):  # (as labsort_radix_path above)
+        L.labsort_radix_counting.argtypes = [p, sz, p]
     L.labsort_sort_host_multi.argtypes = [p, sz, i, i]
     L.labsort_sort_host_ranks.argtypes = [p, sz, i, i, p, i]
     L.labsort_multi_timing.argtypes = [ctypes.POINTER(ctypes.c_double), i, ctypes.POINTER(sz)]
@@ -546,6 +549,16 @@ def radix_path(workspace, n: int, stream=None) -> int:
     r = int(lib.labsort_radix_path(_ptr(workspace), n, _stream(stream)))
     if r < 0:
         _check(-r, "radix_path")
+    return r
+
+
+def radix_counting(workspace, n: int, stream=None) -> int:
+    """Synchronise `stream`; which upfront count the last keys-only radix sort of n keys on
+    `workspace` ran: 0 the full count only, 1 the hybrid path's lean count only, 2 the lean count
+    and then the full one (labsort_radix_counting)."""
+    r = int(lib.labsort_radix_counting(_ptr(workspace), n, _stream(stream)))
+    if r < 0:
+        _check(-r, "radix_counting")
     return r
 
 

@@ -178,6 +178,16 @@ uint32_t hybrid_gate(size_t n) {
     return n >= HY_MIN_N && n <= HY_MAX_N ? HY_FAST_GROUP : 0u;
 }
 
+// LABSORT_HY_COUNT (read per call; host gate open only): unset or "auto" a sample of the keys
+// chooses which count runs first, "lean" the hybrid path's own count always, "full" the full
+// count only.  The path taken is the same in all three.
+uint32_t hy_count_mode() {
+    const char *e = std::getenv("LABSORT_HY_COUNT");
+    if (e && !std::strcmp(e, "lean")) return HY_COUNT_LEAN;
+    if (e && !std::strcmp(e, "full")) return HY_COUNT_FULL;
+    return HY_COUNT_AUTO;
+}
+
 bool small_path(size_t n, int algo) { return algo != LABSORT_ALGO_RADIX1 && n <= (size_t)TS_TILE; }
 
 // 8-bit LSD radix of keys (vi == vo == nullptr) or (key, payload) pairs: the keys' segmented
@@ -211,9 +221,14 @@ int sort_radix8(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *
     // classic path the finish's do.
     const uint32_t hy_limit = vi ? 0u : hybrid_gate(n);
     const bool hyb = hy_limit != 0u;
-    const HyCounts hc{reinterpret_cast<uint32_t *>(ws + L.off_hps2), reinterpret_cast<uint32_t *>(ws + L.off_top14), hy_limit};
+    const HyCounts hc{reinterpret_cast<uint32_t *>(ws + L.off_hps2), reinterpret_cast<uint32_t *>(ws + L.off_top14), hy_limit,
+                      err, hy_count_mode()};
     {
+        // host gate open: two counting launches, of which one counts -- the lean count of the
+        // hybrid path's fields with the rule's verdict, then the full count, which returns at once
+        // after a hybrid verdict (hist_lean.hip; both under the one timing scope)
         TimingScope ts(LABSORT_K_HISTOGRAM, s);
+        if (hyb) HIP_TRY(launch_hist_lean(ki, n, flip, joint, s, hc));
         HIP_TRY(launch_hist_seg(ki, n, flip, hps, joint, s, hyb ? &hc : nullptr));
     }
     // the look-back clear rides in the plan launch (k_plan8's workgroups 1..)
@@ -572,6 +587,22 @@ int labsort_radix_path(const void *d_ws, size_t n, void *stream) {
     }
     if (e != hipSuccess) return -fail_hip(e);
     return hybrid ? 1 : 0;
+}
+
+int labsort_radix_counting(const void *d_ws, size_t n, void *stream) {
+    hipStream_t s = as_stream(stream);
+    uint32_t ran[2] = {0, 0};  // HY_CTL_LEAN, HY_CTL_FULL
+    // (no workspace; one tile, the gathered passes: no counting launches)
+    if (n == 0 || !d_ws || small_path(n, LABSORT_ALGO_RADIX) || use_gather(n) || n > RADIX_MAX_N) return 0;
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) {
+        static_assert(HY_CTL_FULL == HY_CTL_LEAN + 1, "read together");
+        const size_t at = radix_layout(n, 8, OSP_TILE).off_err + HY_CTL_LEAN * 4;
+        e = hipMemcpyAsync(ran, static_cast<const char *>(d_ws) + at, 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) return -fail_hip(e);
+    return ran[0] ? (ran[1] ? 2 : 1) : 0;
 }
 
 int labsort_pairs_workspace_status(const void *d_ws, size_t n, int algo, void *stream) {

@@ -175,7 +175,34 @@ struct HyCounts {
     uint32_t *hps2;   // digit-2 histogram of each position segment
     uint32_t *top14;  // histogram of the top HY_TOP_BITS bits
     uint32_t limit;   // the plan takes the hybrid path up to this largest top14 count (<= HY_MAX_BUCKET)
+    uint32_t *ctl;    // the workspace's zeroed header: HY_CTL_* words (nullptr: no lean count in this sequence)
+    uint32_t mode;    // HY_COUNT_*
 };
+// The hybrid path's own count (hist_lean.hip) runs before the full one and leaves its verdict in
+// the header block that starts with the error word; the status functions read word 0 only.
+constexpr uint32_t HY_CTL_TICKET = 1;   // workgroups of k_hist_lean that have flushed their counts
+constexpr uint32_t HY_CTL_NAND = 2;     // OR of ~(key ^ flip): the complement of the keys' AND (zero-initialised)
+constexpr uint32_t HY_CTL_OR = 3;       // OR of key ^ flip
+constexpr uint32_t HY_CTL_VERDICT = 4;  // 0: the lean count did not run; else HY_VERDICT_*
+constexpr uint32_t HY_CTL_LEAN = 5;     // 1: k_hist_lean counted (labsort_radix_counting)
+constexpr uint32_t HY_CTL_FULL = 6;     // 1: k_hist_seg<true> counted
+constexpr uint32_t HY_VERDICT_CLASSIC = 1, HY_VERDICT_HYBRID = 2;
+// LABSORT_HY_COUNT (read per call): which count runs first -- chosen from a sample of the keys,
+// the lean one always ("hybrid likely"), the full one always (as before the lean count existed)
+constexpr uint32_t HY_COUNT_AUTO = 0, HY_COUNT_LEAN = 1, HY_COUNT_FULL = 2;
+// replicas of the lean count's digit-2 counters: 32 (96 KB of LDS with the 64 KB of top14
+// counters, one workgroup per CU) or 16 (80 KB, two per CU); A/B in profiles/lean_count_ab.txt
+#ifndef LABSORT_HY_LEAN_SL
+#define LABSORT_HY_LEAN_SL 32
+#endif
+constexpr int HY_LEAN_SL = LABSORT_HY_LEAN_SL;
+// workgroups per position segment of the upfront counts: HS_BPS at large n; at small n at least
+// HS_MIN_KEYS keys each, since every workgroup flushes ~13 K counters with global atomics
+// (512 workgroups at 2^20: 97 us, contended on the same 48 KB)
+inline uint32_t hist_seg_bps(size_t n) {
+    const size_t bps = n / ((size_t)NSEG * HS_MIN_KEYS);
+    return (uint32_t)(bps < 1 ? 1 : bps > (size_t)HS_BPS ? (size_t)HS_BPS : bps);
+}
 
 struct Bufs {
     uint32_t *p[3];  // IN, OUT, TMP
@@ -199,6 +226,9 @@ hipError_t launch_onesweep(Bufs b, const Plan *plan, int pass, int bits, size_t 
 // hy (or nullptr): the histogram also counts the hybrid path's fields and the plan may choose it
 hipError_t launch_hist_seg(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *hps, uint32_t *joint,
                            hipStream_t s, const HyCounts *hy = nullptr);
+// the hybrid path's own count and verdict (hist_lean.hip); launch_hist_seg with hy.ctl set follows it
+hipError_t launch_hist_lean(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *joint, hipStream_t s,
+                            const HyCounts &hy);
 hipError_t launch_plan8(const uint32_t *hps, const uint32_t *joint, size_t n, int in_is_out, Plan *plan,
                         SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, hipStream_t s,
                         const HyCounts *hy = nullptr);

@@ -13,7 +13,8 @@
 //   k_hist_seg        letra.pdf's global "totalFalses" generalised to 8-bit digits:
 //                     digit 0 per position segment and the joint fields that size the
 //                     later passes' segments, in one read of the keys (k_histogram:
-//                     the plain form); k_plan8 turns them into every pass's plan.
+//                     the plain form); k_plan8 turns them into every pass's plan.  (The hybrid
+//                     path's own count, k_hist_lean, is in hist_lean.hip.)
 //   k_onesweep_p      one persistent LSD pass (the default radix above 2^25 keys): lane-
 //                     ordered LDS-atomic rank, segmented decoupled look-back for the
 //                     global offsets, LDS reorder, coalesced scatter; <true>: key/value.
@@ -210,6 +211,17 @@ __global__ __launch_bounds__(HIST_BLOCK) void k_hist_seg(const uint32_t *__restr
     __shared__ uint32_t h[256 * SL];
     __shared__ uint32_t hj[NJ * JF];
     __shared__ uint32_t ht[HY ? HY_TOP : 1];
+    if constexpr (HY) {
+        // The second counting slot (hist_lean.hip ran before, in this stream): nothing to do when
+        // the lean count's verdict is hybrid.  No verdict: its sample said "hybrid unlikely" and
+        // it counted nothing.  A classic verdict: mispredicted, so every field is counted here
+        // after all; the stored verdict stands, and the top14 / hps2 counts, now doubled, are
+        // read by nobody on the classic path.
+        if (hy.ctl) {
+            if (hy.ctl[HY_CTL_VERDICT] == HY_VERDICT_HYBRID) return;
+            if (blockIdx.x == 0 && threadIdx.x == 0) hy.ctl[HY_CTL_FULL] = 1u;
+        }
+    }
     for (int i = threadIdx.x; i < 256 * SL; i += HIST_BLOCK) h[i] = 0u;
     for (int i = threadIdx.x; i < NJ * JF; i += HIST_BLOCK) hj[i] = 0u;
     if constexpr (HY) {
@@ -463,8 +475,10 @@ __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps,
     if (t < 4) triv[t] = 0;
     if (t == 0) max14 = 0u;
     __syncthreads();
-    // hybrid path (hy.top14 != nullptr: the host gate admits it): the largest top-14-bit count
-    if (hy.top14) {
+    // hybrid path (hy.top14 != nullptr: the host gate admits it): the largest top-14-bit count,
+    // unless the lean count (hist_lean.hip) ran and left the rule's verdict
+    const uint32_t verdict = hy.ctl ? hy.ctl[HY_CTL_VERDICT] : 0u;
+    if (hy.top14 && verdict == 0u) {
         uint32_t m = 0;
         for (uint32_t i = t; i < (uint32_t)HY_TOP; i += 256u) m = max(m, hy.top14[i]);
         atomicMax(&max14, m);
@@ -487,7 +501,10 @@ __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps,
     // fits one workgroup's LDS sort: a bucket is part of a top-14-bit group, so the largest
     // group bounds it (conservative, never wrong).  Digits 0 and 1 then count as trivial here:
     // the finish sorts them, bucket by bucket, after the pass on digit 3.
-    const bool hybrid = hy.top14 && !triv[0] && !triv[1] && max14 <= min(hy.limit, HY_MAX_BUCKET);
+    // (After a lean count with a hybrid verdict only hps2, top14, the third joint field and the
+    // digit-2 totals are there; digits 0 and 1 read as all-zero histograms, which is "varies".)
+    const bool hybrid = verdict ? verdict == HY_VERDICT_HYBRID
+                                : hy.top14 && !triv[0] && !triv[1] && max14 <= min(hy.limit, HY_MAX_BUCKET);
     __syncthreads();
     if (hybrid && t < 2) triv[t] = 1;
     __syncthreads();
@@ -1778,11 +1795,7 @@ hipError_t launch_onesweep_p(Bufs b, const Plan *plan, int pass, size_t n, uint3
 hipError_t launch_hist_seg(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *hps, uint32_t *joint,
                            hipStream_t s, const HyCounts *hy) {
     if (n == 0) return hipSuccess;
-    // workgroups per position segment: HS_BPS at large n; at small n at least
-    // HS_MIN_KEYS keys each, since every workgroup flushes ~13 K counters with global
-    // atomics (512 workgroups at 2^20: 97 us, contended on the same 48 KB)
-    size_t bps = n / ((size_t)NSEG * HS_MIN_KEYS);
-    bps = bps < 1 ? 1 : bps > (size_t)HS_BPS ? (size_t)HS_BPS : bps;
+    const uint32_t bps = hist_seg_bps(n);
     if (hy) k_hist_seg<true><<<NSEG * (unsigned)bps, HIST_BLOCK, 0, s>>>(keys, n, flip, hps, joint, (uint32_t)bps, *hy);
     else k_hist_seg<false><<<NSEG * (unsigned)bps, HIST_BLOCK, 0, s>>>(keys, n, flip, hps, joint, (uint32_t)bps, HyCounts{});
     return hipGetLastError();

@@ -243,7 +243,8 @@ int sort_radix8(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *
     }
     if (hyb) {
         TimingScope ts(LABSORT_K_SEGSORT, s);
-        HIP_TRY(launch_hybrid_finish(plan, b, n, flip, hc.top14, reinterpret_cast<uint32_t *>(ws + L.off_fin_hdr),
+        HIP_TRY(launch_hybrid_finish(plan, b, n, flip, hist, sps + 3, lookback + (size_t)3 * L.ntiles * L.R, L.ntiles, err,
+                                     reinterpret_cast<uint32_t *>(ws + L.off_fin_hdr),
                                      reinterpret_cast<uint32_t *>(ws + L.off_fin_off),
                                      reinterpret_cast<uint32_t *>(ws + L.off_fin_lists), s));
     }

@@ -120,10 +120,12 @@ static_assert(SEG_WAVE3_KEYS < HY_BLOCK_KEYS && HY_BLOCK_KEYS < SEG_TILE_KEYS, "
 static_assert(HY_FAST_GROUP == 4u * HY_BLOCK_KEYS, "the default gate's group bound: four block-class buckets");
 // hdr: SEG_HDR_BYTES cleared since the last finish; off: HY_BUCKETS + 1 words; lists: SEG_CLASSES
 // lists of HY_BUCKETS words.  Bucket offsets, class lists, the five class kernels: seven
-// launches, host arguments only.  top14: the histogram of the keys' top 14 bits, which brackets
-// each bucket's boundary search.
-hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t flip, const uint32_t *top14, uint32_t *hdr,
-                                uint32_t *off, uint32_t *lists, hipStream_t s);
+// launches, host arguments only.  The offsets come from what the digit-3 pass left: hist, the four
+// digits' totals (k_plan8's hist_out); sp3 and lookback3, that pass's SegPlan and look-back region
+// of nslots slots; err, the radix workspace's error word, set when that region is unfinished.
+hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t flip, const uint32_t *hist, const SegPlan *sp3,
+                                const uint32_t *lookback3, size_t nslots, uint32_t *err, uint32_t *hdr, uint32_t *off,
+                                uint32_t *lists, hipStream_t s);
 
 // workspace of the general path's inner pair sorts of n pairs (top-k's single-row sort uses the same)
 size_t seg_inner_bytes(size_t n);

@@ -9,6 +9,7 @@
 //                LSD passes (4, 8 or 16 keys per lane)
 //   k_seg_block  block and tile classes: k_tile_sort's LDS passes on a [start, end) range,
 //                one workgroup per segment, grid-stride over the class list
+//   k_fin_edges  the hybrid radix sort's finish: the bucket offsets, from the digit-3 pass's look-back words
 //   k_fin_block  (fin_block.h) the block class of the hybrid radix sort's finish
 //   k_seg_ids, k_seg_gather, k_seg_err_acc   the general path's glue around the pair sorts
 // k_seg_wave and k_seg_block live in seg_kernels.h: this file compiles their integer-key
@@ -196,67 +197,101 @@ hipError_t launch_seg_lds_classes(size_t max_len, bool pairs, const uint32_t *in
 // the hybrid radix sort's finish
 // ---------------------------------------------------------------------------------
 namespace {
-constexpr int FB_BLOCK = 1024;  // buckets per workgroup of k_fin_bounds
+constexpr int FE_BLOCK = 1024, FE_W = FE_BLOCK / WAVE, FE_KPT = OSP_TILE / FE_BLOCK;
+static_assert(FE_KPT * FE_BLOCK == OSP_TILE && HY_BUCKETS == 256u * 256u, "one tile per boundary, one workgroup per digit-2 value");
 
-// off[q] = first position whose key's top 16 bits are >= q, for the HY_BUCKETS buckets q, and
-// off[HY_BUCKETS] = n.  The keys are ordered by their top 16 bits.  Bucket q lies in the range of
-// its top-14-bit group q >> 2, which the exclusive scan of top14 gives: at most HY_MAX_BUCKET
-// keys when the plan chose the hybrid path, so the search takes 15 steps, not 28.
-__global__ __launch_bounds__(FB_BLOCK) void k_fin_bounds(const Plan *__restrict__ plan, Bufs bufs, uint32_t n, uint32_t flip,
-                                                         const uint32_t *__restrict__ top14, uint32_t *__restrict__ off) {
-    constexpr uint32_t GPB = FB_BLOCK / 4;  // top-14-bit groups per workgroup
-    __shared__ uint32_t wsum[FB_BLOCK / WAVE];
-    __shared__ uint32_t gstart[GPB + 1];
+// Where the digit-3 pass put, for each digit-3 value d (thread d < 256; the other threads' result
+// means nothing), the first key of digit d that lay at or after position P of its input: the
+// segment's base, the inclusive prefix the tile before P's tile published in the pass's look-back
+// region (every slot holds LB_INC | prefix once the pass is through), and the keys of digit d in
+// P's tile before P, counted here.  P's segment is the last one that starts at or before P, its tile
+// by k_onesweep_p's tile_range: aligned to OSP_TILE but for a segment's first.  A look-back word
+// without LB_INC, or a slot outside the region, sets `bad`.  wh: FE_W * 256 words of LDS.
+__device__ uint32_t fin_edge_at(uint32_t P, const uint32_t *__restrict__ keys, uint32_t flip, const SegPlan *__restrict__ sp,
+                                const uint32_t *__restrict__ lb, uint32_t nslots, uint32_t *wh, bool &bad) {
+    const uint32_t tid = threadIdx.x, wid = tid >> 6;
+    uint32_t sg = 0;
+    for (uint32_t s = 1; s < (uint32_t)NSEG; ++s) sg = sp->start[s] <= P ? s : sg;  // (the starts ascend)
+    const uint32_t s0 = sp->start[sg], a0 = s0 - s0 % (uint32_t)OSP_TILE;
+    const uint32_t l = (P - a0) / (uint32_t)OSP_TILE, beg = l ? a0 + l * (uint32_t)OSP_TILE : s0;
+    for (uint32_t i = tid; i < (uint32_t)(FE_W * 256); i += FE_BLOCK) wh[i] = 0u;
+    uint32_t k[FE_KPT];
+#pragma unroll
+    for (int j = 0; j < FE_KPT; ++j) {
+        const uint32_t i = beg + (uint32_t)j * FE_BLOCK + tid;
+        k[j] = i < P ? keys[i] : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < FE_KPT; ++j)
+        if (beg + (uint32_t)j * FE_BLOCK + tid < P) atomicAdd(&wh[wid * 256u + ((k[j] ^ flip) >> 24)], 1u);
+    __syncthreads();
+    if (tid >= 256u) return 0u;
+    uint32_t r = sp->base[sg * 256u + tid];
+#pragma unroll
+    for (int w = 0; w < FE_W; ++w) r += wh[(uint32_t)w * 256u + tid];
+    if (l) {
+        const uint32_t slot = sp->tpre[sg] + l - 1u;
+        const uint32_t w = slot < nslots ? lb[(size_t)slot * 256u + tid] : 0u;
+        if ((w & LB_INC) == 0u) bad = true;
+        r += w & LB_VAL;
+    }
+    return r;
+}
+
+// The finish's bucket offsets, from what the digit-3 pass left behind: off[q] = first position whose
+// key's top 16 bits are >= q for the HY_BUCKETS buckets q = (d3 << 8) | d2, and off[HY_BUCKETS] = n.
+// The digit-3 pass's input is ordered by digit 2 and the scatter is stable, so bucket (d3, d2) starts
+// where the pass put the first key of digit d3 at or after input position S2[d2], the number of keys
+// with a smaller digit 2 (fin_edge_at).  One workgroup per d2, thread d3 < 256 writes one offset;
+// hist: the four digits' totals as k_plan8 leaves them.  Digit 3 constant (plan->src[3] is SKIP,
+// no pass ran, its SegPlan and look-back region are not read): the offsets are 0 below that digit,
+// S2[d2] at it and n above, which is the digit-3 totals' exclusive scan, plus S2[d2] at the digit.
+// An unfinished look-back word sets both error words, the radix workspace's (err) and the
+// finish's (hdr), which every class kernel reads first; no offset is written from it.
+// (The workgroup also finding the offsets of d2 + 1 and appending its 256 buckets to the class lists,
+// in place of the k_seg_bin launch: 12.6 us against 9.2 + 6.3, but the lists then run in steps of 256
+// buckets and k_fin_block took 593 us against 587; harness/exp/fin_edges_fused_bin.patch.)
+__global__ __launch_bounds__(FE_BLOCK) void k_fin_edges(const Plan *__restrict__ plan, Bufs bufs, uint32_t n, uint32_t flip,
+                                                        const uint32_t *__restrict__ hist, const SegPlan *__restrict__ sp,
+                                                        const uint32_t *__restrict__ lb, uint32_t nslots, uint32_t *err,
+                                                        uint32_t *hdr, uint32_t *__restrict__ off) {
+    __shared__ uint32_t wh[FE_W * 256];
+    __shared__ uint32_t wsum[4];
+    __shared__ uint32_t s2;
     if (plan->hybrid == 0u) return;
-    const uint32_t *__restrict__ keys = bufs.p[plan->fin_src];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-    const uint32_t g0 = blockIdx.x * GPB;  // this workgroup's first group
-    // keys in the groups before g0, then the exclusive scan of this workgroup's groups
-    uint32_t before = 0u;
-    for (uint32_t i = tid; i < g0; i += FB_BLOCK) before += top14[i];
-    const uint32_t mine = tid < GPB ? top14[g0 + tid] : 0u;
-    uint32_t x = mine, tot = before;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(x, o);
-        if (lane >= (uint32_t)o) x += t;
+    const uint32_t tid = threadIdx.x, d2 = blockIdx.x;
+    const uint32_t h2 = tid < 256u ? hist[2 * 256 + tid] : 0u;
+    const uint32_t x2 = block_excl_scan<FE_BLOCK, 256>(h2, wsum);
+    if (tid == d2) s2 = min(x2, n);
+    __syncthreads();
+    const uint32_t P = s2;
+    uint32_t o;
+    bool bad = false;
+    if (plan->src[3] == SEL_SKIP) {
+        const uint32_t h3 = tid < 256u ? hist[3 * 256 + tid] : 0u;
+        o = block_excl_scan<FE_BLOCK, 256>(h3, wsum) + (h3 == n ? P : 0u);
+    } else {
+        // (the pass's input, which it leaves as it was on every buffer plan)
+        o = fin_edge_at(P, bufs.p[plan->src[3]], flip, sp, lb, nslots, wh, bad);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
-    if (lane == 63u) wsum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0u;  // counts of the waves before this one (the groups sit in waves 0-3)
-    for (uint32_t w = 0; w < wid && w < GPB / WAVE; ++w) pre += wsum[w];
-    __syncthreads();
-    if (lane == 0u) wsum[wid] = tot;
-    __syncthreads();
-    uint32_t base = 0u;
-    for (uint32_t w = 0; w < (uint32_t)(FB_BLOCK / WAVE); ++w) base += wsum[w];
-    if (tid < GPB) {
-        gstart[tid] = base + pre + x - mine;
-        if (tid == GPB - 1u) gstart[GPB] = base + pre + x;
+    if (tid >= 256u) return;
+    if (bad) {
+        atomicOr(err, 1u);
+        atomicOr(hdr, 1u);
+        return;
     }
-    __syncthreads();
-    const uint32_t q = blockIdx.x * FB_BLOCK + tid;  // bucket
-    uint32_t lo = min(gstart[tid >> 2], n), hi = min(gstart[(tid >> 2) + 1u], n);
-    // (seven probes per round instead of one, 4 + 3 dependent rounds instead of 15, measured slower:
-    // 78 us against 45 at 2^28 -- the probes are scattered single-word loads over 1 GiB, and their
-    // number, not the length of the chain, is what costs)
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (((keys[mid] ^ flip) >> 16) >= q) hi = mid;
-        else lo = mid + 1u;
-    }
-    off[q] = lo;
+    const uint32_t q = (tid << 8) | d2;
+    off[q] = o;
     if (q == HY_BUCKETS - 1u) off[HY_BUCKETS] = n;
 }
 }  // namespace
 
-hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t flip, const uint32_t *top14, uint32_t *hdr,
-                                uint32_t *off, uint32_t *lists, hipStream_t s) {
-    static_assert(HY_BUCKETS % FB_BLOCK == 0 && HY_TOP * 4 == (int)HY_BUCKETS, "four buckets per top-14-bit group");
+hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t flip, const uint32_t *hist, const SegPlan *sp3,
+                                const uint32_t *lookback3, size_t nslots, uint32_t *err, uint32_t *hdr, uint32_t *off,
+                                uint32_t *lists, hipStream_t s) {
     const size_t stride = HY_BUCKETS;
-    k_fin_bounds<<<HY_BUCKETS / FB_BLOCK, FB_BLOCK, 0, s>>>(plan, b, (uint32_t)n, flip, top14, off);
+    k_fin_edges<<<256, FE_BLOCK, 0, s>>>(plan, b, (uint32_t)n, flip, hist, sp3, lookback3, (uint32_t)nslots, err, hdr, off);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // every bucket is written (the finish may read TMP or IN and write OUT): one-key buckets are listed

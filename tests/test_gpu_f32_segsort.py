@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import f32_model as M
+import sort_sweep_model as S
 
 pytestmark = pytest.mark.gpu
 
@@ -200,6 +201,49 @@ def test_rejected_offsets(ls, torch_gpu, path, pairs):
     M.assert_keys(ok.cpu().numpy().view(np.uint32), ek)
     if pairs:
         np.testing.assert_array_equal(ov.cpu().numpy().view(np.uint32), ev)
+
+
+@pytest.mark.parametrize("inplace", [False, True])
+@pytest.mark.parametrize("pairs", [False, True])
+def test_digit_masks(ls, torch_gpu, pairs, inplace):
+    """The pass-skip logic of every class kernel: segments of 1 to 9000 keys and of the tile's length,
+    each length once per set of differing digits (16 masks) and per variant of
+    sort_sweep_model.digit_mask_rows (digits random per key, two values one bit apart, all keys equal
+    but the first, the last or one in the middle; at the tile's length three of the five).  The
+    payloads are the positions, so equal keys must keep their order whichever passes ran."""
+    T = tile(ls, pairs)
+    keys, offs, labels = S.mask_segments("f32", T, 0xF5F0)
+    n = keys.size
+    assert n < 4_000_000 and max(length for length, _, _ in labels) == T
+    gk, gv = run(ls, torch_gpu, keys, offs, T, positions(n) if pairs else None, inplace)
+    ek, ev = M.segments_expected(keys, [int(o) for o in offs], positions(n) if pairs else None)
+    wrong = gk != ek  # (no NaN among these keys)
+    if pairs:
+        wrong |= gv != ev
+    if wrong.any():
+        s = int(np.searchsorted(offs.astype(np.int64), int(np.flatnonzero(wrong)[0]), side="right")) - 1
+        raise AssertionError(f"pairs={pairs} inplace={inplace}: {int(wrong.sum())} elements differ, the first in segment {s}: "
+                             f"{labels[s][0]} keys, mask {labels[s][1]:#x} {labels[s][2]}")
+    M.assert_keys(gk, ek, f"pairs={pairs} inplace={inplace}")
+
+
+@pytest.mark.parametrize("seed", S.F32SEG_SEEDS)
+def test_seeded_sweep(ls, torch_gpu, seed):
+    """60 cases per seed (sort_sweep_model.f32_segment_sweep_cases): up to 2^17 keys cut at random places,
+    empty segments among them, few long segments in every third case; max_segment_keys the true
+    maximum or 0 (both paths); keys or pairs with random payloads; in place or out of place; every
+    segment from its own generator (digit masks, heavy ties with NaNs, NaNs only, sorted ...)."""
+    cases = list(S.f32_segment_sweep_cases(seed, ls.segment_tile_keys(), ls.segment_pair_tile_keys()))
+    failures, hit = [], {}
+    for i, c in enumerate(cases):
+        what = f"{c['path']} {'pairs' if c['pairs'] else 'keys'}"
+        hit[what] = hit.get(what, 0) + 1
+        try:
+            check(ls, torch_gpu, c["keys"], c["offs"], c["m"], c["vals"], c["inplace"])
+        except AssertionError as err:
+            failures.append(f"seed {seed} case {i}: {c['tag']}: {str(err).strip().splitlines()[0]}")
+    print(f"seed {seed}: {dict(sorted(hit.items()))}")
+    assert not failures, failures
 
 
 def _graph_lengths(rng, n, nseg, T):

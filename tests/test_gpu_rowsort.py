@@ -1,7 +1,8 @@
 """labsort_sort_rows_device on the GPU: whole output arrays (keys and positions) against the numpy
 models of the contract (tests/rowsort_model.py over f16_model / f32_model: the stable argsort of
 u(key)), for the five key types, both directions, with and without positions, across the edges of
-the LDS classes and of the two tiles, and on the long path behind them.  Keys compare bit-exact
+the LDS classes and of the two tiles, on the long path behind them, on rows whose keys differ in
+every chosen set of digits (tests/sort_sweep_model.py) and in a seeded sweep.  Keys compare bit-exact
 except that a NaN only has to be a NaN, positions exactly.  Every call runs on a workspace filled
 with 0xFF and on outputs filled with a pattern with a guard element on each side, is followed by
 the status call, and must leave its input as it was."""
@@ -10,6 +11,7 @@ import pytest
 
 import f16_model as M
 import rowsort_model as R
+import sort_sweep_model as S
 
 pytestmark = pytest.mark.gpu
 
@@ -283,6 +285,70 @@ def test_graph_replay(ls, torch_gpu, kind):
         ek, ei = R.expected(x, True, kind)
         R.assert_keys(ko.view(sdt).cpu().numpy().view(R.wdtype(kind)), ek, kind, dist)
         np.testing.assert_array_equal(io.cpu().numpy().view(np.uint32), ei, err_msg=dist)
+
+
+@KINDS
+@pytest.mark.parametrize("cols", [33, 64, 65, 200, 400, 900, 3000, 9000, 16384, 32768])
+def test_digit_masks(ls, torch_gpu, cols, kind):
+    """The pass-skip logic of every class: one matrix whose rows run through every set of differing
+    digits (16 masks of four digits, 4 of a packed word's two) times every variant of
+    sort_sweep_model.digit_mask_rows: digits random per key, digits of two values one bit apart, and
+    all keys equal but the first, the last (beside the padding) or one in the middle (in another
+    wave's stripe).  A kernel that skips a pass it needs, or lets a packed word's position half
+    decide, orders a row wrongly; with only some passes run, equal keys must still come out in
+    position order.  32768: the calls that stay in LDS at that length."""
+    torch = torch_gpu
+    x, labels = S.mask_matrix(kind, cols, 0x5048 + cols)
+    assert x.shape[0] == (20 if R.is16(kind) else 80)
+    np.testing.assert_array_equal(S.mask_of(R.u_of(x, kind)), [m for m, _ in labels])
+    idx_forms = [w for w in (True, False) if lds_path(ls, cols, kind, w)]
+    assert idx_forms == ([True, False] if R.is16(kind) or cols <= 16384 else [False])
+    offs = [(0, 0), (1, 1)] if R.is16(kind) else [(0, 0)]
+    for desc in BOTH:
+        exp = R.expected(x, desc, kind)
+        for with_idx in idx_forms:
+            for in_off, out_off in offs:
+                gk, gi = run(ls, torch, x, desc, kind, with_idx=with_idx, in_off=in_off, out_off=out_off)
+                msg = f"{kind} cols={cols} descending={desc} idx={with_idx} offsets=({in_off}, {out_off})"
+                # (no NaN among these keys: words compare as they are; the first wrong row by its name)
+                bad = (gk != exp[0]).any(axis=1) | ((gi != exp[1]).any(axis=1) if with_idx else False)
+                if bad.any():
+                    r = int(np.flatnonzero(bad)[0])
+                    raise AssertionError(f"{msg}: {int(bad.sum())} rows differ, the first is row {r}: "
+                                         f"mask {labels[r][0]:#x} {labels[r][1]}")
+                R.assert_keys(gk, exp[0], kind, msg)
+                if with_idx:
+                    np.testing.assert_array_equal(gi, exp[1], err_msg=f"positions {msg}")
+                    S.assert_ties_in_position_order(x, gi, kind, desc, msg)
+
+
+@pytest.mark.parametrize("seed", S.ROWSORT_SEEDS)
+def test_seeded_sweep(ls, torch_gpu, monkeypatch, seed):
+    """40 cases per seed (sort_sweep_model.rowsort_sweep_cases): the five key types, 1 to 48 rows, cols on
+    the class and tile edges, log-uniform below the tile and past it, both directions, with and
+    without positions, the grid form unset or forced, 16-bit matrices at either 2-byte phase, every
+    row from its own generator (digit masks, ties, NaNs, sorted, all equal ...).  One workspace per
+    seed, filled with 0xFF once and never cleared between the cases."""
+    torch = torch_gpu
+    e = ls.segment_class_edges(False)
+    cases = list(S.rowsort_sweep_cases(seed, e[:-1], ls.segment_tile_keys(), ls.segment_pair_tile_keys()))
+    size = max(ls.sort_rows_workspace_bytes(c["rows"], c["cols"]) for c in cases)
+    ws = torch.full((size,), 0xFF, dtype=torch.uint8, device="cuda")
+    failures, paths = [], {}
+    for i, c in enumerate(cases):
+        assert (c["path"] != "long") == lds_path(ls, c["cols"], c["kind"], c["with_idx"]), c["tag"]
+        paths[c["path"]] = paths.get(c["path"], 0) + 1
+        if c["grid"] is None:
+            monkeypatch.delenv("LABSORT_ROWSORT_GRID", raising=False)
+        else:
+            monkeypatch.setenv("LABSORT_ROWSORT_GRID", c["grid"])
+        try:
+            check(ls, torch, c["x"], c["descending"], c["kind"], ws=ws, with_idx=c["with_idx"], in_off=c["in_off"],
+                  out_off=c["out_off"])
+        except AssertionError as err:
+            failures.append(f"seed {seed} case {i}: {c['tag']}: {str(err).strip().splitlines()[0]}")
+    print(f"seed {seed}: classes and paths {dict(sorted(paths.items()))}")
+    assert not failures, failures
 
 
 def to_torch(x, kind, torch):

@@ -6,6 +6,8 @@ between neighbouring segments shows.  Every case ends with segments_workspace_st
 import numpy as np
 import pytest
 
+import sort_sweep_model as S
+
 pytestmark = pytest.mark.gpu
 
 PATTERN = 0x5A5A5A5A
@@ -373,6 +375,31 @@ def test_segments_seeded_stress(ls, torch_gpu):
         np.testing.assert_array_equal(gk, ek, err_msg=tag)
         if pairs:
             np.testing.assert_array_equal(gv, ev, err_msg=tag)
+
+
+# ---- 10b. the pass-skip logic: every set of differing digits ---------------------------------
+@pytest.mark.parametrize("pairs", [False, True])
+@pytest.mark.parametrize("key", ["u32", "i32"])
+def test_digit_masks(ls, torch_gpu, key, pairs):
+    """Segments of 1 to 9000 keys and of the tile's length, each length once per set of differing
+    digits (16 masks) and per variant of sort_sweep_model.digit_mask_rows (digits random per key, two
+    values one bit apart, all keys equal but the first, the last or one in the middle; at the tile's
+    length three of the five): k_seg_wave's own copy of the skip test and the block kernels'.  The
+    payloads are the global index, so equal keys must keep their order whichever passes ran."""
+    T = tile(ls, pairs)
+    keys, offs, labels = S.mask_segments(key, T, 0x5E60)
+    n = keys.size
+    assert n < 4_000_000 and max(length for length, _, _ in labels) == T
+    vals = np.arange(n, dtype=np.uint32) if pairs else None
+    gk, gv = run(ls, torch_gpu, keys, offs, T, key, vals)
+    ek, ev = expect(keys, offs, key, vals)
+    wrong = gk != ek
+    if pairs:
+        wrong |= gv != ev
+    if wrong.any():
+        s = int(np.searchsorted(offs.astype(np.int64), int(np.flatnonzero(wrong)[0]), side="right")) - 1
+        raise AssertionError(f"{key} pairs={pairs}: {int(wrong.sum())} elements differ, the first in segment {s}: "
+                             f"{labels[s][0]} keys, mask {labels[s][1]:#x} {labels[s][2]}")
 
 
 # ---- 11. timing hook -----------------------------------------------------------------------

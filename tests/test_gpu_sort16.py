@@ -10,6 +10,7 @@ import pytest
 
 import f16_model as M
 import rowsort_model as R
+import sort_sweep_model as S
 
 pytestmark = pytest.mark.gpu
 
@@ -171,6 +172,40 @@ def test_agrees_with_the_row_sort(ls, torch_gpu, shape, kind):
         k2, i2 = check(ls, torch_gpu, x, desc, kind, exp=exp[desc], entry="rows")
         np.testing.assert_array_equal(k1, k2)
         np.testing.assert_array_equal(i1, i2)
+
+
+@pytest.mark.parametrize("seed", S.SORT16_SEEDS)
+def test_seeded_sweep(ls, torch_gpu, seed):
+    """16 cases per seed (sort_sweep_model.sort16_sweep_cases): both key types, 1 to 4 long rows of up to
+    6 C keys, half of the widths a whole number of chunks +-1, both directions, with and without
+    positions, either 2-byte phase of input and output, through labsort_sort16_device or through
+    labsort_sort_rows_device (whose outputs must then equal the first entry's bit for bit), every row
+    from its own generator: among them rows whose images differ in one byte only, so that one radix
+    pass puts whole chunks into one bin.  One workspace per seed, filled with 0xFF once and never
+    cleared between the cases."""
+    torch = torch_gpu
+    C = ls.sort16_chunk_keys()
+    cases = list(S.sort16_sweep_cases(seed, C, ls.segment_tile_keys()))
+    size = max(max(ls.sort16_workspace_bytes(c["rows"], c["cols"], True), ls.sort_rows_workspace_bytes(c["rows"], c["cols"]))
+               for c in cases)
+    ws = torch.full((size,), 0xFF, dtype=torch.uint8, device="cuda")
+    failures, hit = [], {}
+    for i, c in enumerate(cases):
+        for what in (c["entry"], c["kind"], f"edge {c['edge']}"):
+            hit[what] = hit.get(what, 0) + 1
+        kw = dict(ws=ws, with_idx=c["with_idx"], in_off=c["in_off"], out_off=c["out_off"])
+        try:
+            exp = R.expected(c["x"], c["descending"], c["kind"])
+            k1, i1 = check(ls, torch, c["x"], c["descending"], c["kind"], exp=exp, entry="sort16", **kw)
+            if c["entry"] == "rows":
+                k2, i2 = check(ls, torch, c["x"], c["descending"], c["kind"], exp=exp, entry="rows", **kw)
+                np.testing.assert_array_equal(k1, k2, err_msg="keys of the two entries")
+                if c["with_idx"]:
+                    np.testing.assert_array_equal(i1, i2, err_msg="positions of the two entries")
+        except AssertionError as err:
+            failures.append(f"seed {seed} case {i}: {c['tag']}: {str(err).strip().splitlines()[0]}")
+    print(f"seed {seed}: {dict(sorted(hit.items()))}")
+    assert not failures, failures
 
 
 @KINDS

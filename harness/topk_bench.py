@@ -20,8 +20,11 @@ rounded to the type, on the three shapes 1 x n k 1024, n/2^16 x 2^16 k 64, n/409
   widen     x.float(), the pass a caller without 16-bit keys pays before it
   torch     torch.topk on the 16-bit tensor
   copy      labsort_copy of the input's bytes
---parent PATH (--key i32 / f32): the same top-k call through another build of liblabsort.so,
-alternating with this one (the regression check of a change to topk.hip).
+--parent PATH (any --key): the same top-k call through another build of liblabsort.so, alternating
+with this one on the same buffers after --warmup calls of each (the regression check of a change to
+topk.hip); int32 keys also on one row of keys % 1000, which never narrows.  Outputs must be equal word
+for word.  A shape is within the rule when this build's median exceeds the parent's by at most the
+parent's own max - min of the run.
 --largest: the k largest, as torch.topk's default.
 
 --sweep: the large-k threshold.  One row of 2^logn keys, k from 2^10 up to the whole row, with the
@@ -48,10 +51,11 @@ def timed(fn):
     return a.elapsed_time(b)
 
 
-def alternate(variants, reps):
-    """variants: {name: fn}.  One warm-up each, then reps rounds over all of them."""
-    for fn in variants.values():
-        fn()
+def alternate(variants, reps, warmup=1):
+    """variants: {name: fn}.  warmup calls of each, then reps rounds over all of them."""
+    for _ in range(warmup):
+        for fn in variants.values():
+            fn()
     torch.cuda.synchronize()
     t = {k: [] for k in variants}
     for _ in range(reps):
@@ -142,29 +146,40 @@ def f16_main(logn, reps, out, with_torch, key, largest):
         del ws, ko, ko32, io, io32
 
 
-def parent_main(logn, reps, out, key, largest, path):
-    """This build against another one (--parent) on the 16-bit shapes, int32 or float32 keys."""
+def parent_main(logn, reps, out, key, largest, path, warmup):
+    """This build against another one (--parent) on the 16-bit shapes."""
     n = 1 << logn
     other = parent_topk(path)
-    keys = torch.empty(n, dtype=torch.float32 if key == "f32" else torch.int32, device="cuda")
-    if key == "f32":
-        keys.normal_(generator=torch.Generator(device="cuda").manual_seed(0x70C0EED))
-    else:
-        ls.fill(keys, n, seed=0x70C0EED, dist="u32")
+    dt = {"i32": torch.int32, "f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[key]
+    keys = torch.empty(n, dtype=torch.int32 if key == "i32" else torch.float32, device="cuda")
     print(f"# top-k, {key} keys, {'largest' if largest else 'smallest'} k with positions, n = 2^{logn}: this build (new) against "
-          f"{path} (parent), {reps} alternating repetitions, ms: median [min, max]", file=out)
+          f"{path} (parent), {warmup} warm-up calls, {reps} alternating repetitions, ms: median [min, max]", file=out)
     print(f"# device: {torch.cuda.get_device_name(0)}; {ls.version()}", file=out)
-    for rows, cols, k in [(1, n, 1024), (n >> 16, 1 << 16, 64), (n >> 12, 4096, 8)]:
-        ko, ko2 = (torch.empty(rows * k, dtype=keys.dtype, device="cuda") for _ in range(2))
+    shapes = [("", 1, n, 1024), ("", n >> 16, 1 << 16, 64), ("", n >> 12, 4096, 8)]
+    if key == "i32":
+        shapes.append(("mod1000", 1, n, 1024))
+    filled = None
+    for dist, rows, cols, k in shapes:
+        if dist != filled:
+            if key == "i32":
+                ls.fill(keys, n, seed=0x70C0EED, dist=dist or "u32")
+            else:  # standard normal, for the 16-bit types rounded to the type
+                keys.normal_(generator=torch.Generator(device="cuda").manual_seed(0x70C0EED))
+            x = keys if keys.dtype == dt else keys.to(dt)
+            filled = dist
+        ko, ko2 = (torch.empty(rows * k, dtype=dt, device="cuda") for _ in range(2))
         io, io2 = (torch.empty(rows * k, dtype=torch.int32, device="cuda") for _ in range(2))
         ws = torch.full((ls.topk_workspace_bytes(rows, cols, k),), 0xFF, dtype=torch.uint8, device="cuda")
-        v = {"new": lambda: ls.topk_device(keys, rows, cols, k, ko, io, largest=largest, key=key, workspace=ws),
-             "parent": lambda: other(keys, rows, cols, k, ko2, io2, largest, key, ws)}
-        t = alternate(v, reps)
+        v = {"new": lambda: ls.topk_device(x, rows, cols, k, ko, io, largest=largest, key=key, workspace=ws),
+             "parent": lambda: other(x, rows, cols, k, ko2, io2, largest, key, ws)}
+        t = alternate(v, reps, warmup)
         torch.cuda.synchronize()
-        assert torch.equal(ko.view(torch.int32), ko2.view(torch.int32)) and torch.equal(io, io2), (rows, cols, k)
-        print(f"{key:<6}{rows:>6} x {cols:<10} k {k:<6}" + "  ".join(f"{name} {fmt(ts)}" for name, ts in t.items()) +
-              f"  new/parent {med(t['new']) / med(t['parent']):.3f}", file=out)
+        bits = torch.int32 if dt.itemsize == 4 else torch.int16
+        assert torch.equal(ko.view(bits), ko2.view(bits)) and torch.equal(io, io2), (rows, cols, k)
+        over, spread = med(t["new"]) - med(t["parent"]), max(t["parent"]) - min(t["parent"])
+        print(f"{key:<6}{dist:<8}{rows:>6} x {cols:<10} k {k:<6}" + "  ".join(f"{name} {fmt(ts)}" for name, ts in t.items()) +
+              f"  new/parent {med(t['new']) / med(t['parent']):.3f}  new - parent {over:+.3f}  parent's spread {spread:.3f}  "
+              f"{'within' if over <= spread else 'OVER'}", file=out)
         out.flush()
         del ws, ko, ko2, io, io2
 
@@ -247,7 +262,8 @@ if __name__ == "__main__":
     ap.add_argument("--key", choices=["i32", "f32", "bf16", "f16"], default="i32",
                     help="f32: standard-normal float32 keys; bf16 / f16: the same rounded to the type, against the f32 call")
     ap.add_argument("--largest", action="store_true", help="bf16 / f16 and --parent runs: the k largest")
-    ap.add_argument("--parent", default="", help="another build of liblabsort.so to alternate with (i32 / f32)")
+    ap.add_argument("--parent", default="", help="another build of liblabsort.so to alternate with")
+    ap.add_argument("--warmup", type=int, default=1, help="--parent runs: calls of each build before the timed ones")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -255,9 +271,9 @@ if __name__ == "__main__":
     out = open(a.out, "a") if a.out else sys.stdout
     if a.sweep:
         sweep_main(a.logn, a.reps, out)
+    elif a.parent:
+        parent_main(a.logn, a.reps, out, a.key, a.largest, a.parent, a.warmup)
     elif a.key in ("bf16", "f16"):
         f16_main(a.logn, a.reps, out, not a.no_torch, a.key, a.largest)
-    elif a.parent:
-        parent_main(a.logn, a.reps, out, a.key, a.largest, a.parent)
     else:
         shapes_main(a.logn, a.reps, out, not a.no_torch, a.key)

@@ -181,12 +181,22 @@ __device__ __forceinline__ uint32_t block_diff_bits(uint32_t a, uint32_t o, uint
     return aa ^ oo;
 }
 
+// Inclusive prefix sum of x over the wave's lanes (all 64 active).
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(x, off);
+        if (lane >= (uint32_t)off) x += t;
+    }
+    return x;
+}
+
 // Exclusive scan over the first R threads of the block (value v in thread tid < R,
 // others pass 0).  Must be called by every thread (contains a barrier when R > 64).
 template <int BLOCK, int R>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum) {
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t x = v;
+    uint32_t x = v;  // (wave_incl_scan, written out: through the helper k_onesweep's instruction text moves)
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const uint32_t t = __shfl_up(x, off);
@@ -249,6 +259,84 @@ __device__ __forceinline__ void wave_rank(const uint32_t (&dig)[KPT], uint32_t (
         if (pre == 0) wh[d] = old + (uint32_t)__popcll(m);  // one leader per digit
         rank[j] = old + pre;
     }
+}
+
+// ---------------------------------------------------------------------------------
+// aligned-group loads (the top-k select's and sort16's reads of a chunk of a row)
+// ---------------------------------------------------------------------------------
+// Elements [beg, end) of an array of 4- or 2-byte elements T are read in groups of
+// E = 16 / sizeof(T) (quads, octs) that start 16-byte aligned: group q holds the elements
+// i0 .. i0 + E - 1, i0 = beg - mis + E q, where mis = 0 .. E - 1 is how far element beg lies
+// into its 16 bytes (base is aligned to T only; a row of odd length starts anywhere).
+// group_mis: mis.  group_count: the groups that hold an element of the range.
+template <typename T>
+__device__ __forceinline__ uint32_t group_mis(const T *base, uint32_t beg) {
+    return (uint32_t)(((uintptr_t)(base + beg) / sizeof(T)) & (16u / sizeof(T) - 1u));
+}
+template <int E>
+__device__ __forceinline__ uint32_t group_count(uint32_t beg, uint32_t end, uint32_t mis) {
+    return (end - beg + mis + (uint32_t)E - 1u) / (uint32_t)E;
+}
+// Group q < group_count: a group inside the range is one 16-byte load, the head and the tail
+// are read element by element.  u[j] = map(element i0 + j) where it exists (0 elsewhere);
+// returns the mask of those j.  map takes a uint32_t and, for 2-byte elements, must read its
+// low half only (the high half holds the neighbour).
+template <typename T, typename MAP>
+__device__ __forceinline__ uint32_t load_group(const T *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
+                                               uint32_t (&u)[16 / sizeof(T)], int64_t &i0, MAP map) {
+    constexpr int E = 16 / sizeof(T);
+    static_assert(E == 4 || E == 8, "4- or 2-byte elements");
+    i0 = (int64_t)beg - (int64_t)mis + E * (int64_t)q;
+    if (i0 >= (int64_t)beg && i0 + E <= (int64_t)end) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(base + i0);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (E == 4) {
+                u[j] = map(w[j]);
+            } else {
+                u[2 * j] = map(w[j]);
+                u[2 * j + 1] = map(w[j] >> 16);
+            }
+        }
+        return (1u << E) - 1u;
+    }
+    uint32_t vm = 0u;
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const int64_t i = i0 + j;
+        u[j] = 0u;
+        if (i >= (int64_t)beg && i < (int64_t)end) {
+            u[j] = map((uint32_t)base[i]);
+            vm |= 1u << j;
+        }
+    }
+    return vm;
+}
+
+// ---------------------------------------------------------------------------------
+// slotted LDS digit histogram: h[digit * SLOTS + slot], 256 digits, slot = tid & (SLOTS - 1),
+// so that the lanes of a wave that meet on one digit spread over SLOTS words
+// ---------------------------------------------------------------------------------
+// Clears h; the caller's barrier follows.
+template <int SLOTS, int BLOCK>
+__device__ __forceinline__ void slot_hist_clear(uint32_t *h, uint32_t tid) {
+    for (uint32_t i = tid; i < 256u * SLOTS; i += BLOCK) h[i] = 0u;
+}
+// One key of thread tid.
+template <int SLOTS>
+__device__ __forceinline__ void slot_hist_add(uint32_t *h, uint32_t digit, uint32_t tid) {
+    atomicAdd(&h[digit * SLOTS + (tid & (SLOTS - 1u))], 1u);
+}
+// Digit d's count (after a barrier): its slots, read from a start rotated by d so that
+// neighbouring threads read different banks.
+template <int SLOTS>
+__device__ __forceinline__ uint32_t slot_hist_fold(const uint32_t *h, uint32_t d) {
+    static_assert((SLOTS & (SLOTS - 1)) == 0, "a power of two");
+    uint32_t sum = 0u;
+#pragma unroll 8
+    for (uint32_t q = 0; q < (uint32_t)SLOTS; ++q) sum += h[d * SLOTS + ((q + d) & (SLOTS - 1u))];
+    return sum;
 }
 
 }  // namespace labsort

@@ -348,12 +348,7 @@ __device__ __forceinline__ void gs_gather_f(const uint32_t *__restrict__ src, co
         const uint4 t4 = *reinterpret_cast<const uint4 *>(&g.tot[4u * lane]);
         const uint32_t tv[4] = {t4.x, t4.y, t4.z, t4.w};
         const uint32_t sum = t4.x + t4.y + t4.z + t4.w;
-        uint32_t x = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(x, off);
-            if (lane >= (uint32_t)off) x += y;
-        }
+        const uint32_t x = wave_incl_scan(sum, lane);
         uint32_t gd = x - sum, first = 4u, last = 0u, gfirst = 0u;
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q) {
@@ -391,7 +386,7 @@ __device__ __forceinline__ void gs_gather_f(const uint32_t *__restrict__ src, co
                 }
                 s += w[j] >> 16;
             }
-            uint32_t x = s;
+            uint32_t x = s;  // (wave_incl_scan, written out: through the helper this kernel's instruction text moves)
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const uint32_t y = __shfl_up(x, off);
@@ -414,12 +409,7 @@ __device__ __forceinline__ void gs_gather_f(const uint32_t *__restrict__ src, co
             const uint4 b4 = *reinterpret_cast<const uint4 *>(&g.bits[4u * lane]);
             const uint32_t p0 = (uint32_t)__popc(b4.x), p1 = (uint32_t)__popc(b4.y), p2 = (uint32_t)__popc(b4.z),
                            p3 = (uint32_t)__popc(b4.w), ps = p0 + p1 + p2 + p3;
-            uint32_t y = ps;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t z = __shfl_up(y, off);
-                if (lane >= (uint32_t)off) y += z;
-            }
+            const uint32_t y = wave_incl_scan(ps, lane);
             const uint32_t e0 = y - ps;
             *reinterpret_cast<uint4 *>(&g.wpre[4u * lane]) = make_uint4(e0, e0 + p0, e0 + p0 + p1, e0 + p0 + p1 + p2);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(HIST_BLOCK) void k_histogram(const uint32_t *__rest
     }
     __syncthreads();
     for (int i = threadIdx.x; i < P * R; i += HIST_BLOCK) {
-        uint32_t s = 0;
+        uint32_t s = 0;  // (slot_hist_fold, written out: through the helper this kernel's instruction text moves)
 #pragma unroll 8
         for (int q = 0; q < SLOTS; ++q) s += h[i * SLOTS + ((q + i) & (SLOTS - 1))];
         if (s) atomicAdd(&hist[i], s);
@@ -1050,7 +1050,7 @@ void k_onesweep_p(Bufs bufs, const Plan *__restrict__ plan, int pass, uint32_t n
             if (tid == (uint32_t)R - 1) tot -= (uint32_t)TILE - nvalidB;  // sentinels
             hB = tot;
             st_agent(lookback + (size_t)slotB * R + tid, (lB == 0 ? LB_INC : LB_AGG) | hB);
-            xB = hB;
+            xB = hB;  // (wave_incl_scan, written out: through the helper this kernel's instruction text moves)
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const uint32_t t = __shfl_up(xB, off);

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(SEG_WAVE_WPB * WAVE) void k_rs_wave(const void *in,
                     c[q] = sm.hist[4u * lane + q];
                     s += c[q];
                 }
-                uint32_t xs = s;
+                uint32_t xs = s;  // (wave_incl_scan, written out: through the helper this kernel's instruction text moves)
 #pragma unroll
                 for (int offx = 1; offx < 64; offx <<= 1) {
                     const uint32_t t = __shfl_up(xs, offx);

@@ -32,45 +32,12 @@ namespace {
 constexpr int S16_W = S16_BLOCK / WAVE;
 constexpr uint32_t S16_KPW = (uint32_t)WAVE * S16_KPT;  // keys of a chunk that one wave ranks: a contiguous stripe
 
-// FIRST: the element is a key of the input and becomes u; else it is u already (the temporary)
+// FIRST: the element is a key of the input and becomes u; else it is u already (the temporary).
+// Only the low half of x counts.
 template <bool FIRST>
 __device__ __forceinline__ uint32_t s16_u(uint32_t x, uint32_t nan_t, uint32_t x16) {
     if constexpr (FIRST) return ord16(x, nan_t) ^ x16;
     else return x & 0xFFFFu;
-}
-
-// Elements [beg, end) of a row (base: 2-byte aligned, a row of odd length starts on either phase)
-// in octs of eight that start 16-byte aligned: oct q covers i0 .. i0 + 7 with
-// i0 = beg - mis + 8 q, mis = 0 .. 7.  An oct inside the range is one 16-byte load, the head and the
-// tail are read element by element (k_tk_hist16's loads).  Returns the mask of the valid elements.
-__device__ __forceinline__ uint32_t s16_mis(const uint16_t *base, uint32_t beg) {
-    return (uint32_t)(((uintptr_t)(base + beg) >> 1) & 7u);
-}
-template <bool FIRST>
-__device__ __forceinline__ uint32_t s16_load_oct(const uint16_t *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
-                                                 uint32_t nan_t, uint32_t x16, uint32_t (&u)[8], int64_t &i0) {
-    i0 = (int64_t)beg - (int64_t)mis + 8 * (int64_t)q;
-    if (i0 >= (int64_t)beg && i0 + 8 <= (int64_t)end) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(base + i0);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            u[2 * j] = s16_u<FIRST>(w[j] & 0xFFFFu, nan_t, x16);
-            u[2 * j + 1] = s16_u<FIRST>(w[j] >> 16, nan_t, x16);
-        }
-        return 255u;
-    }
-    uint32_t vm = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int64_t i = i0 + j;
-        u[j] = 0u;
-        if (i >= (int64_t)beg && i < (int64_t)end) {
-            u[j] = s16_u<FIRST>(base[i], nan_t, x16);
-            vm |= 1u << j;
-        }
-    }
-    return vm;
 }
 
 struct S16Args {
@@ -83,40 +50,43 @@ struct S16Args {
     uint32_t cols, nch, nan_t, x16;
 };
 
+// Octs of the chunk [beg, end) of a row as u (devutil.h, load_group: the top-k select's loads)
+template <bool FIRST>
+__device__ __forceinline__ uint32_t s16_load(const S16Args &a, const uint16_t *base, uint32_t beg, uint32_t end, uint32_t mis,
+                                             uint32_t q, uint32_t (&u)[8], int64_t &i0) {
+    const uint32_t nan_t = a.nan_t, x16 = a.x16;
+    return load_group(base, beg, end, mis, q, u, i0, [nan_t, x16](uint32_t x) { return s16_u<FIRST>(x, nan_t, x16); });
+}
+
 // count: digit (u >> shift) & 255 of the chunk's keys
 template <bool FIRST>
 __global__ __launch_bounds__(S16_BLOCK) void k_s16_count(S16Args a) {
     __shared__ uint32_t h[256 * S16_SLOTS];
     constexpr uint32_t shift = FIRST ? 0u : 8u;
-    const uint32_t tid = threadIdx.x, slot = tid & (S16_SLOTS - 1u);
+    const uint32_t tid = threadIdx.x;
     const uint32_t row = blockIdx.x / a.nch, chunk = blockIdx.x - row * a.nch;
-    for (uint32_t i = tid; i < 256u * S16_SLOTS; i += S16_BLOCK) h[i] = 0u;
+    slot_hist_clear<S16_SLOTS, S16_BLOCK>(h, tid);
     __syncthreads();
     const uint16_t *base = a.kin + (size_t)row * a.cols;
     const uint32_t beg = chunk * (uint32_t)S16_CHUNK;
     const uint32_t end = a.cols - beg > (uint32_t)S16_CHUNK ? beg + (uint32_t)S16_CHUNK : a.cols;
-    const uint32_t mis = s16_mis(base, beg), nq = (end - beg + mis + 7u) / 8u;
+    const uint32_t mis = group_mis(base, beg), nq = group_count<8>(beg, end, mis);
     for (uint32_t q0 = 0; q0 < nq; q0 += 2u * S16_BLOCK) {
         uint32_t u[2][8], vm[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const uint32_t q = q0 + (uint32_t)t * S16_BLOCK + tid;
             int64_t i0;
-            vm[t] = q < nq ? s16_load_oct<FIRST>(base, beg, end, mis, q, a.nan_t, a.x16, u[t], i0) : 0u;
+            vm[t] = q < nq ? s16_load<FIRST>(a, base, beg, end, mis, q, u[t], i0) : 0u;
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if ((vm[t] >> j) & 1u) atomicAdd(&h[((u[t][j] >> shift) & 255u) * S16_SLOTS + slot], 1u);
+                if ((vm[t] >> j) & 1u) slot_hist_add<S16_SLOTS>(h, (u[t][j] >> shift) & 255u, tid);
     }
     __syncthreads();
-    if (tid < 256u) {
-        uint32_t sum = 0u;
-#pragma unroll 8
-        for (uint32_t q = 0; q < (uint32_t)S16_SLOTS; ++q) sum += h[tid * S16_SLOTS + ((q + tid) & (S16_SLOTS - 1u))];
-        a.cnt[((size_t)row * 256u + tid) * a.nch + chunk] = sum;
-    }
+    if (tid < 256u) a.cnt[((size_t)row * 256u + tid) * a.nch + chunk] = slot_hist_fold<S16_SLOTS>(h, tid);
 }
 
 // scan, few chunks per row: thread i walks the nch words of (row, digit) i = row * 256 + digit
@@ -143,12 +113,7 @@ __global__ __launch_bounds__(S16_SCAN_BLOCK) void k_s16_scan_block(uint32_t *cnt
     for (uint32_t c0 = 0; c0 < nch; c0 += (uint32_t)S16_SCAN_BLOCK) {  // (uniform over the workgroup)
         const uint32_t c = c0 + tid;
         const uint32_t v = c < nch ? p[c] : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(x, off);
-            if (lane >= (uint32_t)off) x += t;
-        }
+        const uint32_t x = wave_incl_scan(v, lane);
         if (lane == 63u) wsum[wid] = x;
         __syncthreads();
         uint32_t add = 0u, total = 0u;
@@ -192,11 +157,11 @@ __global__ __launch_bounds__(S16_BLOCK) void k_s16_scatter(S16Args a) {
     const uint32_t end = beg + n;
     probe_lane_order(sm.probe, &sm.ordered, lane, wid);
     {  // the chunk into LDS as 16-bit u, element beg + i in slot i
-        const uint32_t mis = s16_mis(base, beg), nq = (n + mis + 7u) / 8u;
+        const uint32_t mis = group_mis(base, beg), nq = group_count<8>(beg, end, mis);
         for (uint32_t q = tid; q < nq; q += S16_BLOCK) {
             uint32_t u[8];
             int64_t i0;
-            const uint32_t vm = s16_load_oct<FIRST>(base, beg, end, mis, q, a.nan_t, a.x16, u, i0);
+            const uint32_t vm = s16_load<FIRST>(a, base, beg, end, mis, q, u, i0);
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if ((vm >> j) & 1u) sm.keys[(uint32_t)(i0 + j - (int64_t)beg)] = (uint16_t)u[j];  // < n

@@ -1,11 +1,14 @@
 // topk.hip -- top-k selection: the k smallest or largest keys of every row, with their positions
-// (labsort_topk_device).  All kernels work on u = key ^ xr, where plain uint32 order is the
-// order asked for; for float32 keys (the F32 instantiations) u = f32_ord(key) ^ xr, formed where
-// the raw input is read and undone where the keys are written.  For the 16-bit float key types
-// (the k_tk_*16 kernels) the input is 2-byte elements and u = (ord16(key) << 16) ^ xr with
-// xr = largest ? 0xFFFF0000 : 0: the kernels that read the raw input load eight keys per 16 bytes
-// and widen them, two digit levels decide the threshold, and everything behind the input reads
-// (candidate buffer, survivor list, the inner sorts) keeps its 32-bit layout.
+// (labsort_topk_device).  All kernels work on u, where plain uint32 order is the order asked for,
+// formed where the raw input is read (tk_u) and undone where the keys are written (k_tk_write):
+//   int32 / uint32   u = key ^ xr
+//   float32          u = f32_ord(key) ^ xr
+//   bfloat16/float16 u = (ord16(key) << 16) ^ xr, xr = largest ? 0xFFFF0000 : 0; the input is 2-byte
+//                    elements, and two digit levels decide the threshold
+// Every kernel that reads keys is written once and instantiated on the key type (TkKey): it says how a
+// group of the raw input is loaded (quads of 32-bit words, octs of 16-bit elements that are widened)
+// and mapped.  Everything behind the input reads (candidate buffer, survivor list, the inner sorts)
+// holds 32-bit u for every key type.
 //
 // Rows longer than the segmented sort's pair tile are selected by an MSD radix select with 8-bit
 // digits.  A row is cut into chunks of TK_CHUNK keys; per level:
@@ -88,85 +91,41 @@ __device__ __forceinline__ TkSrc tk_src(const TkArgs &a, uint32_t row, const TkS
     return TkSrc{a.keys + (size_t)row * a.cols, nullptr, a.cols, a.xr};
 }
 
-// Elements [beg, end) of a source are read in quads that start 16-byte aligned: quad q holds the
-// elements i0 .. i0 + 3, i0 = beg - mis + 4 q, where mis is how far beg lies into its 16 bytes
-// (a row of odd length starts anywhere).  A quad inside the range is one 16-byte load; the head
-// and the tail are read word by word.  Returns the mask of the elements that exist.
-__device__ __forceinline__ uint32_t tk_mis(const uint32_t *base, uint32_t beg) {
-    return (uint32_t)(((uintptr_t)(base + beg) >> 2) & 3u);
-}
-__device__ __forceinline__ uint32_t tk_quads(uint32_t beg, uint32_t end, uint32_t mis) { return (end - beg + mis + 3u) / 4u; }
-
-// F32: a word of the raw input (raw, uniform over the row) becomes its order image first; the
-// candidate buffer already holds u.
-template <bool F32>
+// Elements [beg, end) of a source are read in 16-byte aligned groups (devutil.h, load_group):
+// quads of 32-bit words, or octs of a raw input of 16-bit elements.  Either way a key becomes u.
+// tk_word: a word of the raw input of a float32 call (raw, uniform over the row) becomes its order
+// image first; the candidate buffer already holds u.
+template <int KT>
 __device__ __forceinline__ uint32_t tk_word(uint32_t w, bool raw) {
-    if constexpr (F32) return raw ? f32_ord(w) : w;
+    if constexpr (KT == TK_F32) return raw ? f32_ord(w) : w;
     else return w;
 }
-template <bool F32>
-__device__ __forceinline__ uint32_t tk_load_quad(const uint32_t *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
-                                                 uint32_t xr, bool raw, uint32_t (&u)[4], int64_t &i0) {
-    i0 = (int64_t)beg - (int64_t)mis + 4 * (int64_t)q;
-    if (i0 >= (int64_t)beg && i0 + 4 <= (int64_t)end) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(base + i0);
-        u[0] = tk_word<F32>(v.x, raw) ^ xr; u[1] = tk_word<F32>(v.y, raw) ^ xr;
-        u[2] = tk_word<F32>(v.z, raw) ^ xr; u[3] = tk_word<F32>(v.w, raw) ^ xr;
-        return 15u;
-    }
-    uint32_t vm = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t i = i0 + j;
-        u[j] = 0u;
-        if (i >= (int64_t)beg && i < (int64_t)end) {
-            u[j] = tk_word<F32>(base[i], raw) ^ xr;
-            vm |= 1u << j;
-        }
-    }
-    return vm;
+// u of an element x of the raw input: key ^ xr, f32_ord(key) ^ xr, or (ord16(key) << 16) ^ xr (ord16
+// reads the low half of x)
+template <int KT>
+__device__ __forceinline__ uint32_t tk_u(uint32_t x, uint32_t xr) {
+    if constexpr (tk_is16(KT)) return (ord16(x, tk_nan_t(KT)) << 16) ^ xr;
+    else return tk_word<KT>(x, true) ^ xr;
 }
-
-// The same for a raw input of 16-bit elements: octs of eight keys that start 16-byte aligned, so
-// mis is 0 .. 7 elements (the base is 2-byte aligned, a row of odd length starts anywhere).  An
-// oct inside the range is one 16-byte load, the head and the tail are read element by element;
-// every key is widened to u = (ord16(key) << 16) ^ xr.
+template <int KT>
+using tk_elem_t = std::conditional_t<tk_is16(KT), uint16_t, uint32_t>;
 __device__ __forceinline__ const uint16_t *tk_raw16(const TkArgs &a, uint32_t row) {
     return reinterpret_cast<const uint16_t *>(a.keys) + (size_t)row * a.cols;
 }
-__device__ __forceinline__ uint32_t tk_mis16(const uint16_t *base, uint32_t beg) {
-    return (uint32_t)(((uintptr_t)(base + beg) >> 1) & 7u);
-}
-__device__ __forceinline__ uint32_t tk_octs(uint32_t beg, uint32_t end, uint32_t mis) { return (end - beg + mis + 7u) / 8u; }
-template <int KT>
-__device__ __forceinline__ uint32_t tk_u16(uint32_t x, uint32_t xr) {
-    return (ord16(x, tk_nan_t(KT)) << 16) ^ xr;
-}
-template <int KT>
-__device__ __forceinline__ uint32_t tk_load_oct(const uint16_t *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
-                                                uint32_t xr, uint32_t (&u)[8], int64_t &i0) {
-    i0 = (int64_t)beg - (int64_t)mis + 8 * (int64_t)q;
-    if (i0 >= (int64_t)beg && i0 + 8 <= (int64_t)end) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(base + i0);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            u[2 * j] = tk_u16<KT>(w[j], xr);  // (ord16 reads the low half)
-            u[2 * j + 1] = tk_u16<KT>(w[j] >> 16, xr);
-        }
-        return 255u;
+// Group q of the chunk [beg, end) of s as u[E], E keys per load: E = 8, octs of the raw 16-bit input
+// (raw16); E = 4, quads of s.u, the raw input of a 32-bit call or a candidate buffer.  Returns the
+// mask of the keys that exist; mis is the chunk's misalignment in that source.
+template <int E, int KT>
+__device__ __forceinline__ uint32_t tk_load(const TkSrc &s, const uint16_t *raw16, uint32_t beg, uint32_t end, uint32_t mis,
+                                            uint32_t q, uint32_t (&u)[E], int64_t &i0) {
+    static_assert(E == 4 || tk_is16(KT), "octs are a 16-bit call's reads of its raw input");
+    const uint32_t xr = s.xr;
+    if constexpr (E == 8) {
+        return load_group(raw16, beg, end, mis, q, u, i0, [xr](uint32_t x) { return tk_u<KT>(x, xr); });
+    } else {
+        const bool raw = s.p == nullptr;
+        return load_group(s.u, beg, end, mis, q, u, i0, [xr, raw](uint32_t w) { return tk_word<KT>(w, raw) ^ xr; });
     }
-    uint32_t vm = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int64_t i = i0 + j;
-        u[j] = 0u;
-        if (i >= (int64_t)beg && i < (int64_t)end) {
-            u[j] = tk_u16<KT>(base[i], xr);
-            vm |= 1u << j;
-        }
-    }
-    return vm;
 }
 
 // The digit at which the running count of a row's level histogram reaches krem: the d with
@@ -178,12 +137,7 @@ __device__ __forceinline__ TkPick tk_pick(const uint32_t *hrow, uint32_t krem, u
     const uint4 v = reinterpret_cast<const uint4 *>(hrow)[lane];  // digits 4 lane .. 4 lane + 3
     const uint32_t c[4] = {v.x, v.y, v.z, v.w};
     const uint32_t s = v.x + v.y + v.z + v.w;
-    uint32_t x = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(x, off);
-        if (lane >= (uint32_t)off) x += t;
-    }
+    const uint32_t x = wave_incl_scan(s, lane);
     uint32_t run = x - s, d = 255u, below = x - c[3], bucket = c[3];  // (lane 63's default: the last digit)
     bool found = false;
 #pragma unroll
@@ -206,96 +160,37 @@ __device__ __forceinline__ TkPick tk_pick(const uint32_t *hrow, uint32_t krem, u
     return p;
 }
 
-template <bool F32>
-__global__ __launch_bounds__(TK_BLOCK) void k_tk_hist(TkArgs a, int level, uint32_t nx, uint32_t g) {
-    __shared__ uint32_t h[256 * TK_SLOTS];
-    const uint32_t tid = threadIdx.x, slot = tid & (TK_SLOTS - 1u);
-    const uint32_t row = blockIdx.x / nx, bx = blockIdx.x - row * nx;
-    const TkState st = tk_state(a, row, level);
-    const TkSrc s = tk_src(a, row, st);
-    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
-    const uint32_t c0 = bx * g;
-    if (c0 >= nact) return;
-    const uint32_t c1 = c0 + g < nact ? c0 + g : nact;
-    const uint32_t shift = 24u - 8u * (uint32_t)level;
-    const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
-    uint32_t acc = 0u;
-    for (uint32_t c = c0; c < c1; ++c) {
-        for (uint32_t i = tid; i < 256u * TK_SLOTS; i += TK_BLOCK) h[i] = 0u;
-        __syncthreads();
-        const uint32_t beg = c * TK_CHUNK, end = beg + TK_CHUNK < s.count ? beg + TK_CHUNK : s.count;
-        const uint32_t mis = tk_mis(s.u, beg), nq = tk_quads(beg, end, mis);
-        for (uint32_t q0 = 0; q0 < nq; q0 += 4u * TK_BLOCK) {
-            uint32_t u[4][4], vm[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const uint32_t q = q0 + (uint32_t)t * TK_BLOCK + tid;
-                int64_t i0;
-                vm[t] = q < nq ? tk_load_quad<F32>(s.u, beg, end, mis, q, s.xr, s.p == nullptr, u[t], i0) : 0u;
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (((vm[t] >> j) & 1u) && ((u[t][j] ^ st.prefix) & mask) == 0u)
-                        atomicAdd(&h[((u[t][j] >> shift) & 255u) * TK_SLOTS + slot], 1u);
-        }
-        __syncthreads();
-        if (tid < 256u) {
-            uint32_t sum = 0u;
-#pragma unroll 8
-            for (uint32_t q = 0; q < (uint32_t)TK_SLOTS; ++q) sum += h[tid * TK_SLOTS + ((q + tid) & (TK_SLOTS - 1u))];
-            a.cnt[((size_t)row * a.nch + c) * 256u + tid] = sum;
-            acc += sum;
-        }
-        __syncthreads();
-    }
-    if (tid < 256u && acc) atomicAdd(&a.hist[((size_t)row * TK_LEVELS + level) * 256u + tid], acc);
-}
-
-// ---- the 16-bit call's kernels (KT = TK_BF16 / TK_F16).  They are kernels of their own, and the
-// 32-bit kernels keep their text: written once for both key widths, k_tk_hist and k_tk_compact
-// came out with other register counts for the 32-bit key types. ----
-
-// Counts into h (LDS) the level's digit of the keys of [beg, end) that match the prefix.  E keys
-// per load: 8 keys of the raw 16-bit input (raw16), or 4 words of the candidate buffer; either
-// way a thread has 16 keys in flight.
+// Counts into h (LDS) the level's digit of the keys of [beg, end) that match the prefix, E keys per
+// load (tk_load); either way a thread has 16 keys in flight.
 template <int E, int KT>
 __device__ __forceinline__ void tk_hist_chunk(uint32_t *h, const TkSrc &s, const uint16_t *raw16, uint32_t beg, uint32_t end,
-                                              uint32_t prefix, uint32_t mask, uint32_t shift, uint32_t tid, uint32_t slot) {
+                                              uint32_t prefix, uint32_t mask, uint32_t shift, uint32_t tid) {
     constexpr int T = 16 / E;
-    uint32_t mis, nq;
-    if constexpr (E == 8) {
-        mis = tk_mis16(raw16, beg);
-        nq = tk_octs(beg, end, mis);
-    } else {
-        mis = tk_mis(s.u, beg);
-        nq = tk_quads(beg, end, mis);
-    }
+    const uint32_t mis = E == 8 ? group_mis(raw16, beg) : group_mis(s.u, beg), nq = group_count<E>(beg, end, mis);
     for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)T * TK_BLOCK) {
         uint32_t u[T][E], vm[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const uint32_t q = q0 + (uint32_t)t * TK_BLOCK + tid;
             int64_t i0;
-            if constexpr (E == 8) vm[t] = q < nq ? tk_load_oct<KT>(raw16, beg, end, mis, q, s.xr, u[t], i0) : 0u;
-            else vm[t] = q < nq ? tk_load_quad<false>(s.u, beg, end, mis, q, s.xr, false, u[t], i0) : 0u;
+            vm[t] = q < nq ? tk_load<E, KT>(s, raw16, beg, end, mis, q, u[t], i0) : 0u;
         }
 #pragma unroll
         for (int t = 0; t < T; ++t)
 #pragma unroll
             for (int j = 0; j < E; ++j)
                 if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u)
-                    atomicAdd(&h[((u[t][j] >> shift) & 255u) * TK_SLOTS + slot], 1u);
+                    slot_hist_add<TK_SLOTS>(h, (u[t][j] >> shift) & 255u, tid);
     }
 }
 
-// k_tk_hist: a row that has not narrowed is read from the raw input, eight keys per load; a
-// narrowed one from its candidate buffer of 32-bit u.
+// One kernel for every key type KT.  A 16-bit call reads a row that has not narrowed from the raw
+// input, eight keys per load, and a narrowed one from its candidate buffer of 32-bit u; a 32-bit
+// call reads quads of either.
 template <int KT>
-__global__ __launch_bounds__(TK_BLOCK) void k_tk_hist16(TkArgs a, int level, uint32_t nx, uint32_t g) {
+__global__ __launch_bounds__(TK_BLOCK) void k_tk_hist(TkArgs a, int level, uint32_t nx, uint32_t g) {
     __shared__ uint32_t h[256 * TK_SLOTS];
-    const uint32_t tid = threadIdx.x, slot = tid & (TK_SLOTS - 1u);
+    const uint32_t tid = threadIdx.x;
     const uint32_t row = blockIdx.x / nx, bx = blockIdx.x - row * nx;
     const TkState st = tk_state(a, row, level);
     const TkSrc s = tk_src(a, row, st);
@@ -308,16 +203,18 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_hist16(TkArgs a, int level, uin
     const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
     uint32_t acc = 0u;
     for (uint32_t c = c0; c < c1; ++c) {
-        for (uint32_t i = tid; i < 256u * TK_SLOTS; i += TK_BLOCK) h[i] = 0u;
+        slot_hist_clear<TK_SLOTS, TK_BLOCK>(h, tid);
         __syncthreads();
         const uint32_t beg = c * TK_CHUNK, end = beg + TK_CHUNK < s.count ? beg + TK_CHUNK : s.count;
-        if (s.p == nullptr) tk_hist_chunk<8, KT>(h, s, raw16, beg, end, st.prefix, mask, shift, tid, slot);  // (uniform over the workgroup)
-        else tk_hist_chunk<4, KT>(h, s, raw16, beg, end, st.prefix, mask, shift, tid, slot);
+        if constexpr (tk_is16(KT)) {
+            if (s.p == nullptr) tk_hist_chunk<8, KT>(h, s, raw16, beg, end, st.prefix, mask, shift, tid);  // (uniform over the workgroup)
+            else tk_hist_chunk<4, KT>(h, s, raw16, beg, end, st.prefix, mask, shift, tid);
+        } else {
+            tk_hist_chunk<4, KT>(h, s, raw16, beg, end, st.prefix, mask, shift, tid);
+        }
         __syncthreads();
         if (tid < 256u) {
-            uint32_t sum = 0u;
-#pragma unroll 8
-            for (uint32_t q = 0; q < (uint32_t)TK_SLOTS; ++q) sum += h[tid * TK_SLOTS + ((q + tid) & (TK_SLOTS - 1u))];
+            const uint32_t sum = slot_hist_fold<TK_SLOTS>(h, tid);
             a.cnt[((size_t)row * a.nch + c) * 256u + tid] = sum;
             acc += sum;
         }
@@ -407,95 +304,11 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_scan(TkArgs a, int level) {
 // whose top digits lie below the new prefix go to the survivor list, those that match it to the
 // candidate buffer.  FINAL = true: the keys below the threshold and the first krem keys equal to
 // it go to the survivor list.  Every store is bounds-checked against its list.
-template <bool FINAL, bool F32>
-__global__ __launch_bounds__(TK_BLOCK) void k_tk_compact(TkArgs a, int level) {
-    __shared__ uint32_t wsum[TK_BLOCK / WAVE], tot;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t row = blockIdx.x / a.nch, chunk = blockIdx.x - row * a.nch;
-    const TkState ns = a.st[(size_t)row * (TK_LEVELS + 1) + level + 1];
-    if (!FINAL && !ns.jn) return;
-    TkState from = ns;
-    if (!FINAL) from.narrowed = 0u;  // a row narrows once, from the input
-    const TkSrc s = tk_src(a, row, from);
-    const uint32_t nact = (s.count + TK_CHUNK - 1u) / TK_CHUNK;
-    if (chunk >= nact) return;
-    const size_t idx = (size_t)row * a.nch + chunk;
-    const uint32_t eqb = a.eqbase[idx];
-    // (FINAL: nothing of this chunk is taken: no key below the threshold, its equals past the last one taken)
-    if (FINAL && a.low[idx] == 0u && eqb >= ns.krem) return;
-    const uint32_t lob = a.lowbase[idx] + (FINAL ? ns.sbase : 0u);
-    const uint32_t mask = FINAL ? 0xFFFFFFFFu : 0xFFFFFFFFu << (24u - 8u * (uint32_t)level);
-    const uint32_t P = ns.prefix;
-    uint32_t *su = a.surv_u + (size_t)row * a.k, *sp = a.surv_p + (size_t)row * a.k;
-    uint32_t *cu = a.cand_u + (size_t)row * a.capa, *cp = a.cand_p + (size_t)row * a.capa;
-    const uint32_t beg = chunk * TK_CHUNK, end = beg + TK_CHUNK < s.count ? beg + TK_CHUNK : s.count;
-    const uint32_t mis = tk_mis(s.u, beg), nq = tk_quads(beg, end, mis);
-    uint32_t carry_l = 0u, carry_e = 0u;
-    for (uint32_t q0 = 0; q0 < nq; q0 += TK_BLOCK) {
-        const uint32_t q = q0 + tid;
-        uint32_t u[4], pos[4], vm = 0u;
-        int64_t i0 = 0;
-        if (q < nq) vm = tk_load_quad<F32>(s.u, beg, end, mis, q, s.xr, s.p == nullptr, u, i0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pos[j] = (uint32_t)(i0 + j);
-        if (s.p) {
-            if (vm == 15u) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(s.p + i0);
-                pos[0] = v.x; pos[1] = v.y; pos[2] = v.z; pos[3] = v.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if ((vm >> j) & 1u) pos[j] = s.p[i0 + j];
-            }
-        }
-        uint32_t lm = 0u, em = 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if ((vm >> j) & 1u) {
-                const uint32_t t = u[j] & mask;
-                lm |= (t < P ? 1u : 0u) << j;
-                em |= (t == P ? 1u : 0u) << j;
-            }
-        // one scan for both counts: a batch holds at most 4096 keys
-        const uint32_t packed = (uint32_t)__popc(lm) | ((uint32_t)__popc(em) << 16);
-        const uint32_t ex = block_excl_scan<TK_BLOCK, TK_BLOCK>(packed, wsum);
-        if (tid == TK_BLOCK - 1u) tot = ex + packed;
-        __syncthreads();
-        uint32_t l = lob + carry_l + (ex & 0xFFFFu), e = eqb + carry_e + (ex >> 16);
-        carry_l += tot & 0xFFFFu;
-        carry_e += tot >> 16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if ((lm >> j) & 1u) {
-                if (l < a.k) {
-                    su[l] = u[j];
-                    sp[l] = pos[j];
-                }
-                ++l;
-            }
-            if ((em >> j) & 1u) {
-                if (FINAL) {
-                    const uint32_t t = ns.sbase + ns.tlow + e;
-                    if (e < ns.krem && t < a.k) {
-                        su[t] = u[j];
-                        sp[t] = pos[j];
-                    }
-                } else if (e < a.cap) {
-                    cu[e] = u[j];
-                    cp[e] = pos[j];
-                }
-                ++e;
-            }
-        }
-        __syncthreads();  // wsum and tot are reused by the next batch
-    }
-}
-
-// k_tk_compact for a 16-bit call (KT = TK_BF16 / TK_F16).  The pass is written once for E keys per
-// thread and batch (ec): octs of the raw 16-bit input (every narrowing pass, and the final one of
-// a row that never narrowed), or quads of the candidate buffer.
+// The pass is written once for E keys per thread and batch (ec): for a 16-bit call octs of the raw
+// input (every narrowing pass, and the final one of a row that never narrowed) or quads of the
+// candidate buffer, for a 32-bit call quads of either.
 template <bool FINAL, int KT>
-__global__ __launch_bounds__(TK_BLOCK) void k_tk_compact16(TkArgs a, int level) {
+__global__ __launch_bounds__(TK_BLOCK) void k_tk_compact(TkArgs a, int level) {
     __shared__ uint32_t wsum[TK_BLOCK / WAVE], tot;
     const uint32_t tid = threadIdx.x;
     const uint32_t row = blockIdx.x / a.nch, chunk = blockIdx.x - row * a.nch;
@@ -521,23 +334,13 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_compact16(TkArgs a, int level) 
         constexpr int E = decltype(ec)::value;
         // one scan for both counts, 16 bits each: a batch holds at most 8192 keys
         static_assert(E * TK_BLOCK <= 65535, "the packed scan holds two 16-bit counts per batch");
-        uint32_t mis, nq;
-        if constexpr (E == 8) {
-            mis = tk_mis16(raw16, beg);
-            nq = tk_octs(beg, end, mis);
-        } else {
-            mis = tk_mis(s.u, beg);
-            nq = tk_quads(beg, end, mis);
-        }
+        const uint32_t mis = E == 8 ? group_mis(raw16, beg) : group_mis(s.u, beg), nq = group_count<E>(beg, end, mis);
         uint32_t carry_l = 0u, carry_e = 0u;
         for (uint32_t q0 = 0; q0 < nq; q0 += TK_BLOCK) {
             const uint32_t q = q0 + tid;
             uint32_t u[E], pos[E], vm = 0u;
             int64_t i0 = 0;
-            if (q < nq) {
-                if constexpr (E == 8) vm = tk_load_oct<KT>(raw16, beg, end, mis, q, s.xr, u, i0);
-                else vm = tk_load_quad<false>(s.u, beg, end, mis, q, s.xr, false, u, i0);
-            }
+            if (q < nq) vm = tk_load<E, KT>(s, raw16, beg, end, mis, q, u, i0);
 #pragma unroll
             for (int j = 0; j < E; ++j) pos[j] = (uint32_t)(i0 + j);
             if constexpr (E == 4) {
@@ -593,28 +396,24 @@ __global__ __launch_bounds__(TK_BLOCK) void k_tk_compact16(TkArgs a, int level) 
             __syncthreads();  // wsum and tot are reused by the next batch
         }
     };
-    if (!FINAL || s.p == nullptr) pass(std::integral_constant<int, 8>{});  // (uniform over the workgroup)
-    else pass(std::integral_constant<int, 4>{});
-}
-
-template <bool F32>
-__global__ __launch_bounds__(256) void k_tk_prep(const uint32_t *__restrict__ keys, uint32_t *__restrict__ u,
-                                                 uint32_t *__restrict__ pos, size_t n, uint32_t cols, uint32_t xr) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (u) u[i] = tk_word<F32>(keys[i], true) ^ xr;
-        pos[i] = (uint32_t)i % cols;  // (n <= 2^31 - 1)
+    if constexpr (tk_is16(KT)) {
+        if (!FINAL || s.p == nullptr) pass(std::integral_constant<int, 8>{});  // (uniform over the workgroup)
+        else pass(std::integral_constant<int, 4>{});
+    } else {
+        pass(std::integral_constant<int, 4>{});
     }
 }
 
-// 16-bit keys, for the paths that sort whole rows (not the hot path: one key per thread and load)
+// u[i] = tk_u of element i of the raw input, pos[i] = i % cols: for the paths that sort whole rows
+// (one key per thread and load).  A 32-bit call may pass u == nullptr (the short path sorts the keys
+// themselves); a 16-bit call always widens, and its loop stays free of the test.
 template <int KT>
-__global__ __launch_bounds__(256) void k_tk_prep16(const uint16_t *__restrict__ keys, uint32_t *__restrict__ u,
-                                                   uint32_t *__restrict__ pos, size_t n, uint32_t cols, uint32_t xr) {
+__global__ __launch_bounds__(256) void k_tk_prep(const tk_elem_t<KT> *__restrict__ keys, uint32_t *__restrict__ u,
+                                                 uint32_t *__restrict__ pos, size_t n, uint32_t cols, uint32_t xr) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        u[i] = tk_u16<KT>(keys[i], xr);
-        pos[i] = (uint32_t)i % cols;
+        if (tk_is16(KT) || u) u[i] = tk_u<KT>(keys[i], xr);
+        pos[i] = (uint32_t)i % cols;  // (n <= 2^31 - 1)
     }
 }
 
@@ -631,29 +430,19 @@ __global__ void k_tk_err_acc(uint32_t *hdr, const uint32_t *inner, int nw) {
     }
 }
 
-// grid: x over the k outputs of a row, rows folded into x as well (row = block / bpr)
-template <bool F32>
+// grid: x over the k outputs of a row, rows folded into x as well (row = block / bpr).  The inverse
+// of tk_u; a 16-bit call writes 2-byte elements (either format: unord16 is the same for both)
+template <int KT>
 __global__ __launch_bounds__(256) void k_tk_write(const uint32_t *__restrict__ su, const uint32_t *__restrict__ sp,
-                                                  uint32_t *__restrict__ ko, uint32_t *__restrict__ io, uint32_t m,
+                                                  tk_elem_t<KT> *__restrict__ ko, uint32_t *__restrict__ io, uint32_t m,
                                                   uint32_t k, uint32_t bpr, uint32_t xr) {
     const uint32_t row = blockIdx.x / bpr, bx = blockIdx.x - row * bpr;
     const size_t src = (size_t)row * m, dst = (size_t)row * k;
     for (uint32_t j = bx * 256u + threadIdx.x; j < k; j += bpr * 256u) {
         const uint32_t w = su[src + j] ^ xr;
-        if constexpr (F32) ko[dst + j] = f32_unord(w);
+        if constexpr (tk_is16(KT)) ko[dst + j] = (uint16_t)unord16(w >> 16);
+        else if constexpr (KT == TK_F32) ko[dst + j] = f32_unord(w);
         else ko[dst + j] = w;
-        if (io) io[dst + j] = sp[src + j];
-    }
-}
-
-// 16-bit keys (either format: unord16 is the same for both): 2-byte elements out
-__global__ __launch_bounds__(256) void k_tk_write16(const uint32_t *__restrict__ su, const uint32_t *__restrict__ sp,
-                                                    uint16_t *__restrict__ ko, uint32_t *__restrict__ io, uint32_t m,
-                                                    uint32_t k, uint32_t bpr, uint32_t xr) {
-    const uint32_t row = blockIdx.x / bpr, bx = blockIdx.x - row * bpr;
-    const size_t src = (size_t)row * m, dst = (size_t)row * k;
-    for (uint32_t j = bx * 256u + threadIdx.x; j < k; j += bpr * 256u) {
-        ko[dst + j] = (uint16_t)unord16((su[src + j] ^ xr) >> 16);
         if (io) io[dst + j] = sp[src + j];
     }
 }
@@ -663,15 +452,15 @@ unsigned tk_stream_blocks(size_t n) {
     return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
 }
 
-// kt: TkKey.  The 32-bit kinds run the kernels instantiated on F32, the 16-bit kinds their own.
+// kt: TkKey, the instantiation that runs.
 hipError_t launch_topk_hist(const TkArgs &a, size_t rows, int level, int kt, hipStream_t s) {
     const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
     const uint32_t nx = (a.nch + g - 1u) / g;
     const unsigned grid = (unsigned)(rows * nx);
-    if (kt == TK_BF16) k_tk_hist16<TK_BF16><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
-    else if (kt == TK_F16) k_tk_hist16<TK_F16><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
-    else if (kt == TK_F32) k_tk_hist<true><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
-    else k_tk_hist<false><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
+    if (kt == TK_BF16) k_tk_hist<TK_BF16><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
+    else if (kt == TK_F16) k_tk_hist<TK_F16><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
+    else if (kt == TK_F32) k_tk_hist<TK_F32><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
+    else k_tk_hist<TK_INT><<<grid, TK_BLOCK, 0, s>>>(a, level, nx, g);
     return hipGetLastError();
 }
 
@@ -694,10 +483,10 @@ hipError_t launch_topk_scan(const TkArgs &a, size_t rows, int level, int kt, hip
 template <bool FINAL>
 hipError_t launch_topk_compact(const TkArgs &a, size_t rows, int level, int kt, hipStream_t s) {
     const unsigned grid = (unsigned)(rows * a.nch);
-    if (kt == TK_BF16) k_tk_compact16<FINAL, TK_BF16><<<grid, TK_BLOCK, 0, s>>>(a, level);
-    else if (kt == TK_F16) k_tk_compact16<FINAL, TK_F16><<<grid, TK_BLOCK, 0, s>>>(a, level);
-    else if (kt == TK_F32) k_tk_compact<FINAL, true><<<grid, TK_BLOCK, 0, s>>>(a, level);
-    else k_tk_compact<FINAL, false><<<grid, TK_BLOCK, 0, s>>>(a, level);
+    if (kt == TK_BF16) k_tk_compact<FINAL, TK_BF16><<<grid, TK_BLOCK, 0, s>>>(a, level);
+    else if (kt == TK_F16) k_tk_compact<FINAL, TK_F16><<<grid, TK_BLOCK, 0, s>>>(a, level);
+    else if (kt == TK_F32) k_tk_compact<FINAL, TK_F32><<<grid, TK_BLOCK, 0, s>>>(a, level);
+    else k_tk_compact<FINAL, TK_INT><<<grid, TK_BLOCK, 0, s>>>(a, level);
     return hipGetLastError();
 }
 hipError_t launch_topk_narrow(const TkArgs &a, size_t rows, int level, int kt, hipStream_t s) {
@@ -707,18 +496,17 @@ hipError_t launch_topk_final(const TkArgs &a, size_t rows, int kt, hipStream_t s
     return launch_topk_compact<true>(a, rows, tk_levels(kt) - 1, kt, s);
 }
 
-// u[i] = keys[i] ^ xr (f32: f32_ord(keys[i]) ^ xr; u may be nullptr), pos[i] = i % cols
-hipError_t launch_topk_prep(const uint32_t *keys, uint32_t *u, uint32_t *pos, size_t n, size_t cols, uint32_t xr,
-                            bool f32, hipStream_t s) {
-    if (f32) k_tk_prep<true><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
-    else k_tk_prep<false><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
-    return hipGetLastError();
-}
-// the same for 16-bit keys (kt: TK_BF16 / TK_F16): u[i] = (ord16(keys[i]) << 16) ^ xr
-hipError_t launch_topk_prep16(const uint16_t *keys, uint32_t *u, uint32_t *pos, size_t n, size_t cols, uint32_t xr,
-                              int kt, hipStream_t s) {
-    if (kt == TK_BF16) k_tk_prep16<TK_BF16><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
-    else k_tk_prep16<TK_F16><<<tk_stream_blocks(n), 256, 0, s>>>(keys, u, pos, n, (uint32_t)cols, xr);
+// u[i] = keys[i] ^ xr (TK_F32: f32_ord(keys[i]) ^ xr; 16-bit kinds: (ord16(keys[i]) << 16) ^ xr, keys
+// 2-byte elements; u may be nullptr), pos[i] = i % cols
+hipError_t launch_topk_prep(const void *keys, uint32_t *u, uint32_t *pos, size_t n, size_t cols, uint32_t xr, int kt,
+                            hipStream_t s) {
+    const unsigned grid = tk_stream_blocks(n);
+    const uint32_t *k32 = static_cast<const uint32_t *>(keys);
+    const uint16_t *k16 = static_cast<const uint16_t *>(keys);
+    if (kt == TK_BF16) k_tk_prep<TK_BF16><<<grid, 256, 0, s>>>(k16, u, pos, n, (uint32_t)cols, xr);
+    else if (kt == TK_F16) k_tk_prep<TK_F16><<<grid, 256, 0, s>>>(k16, u, pos, n, (uint32_t)cols, xr);
+    else if (kt == TK_F32) k_tk_prep<TK_F32><<<grid, 256, 0, s>>>(k32, u, pos, n, (uint32_t)cols, xr);
+    else k_tk_prep<TK_INT><<<grid, 256, 0, s>>>(k32, u, pos, n, (uint32_t)cols, xr);
     return hipGetLastError();
 }
 
@@ -744,9 +532,10 @@ hipError_t launch_topk_write(const uint32_t *su, const uint32_t *sp, void *keys_
     if (bpr > room) bpr = room ? room : 1;
     const unsigned grid = (unsigned)(rows * bpr);
     uint32_t *ko = static_cast<uint32_t *>(keys_out);
-    if (tk_is16(kt)) k_tk_write16<<<grid, 256, 0, s>>>(su, sp, static_cast<uint16_t *>(keys_out), idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
-    else if (kt == TK_F32) k_tk_write<true><<<grid, 256, 0, s>>>(su, sp, ko, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
-    else k_tk_write<false><<<grid, 256, 0, s>>>(su, sp, ko, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    // (one 16-bit instantiation serves both formats)
+    if (tk_is16(kt)) k_tk_write<TK_BF16><<<grid, 256, 0, s>>>(su, sp, static_cast<uint16_t *>(keys_out), idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    else if (kt == TK_F32) k_tk_write<TK_F32><<<grid, 256, 0, s>>>(su, sp, ko, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
+    else k_tk_write<TK_INT><<<grid, 256, 0, s>>>(su, sp, ko, idx_out, (uint32_t)m, (uint32_t)k, (uint32_t)bpr, xr);
     return hipGetLastError();
 }
 
@@ -861,8 +650,7 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
     hipStream_t s = as_stream(stream);
     char *ws = static_cast<char *>(d_ws);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t *>(ws + off); };
-    const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
-    const uint16_t *keys16 = static_cast<const uint16_t *>(d_keys);  // (what a 16-bit call reads: k_tk_prep16, tk_raw16)
+    const uint32_t *keys = static_cast<const uint32_t *>(d_keys);  // (a 16-bit call reads 2-byte elements: k_tk_prep, tk_raw16)
     uint32_t *hdr = W(0), *A = W(L.off_a), *B = W(L.off_b), *SU = W(L.off_su), *SP = W(L.off_sp), *offs = W(L.off_offs);
     void *ko = d_keys_out;
     const size_t n = rows * L.m;
@@ -875,8 +663,8 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
         // 16-bit keys: the class kernels load 32-bit words, so the keys are first widened to
         // ord16(key) << 16 into SU and sorted there in place (a class kernel holds its whole segment in
         // registers before its first store, as the in-place segmented sort relies on)
-        if (k16) HIP_TRY(launch_topk_prep16(keys16, SU, B, n, cols, 0u, kt, s));
-        else HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, false, s));
+        if (k16) HIP_TRY(launch_topk_prep(keys, SU, B, n, cols, 0u, kt, s));
+        else HIP_TRY(launch_topk_prep(keys, nullptr, B, n, cols, xr, TK_INT, s));  // (positions only)
         HIP_TRY(launch_seg_bin(offs, rows, n, cols, true, true, hdr, lists, L.list_stride, s));
         HIP_TRY(launch_seg_lds_classes(cols, true, k16 ? SU : keys, SU, B, SP, offs, hdr, lists, L.list_stride, xr, f32, s));
         // (the class kernels wrote keys, not u: nothing to undo but, for 16-bit keys, ord16)
@@ -914,8 +702,7 @@ int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, 
         HIP_TRY(launch_topk_final(a, rows, kt, s));
     } else {
         TimingScope ts(LABSORT_K_TOPK, s);
-        if (k16) HIP_TRY(launch_topk_prep16(keys16, A, B, n, cols, xr, kt, s));
-        else HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, f32, s));
+        HIP_TRY(launch_topk_prep(keys, A, B, n, cols, xr, kt, s));
     }
     // order the m pairs of every row on u (stable): one pair sort, or the segmented pair sort
     char *iws = ws + L.off_inner;

@@ -1,8 +1,8 @@
 """The radix select of labsort_topk_device on the GPU where test_gpu_topk.py does not reach: rows of
 more than 1024 chunks (a histogram workgroup counts several chunks, the scan over the chunks takes a
 second step and carries its sums), every level at which a row can narrow and both sides of the
-candidate buffer's capacity, rows of all those kinds in one call and in one replayed graph, and a
-seeded sweep over key types, directions, shapes, paths and options.
+candidate buffer's capacity, rows of all those kinds in one call and in one replayed graph, rows at
+every misalignment of the kernels' 16-byte group loads, and a seeded sweep over key types, directions, shapes, paths and options.
 
 Every call follows test_gpu_topk.py's protocol: a workspace filled with 0xFF, outputs filled with a
 pattern, the status call afterwards, the input unchanged, whole key and position arrays compared
@@ -36,8 +36,9 @@ def torch_dtype(torch, kind):
     return {"u32": torch.int32, "i32": torch.int32, "f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[kind]
 
 
-def run(ls, torch, x, k, kind, largest, ws=None, with_idx=True, in_off=0):
-    """in_off: elements between the start of the storage and the matrix."""
+def run(ls, torch, x, k, kind, largest, ws=None, with_idx=True, in_off=0, aligned=False):
+    """in_off: elements between the start of the storage and the matrix.  aligned: the case relies on
+    the matrix starting on a 16-byte boundary."""
     rows, cols = x.shape
     wide = T.bits_of(kind) == 32
     it, ut = (torch.int32, np.uint32) if wide else (torch.int16, np.uint16)
@@ -46,6 +47,7 @@ def run(ls, torch, x, k, kind, largest, ws=None, with_idx=True, in_off=0):
     store = torch.full((rows * cols + in_off,), 0x1111, dtype=it, device="cuda")
     d = store[in_off:].view(rows, cols)
     d.copy_(torch.from_numpy(x.view(st).copy()))  # (a copy: shared inputs are read-only)
+    assert not aligned or d.data_ptr() % 16 == 0
     before = store.clone()
     ostore = torch.full((rows * k + 1,), 0x5A5A, dtype=it, device="cuda")
     ko = ostore[:rows * k].view(rows, k)
@@ -193,6 +195,33 @@ def test_narrowing_matrix(ls, torch_gpu, kind, largest):
             nlt, ties = int(np.count_nonzero(u[r] < kth)), np.flatnonzero(u[r] == kth)
             assert nlt < k <= nlt + ties.size and ties.size > 1
             np.testing.assert_array_equal(gi[r, nlt:], ties[:k - nlt], err_msg=f"ties taken, row {r} k={k}")
+
+
+# ---- b2. every misalignment of the group loads ----
+
+ACOLS = CHUNK + 9
+
+
+@functools.lru_cache(maxsize=None)
+def misaligned_rows(bits, level):
+    """Eight rows of ACOLS order images that narrow after `level` (0 or NEVER), read-only."""
+    return frozen(np.stack([T.row_narrowing_at(level, ACOLS, 0x7300 + r, bits) for r in range(8)]))
+
+
+@pytest.mark.parametrize("largest", BOTH)
+@pytest.mark.parametrize("kind", ["i32", "f32", "bf16", "f16"])
+def test_every_group_misalignment(ls, torch_gpu, kind, largest):
+    """Eight rows of TK_CHUNK + 9 keys behind a 16-byte aligned base.  The width is odd, so row r
+    starts r elements into its 16 bytes: every misalignment 0 .. 7 of the loads of eight 16-bit keys
+    and, twice, all four of the loads of four words.  The second chunk is nine keys: a head, a tail
+    and at most two whole groups.  Two inputs per key type: rows that narrow after level 0, so every
+    later read is a read of the candidate buffer in quads (of a 16-bit call too), and rows that never
+    narrow, so every level and the final compaction read the raw input."""
+    assert ACOLS % 8 == 1 and -(-ACOLS // CHUNK) == 2
+    for level in (0, NEVER):
+        x = T.raw_of(misaligned_rows(T.bits_of(kind), level), kind, largest)
+        assert_select_narrows(ls, x, 5, kind, largest, [level] * 8)
+        check(ls, torch_gpu, x, 5, kind, largest, aligned=True)
 
 
 # ---- c. graph replay across levels ----

@@ -484,6 +484,57 @@ int labsort_sort16_device(const void *d_keys, size_t rows, size_t cols, int desc
                           void *stream);
 int labsort_sort16_workspace_status(const void *d_workspace, void *stream);
 
+/* ---- k-th key selection per row: which key is the k-th of every row, and where it is
+ * (torch.kthvalue, the lower median, nearest-rank quantiles, the threshold of top-k masking with a
+ * k per request; no lab.cu counterpart) ----
+ * d_keys is a dense rows x cols matrix, never written; key_type: all five (U32, I32, F32, BF16, F16),
+ * the 16-bit types with 2-byte elements and 2-byte alignment.  d_keys_out holds rows elements of the
+ * key type; d_idx_out holds rows 32-bit positions within the row, or is NULL (the keys written are
+ * the same either way).  With u as defined at labsort_topk_device (the order image, complemented
+ * when `largest`) and k_r the k of row r, row r's output is entry k_r - 1 of the stable ascending
+ * sort of the row's (u(key), position) pairs, written back untransformed: key and position are
+ * bit-identical to column k_r - 1 of labsort_sort_rows_device(descending = largest).  Among the ties
+ * of the k-th key the position is that of the (k_r - count_below)-th occurrence in position order.
+ * NaNs are equal, largest and come back as 0x7FFFFFFF / 0x7FFF; -0.0 < +0.0.
+ * d_k == NULL: every row uses the host k.  d_k != NULL: rows words in device memory, one k per row,
+ * and the host k is ignored.  A d_k[r] outside [1, cols] is clamped into that range by the kernel
+ * that reads it, which sets word 0 of the workspace's 256-byte header:
+ * labsort_kth_workspace_status (which synchronises `stream`) then returns LABSORT_ERR_ARG, as
+ * labsort_segments_workspace_status does for rejected offsets; the other rows' results are valid and
+ * nothing is written out of bounds.  Without such a row it returns LABSORT_OK.
+ * rows == 0 or cols == 0 launches nothing (LABSORT_OK before anything else is looked at).
+ * LABSORT_ERR_ARG before any launch: NULL d_keys / d_keys_out, a bad key type, d_k == NULL with
+ * k == 0 or k > cols, rows > (2^31 - 1) / cols, an odd d_keys / d_keys_out address with a 16-bit
+ * type, d_idx_out == d_keys_out, an output that overlaps the input, d_k or the other output (by the
+ * real element sizes), a missing or short workspace.
+ * cols <= labsort_kth_row_keys(): one launch (after the header's clearing), one workgroup per row.
+ * The row is loaded once as u and held in registers, every 8-bit digit level (four; two for the
+ * 16-bit types) runs on a histogram in LDS, and one ordered scan of the keys equal to the threshold
+ * gives the position.  The workspace is the header.
+ * Longer rows are cut into chunks of labsort_kth_row_keys() consecutive keys (the last may be
+ * partial; any cols and either 2-byte phase is fine).  Per level one kernel counts the level's
+ * digit of the keys that match the digits chosen so far, per chunk and per row, and one picks the
+ * digit at which the row's running count reaches k.  From the second level on a chunk is read only
+ * if it held a key of the digit chosen before; a skipped chunk's counts are zeroed.  With positions
+ * the last pick finds, from the chunks' counts, the one chunk that holds the k-th key, and one more
+ * kernel reads that chunk in position order; without them the last pick writes the key and no
+ * locate kernel runs.  No survivor list, no candidate buffer, no sort, no scatter, and no kernel
+ * waits on another workgroup.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on the
+ * host arguments only, so a captured call may be replayed on new keys and new d_k values in the
+ * same buffers.  The call clears what it relies on in the workspace (garbage or a reused workspace
+ * is fine).  labsort_kth_workspace_bytes takes no key type and never shrinks as rows or cols grow:
+ * 256 bytes for cols <= labsort_kth_row_keys(); above, the header, rows x 4 x 256 histogram words,
+ * the per-row states and rows x chunks x 256 count words (1/16 byte per key), each region 256-byte
+ * aligned.
+ * Timing hooks: the kernels count under LABSORT_K_TOPK. */
+size_t labsort_kth_row_keys(void);      /* longest row the one-launch path takes; info for tests */
+size_t labsort_kth_workspace_bytes(size_t rows, size_t cols);
+int labsort_kth_device(const void *d_keys, size_t rows, size_t cols, size_t k, const uint32_t *d_k, int largest,
+                       int key_type, void *d_keys_out, uint32_t *d_idx_out, void *d_workspace,
+                       size_t workspace_bytes, void *stream);
+int labsort_kth_workspace_status(const void *d_workspace, void *stream);
+
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +
  * ds_permute), stopping early once the tile is sorted: radix_sort_kernel's job. */

@@ -62,6 +62,7 @@ C_SYMBOLS = [
     "labsort_sort_rows_workspace_bytes", "labsort_sort_rows_device", "labsort_sort_rows_workspace_status",
     "labsort_sort16_chunk_keys", "labsort_sort16_workspace_bytes", "labsort_sort16_device",
     "labsort_sort16_workspace_status",
+    "labsort_kth_row_keys", "labsort_kth_workspace_bytes", "labsort_kth_device", "labsort_kth_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
 ]
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
@@ -210,6 +211,13 @@ def _load() -> ctypes.CDLL:
         L.labsort_sort16_workspace_bytes.argtypes = [sz, sz, i]
         L.labsort_sort16_device.argtypes = [p, sz, sz, i, i, p, p, p, sz, p]
         L.labsort_sort16_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_kth_device"):  # (as labsort_radix_path above)
+        L.labsort_kth_row_keys.restype = sz
+        L.labsort_kth_row_keys.argtypes = []
+        L.labsort_kth_workspace_bytes.restype = sz
+        L.labsort_kth_workspace_bytes.argtypes = [sz, sz]
+        L.labsort_kth_device.argtypes = [p, sz, sz, sz, p, i, i, p, p, p, sz, p]
+        L.labsort_kth_workspace_status.argtypes = [p, p]
     if hasattr(L, "labsort_key_order_bits"):  # (as labsort_radix_path above)
         for f in ("labsort_key_order_bits", "labsort_key_from_order_bits"):
             getattr(L, f).restype = ctypes.c_uint32
@@ -829,6 +837,68 @@ def sort(x, descending: bool = False, workspace=None, stream=None):
 def argsort(x, descending: bool = False, workspace=None, stream=None):
     """The indices of sort(x, descending): the stable argsort of every row."""
     return sort(x, descending=descending, workspace=workspace, stream=stream)[1]
+
+
+def kth_row_keys() -> int:
+    """Longest row kth_device selects in one launch (the row held in one workgroup's registers)."""
+    return int(lib.labsort_kth_row_keys())
+
+
+def kth_workspace_bytes(rows: int, cols: int) -> int:
+    return int(lib.labsort_kth_workspace_bytes(rows, cols))
+
+
+def _is_k_tensor(k) -> bool:
+    return hasattr(k, "data_ptr")
+
+
+def kth_device(d_keys, rows: int, cols: int, k, d_keys_out, d_idx_out=None, largest: bool = False, key: str = "u32",
+               workspace=None, stream=None) -> None:
+    """The k-th smallest (largest) key of every row of the dense rows x cols matrix d_keys into
+    d_keys_out (rows elements), and its position within the row into d_idx_out (rows int32 / uint32
+    words, or None): column k - 1 of sort_rows_device(descending=largest), bit for bit, without the
+    sort.  k is an int (1 <= k <= cols, every row), or an int32 CUDA tensor of `rows` elements, one k per
+    row, which is passed as d_k: a value outside [1, cols] is clamped on the device and reported by
+    kth_workspace_status as ERR_ARG, the other rows' results stay valid.  key as topk_device.  Workspace
+    and status follow topk_device: with a caller-owned `workspace` (>= kth_workspace_bytes(rows, cols))
+    the call stays asynchronous; without one it allocates, synchronises and checks."""
+    workspace, wsb, own = _workspace(workspace, lambda: kth_workspace_bytes(rows, cols))
+    d_k = _ptr(k) if _is_k_tensor(k) else None
+    _check(lib.labsort_kth_device(_ptr(d_keys), rows, cols, 0 if d_k is not None else int(k), d_k, 1 if largest else 0,
+                                  KEY[key], _ptr(d_keys_out), None if d_idx_out is None else _ptr(d_idx_out),
+                                  _ptr(workspace), wsb, _stream(stream)), "kth_device")
+    if own:
+        kth_workspace_status(workspace, stream)
+
+
+def kth_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_ARG if a row's k of the last kth_device call on
+    `workspace` lay outside [1, cols] (that row's result is the clamped k's)."""
+    _check(lib.labsort_kth_workspace_status(_ptr(workspace), _stream(stream)), "kth (status)")
+
+
+def kthvalue(x, k, largest: bool = False, workspace=None, stream=None):
+    """(values, indices) of the k-th smallest (largest) key of every row of x: kth_device with its
+    outputs allocated (torch.kthvalue(x, k, dim=-1) with the tie order fixed: of the k-th key's ties the
+    one that a stable sort puts k-th).  x: a contiguous 1-D (one row) or 2-D CUDA tensor of dtype int32,
+    float32, bfloat16 or float16; k: an int, or a contiguous int32 CUDA tensor of `rows` elements (one k
+    per row).  values has x's dtype and shape (rows,), indices is int32 (rows,).  TypeError before the
+    device is touched for another dtype, a non-contiguous or CPU tensor, or a k tensor that is not a
+    contiguous int32 CUDA tensor of `rows` elements.  The lower median of a row is k = (cols + 1) // 2.
+    NaNs are the largest keys here and equal to each other, so a row with NaNs still has a finite median
+    when fewer than half of its keys are NaN, where torch.median returns NaN.  Workspace and status as
+    kth_device."""
+    import torch
+    rows, cols, key = _dense_rows("kthvalue", x)
+    if isinstance(k, torch.Tensor):
+        if k.dtype != torch.int32 or not k.is_cuda or not k.is_contiguous() or k.dim() != 1 or k.shape[0] != rows:
+            raise TypeError(f"kthvalue: k must be an int or a contiguous int32 CUDA tensor of {rows} elements")
+    elif isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"kthvalue: k must be an int or an int32 CUDA tensor, got {type(k)}")
+    values = torch.empty((rows,), dtype=x.dtype, device=x.device)
+    indices = torch.empty((rows,), dtype=torch.int32, device=x.device)
+    kth_device(x, rows, cols, k, values, indices, largest=largest, key=key, workspace=workspace, stream=stream)
+    return values, indices
 
 
 def key_order_bits(word: int, key: str = "u32") -> int:

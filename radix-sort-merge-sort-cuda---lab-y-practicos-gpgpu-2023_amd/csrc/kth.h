@@ -1,0 +1,23 @@
+// kth.h -- k-th key selection per row (kth.hip): shapes.
+#pragma once
+#include "common.h"
+#include "topk.h"
+
+namespace labsort {
+
+constexpr int KTH_BLOCK = TK_BLOCK;     // every kernel of kth.hip: 1024 threads
+constexpr int KTH_KPT = 16;             // keys a thread of the one-launch kernel holds in registers
+constexpr int KTH_ROW_KEYS = TK_CHUNK;  // longest row of the one-launch path (labsort_kth_row_keys)
+static_assert(KTH_ROW_KEYS == KTH_BLOCK * KTH_KPT, "a short row is held in the registers of one workgroup");
+// Rows of up to KTH_SMALL_BLOCK * KTH_KPT keys: the one-launch kernel with a smaller workgroup and
+// fewer counter replicas, so that a thread still holds 16 keys and a level clears and folds 2048
+// LDS words, not 8192 (DESIGN.md §3.16 has the A/B; LABSORT_KTH_SMALL=0 builds without it).
+#ifndef LABSORT_KTH_SMALL
+#define LABSORT_KTH_SMALL 1
+#endif
+constexpr int KTH_SMALL_BLOCK = 256;
+constexpr int KTH_SMALL_SLOTS = 8;
+constexpr int KTH_SMALL_ROW_KEYS = LABSORT_KTH_SMALL ? KTH_SMALL_BLOCK * KTH_KPT : 0;
+constexpr int KTH_HDR_BYTES = TK_HDR_BYTES;  // word 0: a d_k[r] outside [1, cols] was clamped
+
+}  // namespace labsort

@@ -1,0 +1,485 @@
+// kth.hip -- k-th key selection per row (labsort_kth_device): which key is the k-th of every row
+// of a dense matrix, and where it is; k is one host value or one word per row in device memory.
+// All kernels work on u, where plain uint32 order is the order asked for (topk.hip's images):
+//   int32 / uint32   u = key ^ xr
+//   float32          u = f32_ord(key) ^ xr
+//   bfloat16/float16 u = (ord16(key) << 16) ^ xr, xr = largest ? 0xFFFF0000 : 0; two digit levels
+// The MSD radix select with 8-bit digits of topk.hip, stopped at the threshold: after the last
+// level the prefix is the k-th key and krem its rank among its ties.  No survivor list, no
+// candidate buffer, no inner sort, no scatter.
+//
+// Rows of up to KTH_ROW_KEYS keys: k_kth_short, one launch, one workgroup per row (256 threads up to
+// KTH_SMALL_ROW_KEYS keys, 1024 above).  The row is loaded once as u and held in registers; every
+// level counts into the slotted LDS histogram and every wave picks the same digit from it; the
+// position comes from one ordered block scan of the keys equal to the threshold.
+// Longer rows are cut into chunks of TK_CHUNK keys; per level
+//   k_kth_hist  counts the level's digit of the keys that match the prefix, per chunk (cnt, plain
+//               stores) and per row (hist, one atomic add per workgroup and digit).  From level 1
+//               on a chunk is read only if it held a key of the digit chosen at the level before
+//               (one word of its own row of cnt, read before the row is overwritten); a skipped
+//               chunk's row of cnt is zeroed, so that no later level takes stale counts for keys.
+//   k_kth_pick  one workgroup per row: the digit at which the running count reaches krem, and
+//               the next level's state.  Level 0 reads and validates the row's k.  After the last
+//               level: without positions it writes the key; with them it scans cnt[row][*][digit]
+//               along the chunks for the chunk that holds the krem-th tie and the rank within it.
+//   k_kth_locate  (with positions) one workgroup per row reads that one chunk in position order
+//               and writes the key and the position.
+// Every dependency between workgroups is a kernel boundary: no kernel waits on another workgroup.
+#include "kth.h"
+
+#include <type_traits>
+
+#include "devutil.h"
+#include "host.h"
+
+namespace labsort {
+
+// Per row and level: what the level's kernels read.  Level L's pick writes entry L + 1, so no
+// kernel reads a word that another workgroup of the same launch writes.
+struct KthState {
+    uint32_t prefix;  // digits chosen so far, in place (the top 8 * level bits)
+    uint32_t krem;    // rank of the k-th key among the keys that match the prefix (>= 1)
+    uint32_t d;       // the digit chosen at the level before: a chunk without such a key is skipped
+    uint32_t cstar;   // entry `levels` only: the chunk that holds the krem-th key equal to prefix (krem: within it)
+};
+
+struct KthArgs {
+    const void *keys;     // rows x cols, as the caller gave them (16-bit key types: 2-byte elements)
+    const uint32_t *d_k;  // [rows], or nullptr: k
+    uint32_t *hdr;        // word 0: a row's k was out of range
+    uint32_t *hist;       // [rows][TK_LEVELS][256]
+    uint32_t *cnt;        // [rows][nch][256]: each chunk's counts of the current level
+    KthState *st;         // [rows][TK_LEVELS + 1]
+    void *keys_out;       // [rows]
+    uint32_t *idx_out;    // [rows], or nullptr
+    uint32_t cols, k, nch, xr;
+};
+
+namespace {
+
+enum KthKey : int { KTH_INT, KTH_F32, KTH_BF16, KTH_F16 };
+constexpr bool kth_is16(int kt) { return kt == KTH_BF16 || kt == KTH_F16; }
+constexpr uint32_t kth_nan_t(int kt) { return kt == KTH_BF16 ? BF16_NAN_T : F16_NAN_T; }
+constexpr int kth_levels(int kt) { return kth_is16(kt) ? 2 : TK_LEVELS; }
+template <int KT>
+using kth_elem_t = std::conditional_t<kth_is16(KT), uint16_t, uint32_t>;
+template <int KT>
+constexpr int KTH_E = 16 / (int)sizeof(kth_elem_t<KT>);  // keys per 16-byte load
+
+// u of an element x of the input (ord16 reads the low half of x), and the key of an image
+template <int KT>
+__device__ __forceinline__ uint32_t kth_u(uint32_t x, uint32_t xr) {
+    if constexpr (kth_is16(KT)) return (ord16(x, kth_nan_t(KT)) << 16) ^ xr;
+    else if constexpr (KT == KTH_F32) return f32_ord(x) ^ xr;
+    else return x ^ xr;
+}
+__device__ __forceinline__ void kth_write_key(void *keys_out, uint32_t row, uint32_t u, uint32_t xr, int kt) {
+    const uint32_t w = u ^ xr;
+    if (kth_is16(kt)) static_cast<uint16_t *>(keys_out)[row] = (uint16_t)unord16(w >> 16);  // (either format)
+    else static_cast<uint32_t *>(keys_out)[row] = kt == KTH_F32 ? f32_unord(w) : w;
+}
+template <int KT>
+__device__ __forceinline__ const kth_elem_t<KT> *kth_row(const KthArgs &a, uint32_t row) {
+    return static_cast<const kth_elem_t<KT> *>(a.keys) + (size_t)row * a.cols;
+}
+// Group q of [beg, end) of a row as u (devutil.h, load_group)
+template <int KT>
+__device__ __forceinline__ uint32_t kth_load(const kth_elem_t<KT> *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
+                                             uint32_t xr, uint32_t (&u)[KTH_E<KT>], int64_t &i0) {
+    return load_group(base, beg, end, mis, q, u, i0, [xr](uint32_t x) { return kth_u<KT>(x, xr); });
+}
+
+// The row's k, clamped into [1, cols]; a k outside is reported in the header by the thread told to
+__device__ __forceinline__ uint32_t kth_k(const KthArgs &a, uint32_t row, bool report) {
+    const uint32_t kk = a.d_k ? a.d_k[row] : a.k;
+    if (kk >= 1u && kk <= a.cols) return kk;
+    if (report) a.hdr[0] = 1u;
+    return kk < 1u ? 1u : a.cols;
+}
+
+// The digit at which the running count of a level histogram (256 words, 16-byte aligned, global or
+// LDS) reaches krem: the d with count(< d) < krem <= count(<= d), topk.hip's rule (tk_pick, which
+// stays in its translation unit: moving it to a header would rebuild topk.hip's kernels, DESIGN.md
+// §3.15).  Called by a whole wave; the result is wave-uniform.
+struct KthPick {
+    uint32_t d, below;
+};
+__device__ __forceinline__ KthPick kth_pick(const uint32_t *hrow, uint32_t krem, uint32_t lane) {
+    const uint4 v = reinterpret_cast<const uint4 *>(hrow)[lane];  // digits 4 lane .. 4 lane + 3
+    const uint32_t c[4] = {v.x, v.y, v.z, v.w};
+    const uint32_t s = v.x + v.y + v.z + v.w;
+    const uint32_t x = wave_incl_scan(s, lane);
+    uint32_t run = x - s, d = 255u, below = x - c[3];  // (lane 63's default: the last digit)
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!found && run < krem && krem <= run + c[j]) {
+            found = true;
+            d = 4u * lane + (uint32_t)j;
+            below = run;
+        }
+        run += c[j];
+    }
+    const uint64_t m = __ballot(found);
+    const int srcl = m ? __ffsll((long long)m) - 1 : 63;  // (no lane: krem exceeds the row's count, which cannot happen)
+    KthPick p;
+    p.d = __shfl(d, srcl);
+    p.below = __shfl(below, srcl);
+    if (p.below >= krem) p.below = krem - 1u;  // keeps krem >= 1 whatever the histogram held
+    return p;
+}
+
+// Which of the set bits of em is the n-th (n >= 1, at most popc(em))
+template <int E>
+__device__ __forceinline__ uint32_t kth_nth_bit(uint32_t em, uint32_t n) {
+    uint32_t seen = 0u, at = 0u;
+#pragma unroll
+    for (int j = 0; j < E; ++j)
+        if ((em >> j) & 1u) {
+            if (++seen == n) at = (uint32_t)j;
+        }
+    return at;
+}
+
+// One step of an ordered scan over the workgroup: thread tid holds c items, carry is the count of
+// the steps before.  Returns the items before this thread's; adds the step's total to carry.
+// Two barriers: wsum and tot are free again on return.
+template <int BLOCK = KTH_BLOCK>
+__device__ __forceinline__ uint32_t kth_ordered_step(uint32_t c, uint32_t &carry, uint32_t *wsum, uint32_t *tot) {
+    const uint32_t ex = block_excl_scan<BLOCK, BLOCK>(c, wsum);
+    if (threadIdx.x == BLOCK - 1u) *tot = ex + c;
+    __syncthreads();
+    const uint32_t before = carry + ex;
+    carry += *tot;
+    __syncthreads();
+    return before;
+}
+
+// ---- rows of up to BLOCK * KTH_KPT keys: one workgroup of BLOCK threads, the row in registers;
+// SLOTS counter replicas per digit ----
+template <int KT, int BLOCK, int SLOTS>
+__global__ __launch_bounds__(BLOCK) void k_kth_short(KthArgs a) {
+    constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
+    constexpr int TG = T + 1;  // a row that starts inside a group has one group more
+    constexpr int NLEV = kth_levels(KT);
+    __shared__ uint32_t h[256 * SLOTS];
+    __shared__ __attribute__((aligned(16))) uint32_t hrow[256];
+    __shared__ uint32_t wsum[BLOCK / WAVE], tot;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t mis = group_mis(base, 0u), nq = group_count<E>(0u, a.cols, mis);  // <= T * BLOCK + 1
+    uint32_t u[TG][E], vm[TG];
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        const uint32_t q = (uint32_t)t * BLOCK + tid;
+        int64_t i0;
+        vm[t] = 0u;
+        if (q < nq) vm[t] = kth_load<KT>(base, 0u, a.cols, mis, q, a.xr, u[t], i0);
+        else
+#pragma unroll
+            for (int j = 0; j < E; ++j) u[t][j] = 0u;
+    }
+    uint32_t prefix = 0u, krem = kth_k(a, row, tid == 0u);
+    for (int level = 0; level < NLEV; ++level) {
+        const uint32_t shift = 24u - 8u * (uint32_t)level;
+        const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+        slot_hist_clear<SLOTS, BLOCK>(h, tid);
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u)
+                    slot_hist_add<SLOTS>(h, (u[t][j] >> shift) & 255u, tid);
+        __syncthreads();
+        if (tid < 256u) hrow[tid] = slot_hist_fold<SLOTS>(h, tid);
+        __syncthreads();
+        const KthPick p = kth_pick(hrow, krem, lane);  // (every wave: the same answer)
+        prefix |= p.d << shift;
+        krem -= p.below;
+    }
+    if (a.idx_out) {
+        // groups in position order: (t, tid); krem: the rank of the k-th key among the keys equal to prefix
+        uint32_t carry = 0u;
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+            if (carry >= krem) break;  // (uniform)
+            uint32_t em = 0u;
+#pragma unroll
+            for (int j = 0; j < E; ++j) em |= (((vm[t] >> j) & 1u) && u[t][j] == prefix ? 1u : 0u) << j;
+            const uint32_t c = (uint32_t)__popc(em);
+            const uint32_t before = kth_ordered_step<BLOCK>(c, carry, wsum, &tot);
+            if (c && before < krem && krem <= before + c) {
+                const uint32_t q = (uint32_t)t * BLOCK + tid;
+                a.idx_out[row] = E * q - mis + kth_nth_bit<E>(em, krem - before);
+            }
+        }
+    }
+    if (tid == 0u) kth_write_key(a.keys_out, row, prefix, a.xr, KT);
+}
+
+// ---- longer rows ----
+// Workgroup bx of a row counts chunks bx g .. bx g + g - 1 (topk.hip's k_tk_hist: at most
+// TK_MAX_HIST_WG workgroups add to a row's histogram).
+template <int KT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_kth_hist(KthArgs a, int level, uint32_t nx, uint32_t g) {
+    constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
+    __shared__ uint32_t h[256 * TK_SLOTS];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = blockIdx.x / nx, bx = blockIdx.x - row * nx;
+    const uint32_t c0 = bx * g;
+    if (c0 >= a.nch) return;
+    const uint32_t c1 = c0 + g < a.nch ? c0 + g : a.nch;
+    KthState st{0u, 0u, 0u, 0u};
+    if (level) st = a.st[(size_t)row * (TK_LEVELS + 1) + level];
+    const uint32_t shift = 24u - 8u * (uint32_t)level;
+    const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t xr = a.xr, prefix = st.prefix;
+    uint32_t acc = 0u;
+    for (uint32_t c = c0; c < c1; ++c) {
+        uint32_t *crow = a.cnt + ((size_t)row * a.nch + c) * 256u;
+        // the chunk's count of the digit chosen at the level before: every thread reads the same word,
+        // which within this launch only this workgroup writes, and only zero over zero before the barriers below
+        if (level && __builtin_amdgcn_readfirstlane(crow[st.d]) == 0u) {
+            if (tid < 256u) crow[tid] = 0u;  // (no stale counts of the level before)
+            continue;
+        }
+        slot_hist_clear<TK_SLOTS, KTH_BLOCK>(h, tid);
+        __syncthreads();
+        const uint32_t beg = c * TK_CHUNK, end = a.cols - beg > (uint32_t)TK_CHUNK ? beg + TK_CHUNK : a.cols;
+        const uint32_t mis = group_mis(base, beg), nq = group_count<E>(beg, end, mis);
+        for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)T * KTH_BLOCK) {
+            uint32_t u[T][E], vm[T];
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const uint32_t q = q0 + (uint32_t)t * KTH_BLOCK + tid;
+                int64_t i0;
+                vm[t] = 0u;
+                if (q < nq) vm[t] = kth_load<KT>(base, beg, end, mis, q, xr, u[t], i0);
+                else
+#pragma unroll
+                    for (int j = 0; j < E; ++j) u[t][j] = 0u;
+            }
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+#pragma unroll
+                for (int j = 0; j < E; ++j)
+                    if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u)
+                        slot_hist_add<TK_SLOTS>(h, (u[t][j] >> shift) & 255u, tid);
+        }
+        __syncthreads();
+        if (tid < 256u) {
+            const uint32_t sum = slot_hist_fold<TK_SLOTS>(h, tid);
+            crow[tid] = sum;
+            acc += sum;
+        }
+        __syncthreads();
+    }
+    if (tid < 256u && acc) atomicAdd(&a.hist[((size_t)row * TK_LEVELS + level) * 256u + tid], acc);
+}
+
+// last: the call's last level.  kt: the key type, for the key a call without positions writes here.
+__global__ __launch_bounds__(KTH_BLOCK) void k_kth_pick(KthArgs a, int level, int last, int kt) {
+    __shared__ uint32_t wsum[KTH_BLOCK / WAVE], tot, hit[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
+    KthState st{0u, 0u, 0u, 0u};
+    if (level) st = a.st[(size_t)row * (TK_LEVELS + 1) + level];
+    else st.krem = kth_k(a, row, tid == 0u);
+    const KthPick p = kth_pick(a.hist + ((size_t)row * TK_LEVELS + level) * 256u, st.krem, lane);
+    KthState ns;
+    ns.prefix = st.prefix | (p.d << (24u - 8u * (uint32_t)level));
+    ns.krem = st.krem - p.below;
+    ns.d = p.d;
+    ns.cstar = 0u;
+    KthState *out = a.st + (size_t)row * (TK_LEVELS + 1) + level + 1;
+    if (!last) {
+        if (tid == 0u) *out = ns;
+        return;
+    }
+    if (!a.idx_out) {
+        if (tid == 0u) kth_write_key(a.keys_out, row, ns.prefix, a.xr, kt);
+        return;
+    }
+    // the chunk that holds the krem-th key equal to the threshold, from the last level's counts of its
+    // last digit (zero for a skipped chunk), in steps of the block size
+    if (tid == 0u) {
+        hit[0] = 0u;
+        hit[1] = 1u;
+    }
+    __syncthreads();
+    uint32_t carry = 0u;
+    for (uint32_t b = 0; b < a.nch && carry < ns.krem; b += KTH_BLOCK) {  // (uniform)
+        const uint32_t c = b + tid;
+        const uint32_t v = c < a.nch ? a.cnt[((size_t)row * a.nch + c) * 256u + p.d] : 0u;
+        const uint32_t before = kth_ordered_step(v, carry, wsum, &tot);
+        if (v && before < ns.krem && ns.krem <= before + v) {
+            hit[0] = c;
+            hit[1] = ns.krem - before;
+        }
+    }
+    __syncthreads();
+    if (tid == 0u) {
+        ns.cstar = hit[0];
+        ns.krem = hit[1];
+        *out = ns;
+    }
+}
+
+template <int KT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_kth_locate(KthArgs a) {
+    constexpr int E = KTH_E<KT>;
+    __shared__ uint32_t wsum[KTH_BLOCK / WAVE], tot;
+    const uint32_t tid = threadIdx.x, row = blockIdx.x;
+    const KthState st = a.st[(size_t)row * (TK_LEVELS + 1) + kth_levels(KT)];
+    const uint32_t c = st.cstar < a.nch ? st.cstar : a.nch - 1u;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t beg = c * TK_CHUNK, end = a.cols - beg > (uint32_t)TK_CHUNK ? beg + TK_CHUNK : a.cols;
+    const uint32_t mis = group_mis(base, beg), nq = group_count<E>(beg, end, mis);
+    uint32_t carry = 0u;
+    for (uint32_t q0 = 0; q0 < nq && carry < st.krem; q0 += KTH_BLOCK) {  // (uniform)
+        const uint32_t q = q0 + tid;
+        uint32_t u[E], vm = 0u;
+        int64_t i0 = 0;
+        if (q < nq) vm = kth_load<KT>(base, beg, end, mis, q, a.xr, u, i0);
+        uint32_t em = 0u;
+#pragma unroll
+        for (int j = 0; j < E; ++j) em |= (((vm >> j) & 1u) && u[j] == st.prefix ? 1u : 0u) << j;
+        const uint32_t n = (uint32_t)__popc(em);
+        const uint32_t before = kth_ordered_step(n, carry, wsum, &tot);
+        if (n && before < st.krem && st.krem <= before + n)
+            a.idx_out[row] = (uint32_t)i0 + kth_nth_bit<E>(em, st.krem - before);  // (a set bit: inside [beg, end))
+    }
+    if (tid == 0u) kth_write_key(a.keys_out, row, st.prefix, a.xr, KT);
+}
+
+// kt: KthKey, the instantiation that runs
+template <int BLOCK, int SLOTS>
+hipError_t launch_kth_short_as(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
+    const unsigned grid = (unsigned)rows;
+    if (kt == KTH_BF16) k_kth_short<KTH_BF16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
+    else if (kt == KTH_F16) k_kth_short<KTH_F16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
+    else if (kt == KTH_F32) k_kth_short<KTH_F32, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
+    else k_kth_short<KTH_INT, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_kth_short(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
+    if (a.cols <= (uint32_t)KTH_SMALL_ROW_KEYS) return launch_kth_short_as<KTH_SMALL_BLOCK, KTH_SMALL_SLOTS>(a, rows, kt, s);
+    return launch_kth_short_as<KTH_BLOCK, TK_SLOTS>(a, rows, kt, s);
+}
+
+hipError_t launch_kth_hist(const KthArgs &a, size_t rows, int level, int kt, hipStream_t s) {
+    const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
+    const uint32_t nx = (a.nch + g - 1u) / g;
+    const unsigned grid = (unsigned)(rows * nx);
+    if (kt == KTH_BF16) k_kth_hist<KTH_BF16><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
+    else if (kt == KTH_F16) k_kth_hist<KTH_F16><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
+    else if (kt == KTH_F32) k_kth_hist<KTH_F32><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
+    else k_kth_hist<KTH_INT><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_kth_pick(const KthArgs &a, size_t rows, int level, int kt, hipStream_t s) {
+    k_kth_pick<<<(unsigned)rows, KTH_BLOCK, 0, s>>>(a, level, level == kth_levels(kt) - 1, kt);
+    return hipGetLastError();
+}
+
+hipError_t launch_kth_locate(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
+    const unsigned grid = (unsigned)rows;
+    if (kt == KTH_BF16) k_kth_locate<KTH_BF16><<<grid, KTH_BLOCK, 0, s>>>(a);
+    else if (kt == KTH_F16) k_kth_locate<KTH_F16><<<grid, KTH_BLOCK, 0, s>>>(a);
+    else if (kt == KTH_F32) k_kth_locate<KTH_F32><<<grid, KTH_BLOCK, 0, s>>>(a);
+    else k_kth_locate<KTH_INT><<<grid, KTH_BLOCK, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// header | hist | per-row states | per-chunk counts.  Header and histograms are the only words a
+// call relies on being clear.  A short row needs the header alone.
+struct KthLayout {
+    size_t nch, off_hist, zero_bytes, off_st, off_cnt, total;
+};
+KthLayout kth_layout(size_t rows, size_t cols) {
+    KthLayout L{};
+    Carver c;
+    c.take(KTH_HDR_BYTES);
+    L.zero_bytes = L.total = c.o;
+    if (rows == 0 || cols <= (size_t)KTH_ROW_KEYS) return L;
+    L.nch = (cols + TK_CHUNK - 1) / TK_CHUNK;
+    L.off_hist = c.take(rows * TK_LEVELS * 256 * sizeof(uint32_t));
+    L.zero_bytes = c.o;
+    L.off_st = c.take(rows * (TK_LEVELS + 1) * sizeof(KthState));
+    L.off_cnt = c.take(rows * L.nch * 256 * sizeof(uint32_t));
+    L.total = c.o;
+    return L;
+}
+
+}  // namespace
+
+}  // namespace labsort
+
+using namespace labsort;
+
+extern "C" {
+
+size_t labsort_kth_row_keys(void) { return (size_t)KTH_ROW_KEYS; }
+
+size_t labsort_kth_workspace_bytes(size_t rows, size_t cols) { return kth_layout(rows, cols).total; }
+
+int labsort_kth_device(const void *d_keys, size_t rows, size_t cols, size_t k, const uint32_t *d_k, int largest, int key_type,
+                       void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
+    static_assert(KTH_HDR_BYTES == 256, "labsort.h states the header's size");
+    if (rows == 0 || cols == 0) return LABSORT_OK;
+    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
+    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (!d_k && (k == 0 || k > cols)) return LABSORT_ERR_ARG;
+    if (rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    const bool k16 = key_type_is16(key_type);
+    const size_t esz = k16 ? 2 : 4;  // bytes per key
+    if (k16 && (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u)) return LABSORT_ERR_ARG;
+    if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
+    const size_t in_bytes = rows * cols * esz, ko_bytes = rows * esz, w_bytes = rows * 4;
+    if (ranges_overlap(d_keys, in_bytes, d_keys_out, ko_bytes)) return LABSORT_ERR_ARG;
+    if (d_idx_out && (ranges_overlap(d_keys, in_bytes, d_idx_out, w_bytes) || ranges_overlap(d_keys_out, ko_bytes, d_idx_out, w_bytes)))
+        return LABSORT_ERR_ARG;
+    if (d_k && ranges_overlap(d_k, w_bytes, d_keys_out, ko_bytes)) return LABSORT_ERR_ARG;
+    if (d_k && d_idx_out && ranges_overlap(d_k, w_bytes, d_idx_out, w_bytes)) return LABSORT_ERR_ARG;
+    const KthLayout L = kth_layout(rows, cols);
+    if (!d_ws || ws_bytes < L.total) return LABSORT_ERR_ARG;
+    const int kt = key_type == LABSORT_KEY_F32 ? KTH_F32 : key_type == LABSORT_KEY_BF16 ? KTH_BF16 : key_type == LABSORT_KEY_F16 ? KTH_F16 : KTH_INT;
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    KthArgs a{};
+    a.keys = d_keys;
+    a.d_k = d_k;
+    a.hdr = reinterpret_cast<uint32_t *>(ws);
+    a.keys_out = d_keys_out;
+    a.idx_out = d_idx_out;
+    a.cols = (uint32_t)cols;
+    a.k = (uint32_t)(d_k ? 1 : k);
+    a.nch = (uint32_t)L.nch;
+    // 16-bit keys: u = (ord16(key) << 16) ^ xr, its low half clear
+    a.xr = k16 ? (largest ? 0xFFFF0000u : 0u) : flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
+    HIP_TRY(launch_zero(ws, L.zero_bytes, s));  // (a kernel: graph-replayable)
+    TimingScope ts(LABSORT_K_TOPK, s);
+    if (cols <= (size_t)KTH_ROW_KEYS) {
+        HIP_TRY(launch_kth_short(a, rows, kt, s));
+        return LABSORT_OK;
+    }
+    a.hist = reinterpret_cast<uint32_t *>(ws + L.off_hist);
+    a.st = reinterpret_cast<KthState *>(ws + L.off_st);
+    a.cnt = reinterpret_cast<uint32_t *>(ws + L.off_cnt);
+    for (int level = 0; level < kth_levels(kt); ++level) {
+        HIP_TRY(launch_kth_hist(a, rows, level, kt, s));
+        HIP_TRY(launch_kth_pick(a, rows, level, kt, s));
+    }
+    if (d_idx_out) HIP_TRY(launch_kth_locate(a, rows, kt, s));
+    return LABSORT_OK;
+}
+
+int labsort_kth_workspace_status(const void *d_ws, void *stream) {
+    uint32_t w = 0;
+    if (const int st = read_ws_words(d_ws, &w, 1, as_stream(stream))) return st;
+    return w ? LABSORT_ERR_ARG : LABSORT_OK;
+}
+
+}  // extern "C"

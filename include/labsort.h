@@ -98,6 +98,24 @@ extern "C" {
  * gives the word back. */
 uint32_t labsort_key_order_bits(uint32_t word, int key_type);
 uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type);
+/* 8-byte keys: uint64, int64 and IEEE-754 binary64, accepted by labsort_sort64_device ONLY (every
+ * other entry that checks its key type returns LABSORT_ERR_ARG for them; values 5 to 7 are not
+ * assigned).  The order image is a uint64_t: U64 the word, I64 the word ^ (1 << 63), F64 the
+ * float32 contract at 64 bits,
+ *   ord64(x) = ~0             if (x & 0x7FFFFFFFFFFFFFFF) > 0x7FF0000000000000   (every NaN, either sign)
+ *            = ~x             if the sign bit is set
+ *            = x | (1 << 63)  otherwise
+ * so -inf < ... < -0.0 < +0.0 < ... < +inf < NaN, every NaN equal and last, ties (NaNs included)
+ * by position; non-NaN keys come back bit-exact and a NaN as 0x7FFFFFFFFFFFFFFF, by
+ *   unord64(o) = (o >> 63) ? (o & 0x7FFFFFFFFFFFFFFF) : ~o. */
+#define LABSORT_KEY_U64 8
+#define LABSORT_KEY_I64 9
+#define LABSORT_KEY_F64 10
+/* The 64-bit order image of an 8-byte key word and its inverse (host functions; the kernels compile
+ * the same definition).  Another key type gives the word back, as the 32-bit pair above does for
+ * these three. */
+uint64_t labsort_key_order_bits64(uint64_t word, int key_type);
+uint64_t labsort_key_from_order_bits64(uint64_t bits, int key_type);
 
 /* generator distributions (oracle/cpu_sort.cpp uses the same codes and formula) */
 #define LABSORT_DIST_U32 0
@@ -483,6 +501,61 @@ int labsort_sort16_device(const void *d_keys, size_t rows, size_t cols, int desc
                           void *d_keys_out, uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes,
                           void *stream);
 int labsort_sort16_workspace_status(const void *d_workspace, void *stream);
+
+/* ---- sort of rows of 8-byte keys of any length (int64 index tensors, packed (src << 32) | dst edge
+ * keys, 64-bit hashes, float64 scores; no lab.cu counterpart) ----
+ * labsort_sort_rows_device's contract for LABSORT_KEY_U64 / LABSORT_KEY_I64 / LABSORT_KEY_F64 only:
+ * d_keys is a dense rows x cols matrix of 8-byte elements, never written; with u(x) = image(x) ^
+ * (descending ? ~0 : 0), row r of the output is the stable ascending sort of the row's (u(key),
+ * position) pairs, keys written back untransformed (a NaN as 0x7FFFFFFFFFFFFFFF).  d_idx_out holds
+ * rows x cols 32-bit positions within the row, or is NULL (the keys written are the same either
+ * way); rows == 1 is the whole-array sort and d_idx_out then its stable argsort.
+ * rows == 0 or cols == 0 launches nothing (LABSORT_OK before anything else is looked at).
+ * LABSORT_ERR_ARG before any launch: any other key type, NULL d_keys / d_keys_out, rows >
+ * (2^31 - 1) / cols, a d_keys / d_keys_out address that is not 8-byte aligned, d_idx_out ==
+ * d_keys_out, an output that overlaps the input (by the 8-byte and 4-byte extents), a missing or
+ * short workspace.
+ * Every path runs only the 8-bit digits of u that vary, decided on the device:
+ * cols <= C = labsort_sort64_chunk_keys(): one launch after the header is cleared, one workgroup
+ * per row: the row is read once, the workgroup ORs u and ~u over its keys, runs the bytes in which
+ * both have a bit as stable LSD passes in LDS (a key's position is the slot it was loaded into) and
+ * writes the row once.  The plan is per row.  The workspace is the 256-byte header.
+ * Longer rows are cut into chunks of up to C consecutive keys (the last may be partial; any cols is
+ * fine).  The launch sequence is fixed: the header and the plan are cleared; every chunk ORs u and ~u
+ * of its keys into two plan words; one workgroup writes the plan of the call -- the active passes,
+ * their number m, and for the j-th of them its source (the input for j == 0, else what the pass
+ * before wrote) and its destination (the outputs if m - 1 - j is even, else the temporaries, so the
+ * last active pass lands in d_keys_out / d_idx_out whatever m is); then for each byte p = 0 .. 7 a
+ * count per (row, chunk) into a table [row][digit][chunk] by plain stores, an exclusive scan of the
+ * table along the chunks with the row's digit totals, and the scatter of every (row, chunk), each of
+ * which reads the plan and returns at once if pass p is inactive; last a kernel that works only for
+ * m == 0 (every key of the call has one image) and writes unord(ord(key)) and the column index.  The
+ * first active pass maps keys to images as it loads them and makes positions from where it loaded
+ * them, the last one maps back as it stores: about 32 bytes of memory traffic per key and active pass
+ * with positions, 24 without.  No kernel waits on another workgroup.  With d_idx_out == NULL no
+ * position is stored or loaded anywhere.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on the
+ * host arguments only, so a captured call may be replayed on new keys in the same buffers (the plan
+ * is decided again on every replay).
+ * labsort_sort64_workspace_bytes: 256 bytes for cols <= C; above, the header, the plan, the count
+ * table (rows x 256 x chunks-per-row words), the totals, rows * cols * 8 bytes of temporary keys
+ * and, with positions, rows * cols * 4 bytes of temporary positions, each region 256-byte aligned.
+ * It never shrinks as rows or cols grow, and a workspace sized with positions serves a call without
+ * them.  The call clears what it relies on: garbage or a reused workspace is fine.
+ * labsort_sort64_workspace_status synchronises `stream` and reads the header's first word; nothing
+ * sets it, so it returns LABSORT_OK (it exists so that callers treat every entry alike).
+ * labsort_sort64_passes synchronises `stream` and returns the plan of the last call on the
+ * workspace as a bitmask, bit p set if the pass on byte p of the image ran; 0 after a short-path
+ * call; -LABSORT_ERR_HIP (-LABSORT_ERR_ARG for a NULL workspace) on failure.  For tests and tools,
+ * as labsort_radix_path.
+ * Timing hooks: the kernels of both paths count under LABSORT_K_SEGSORT. */
+size_t labsort_sort64_chunk_keys(void);   /* C: keys per (row, chunk) workgroup; info for tests */
+size_t labsort_sort64_workspace_bytes(size_t rows, size_t cols, int with_positions);
+int labsort_sort64_device(const void *d_keys, size_t rows, size_t cols, int descending, int key_type,
+                          void *d_keys_out, uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes,
+                          void *stream);
+int labsort_sort64_workspace_status(const void *d_workspace, void *stream);
+int labsort_sort64_passes(const void *d_workspace, void *stream);
 
 /* ---- k-th key selection per row: which key is the k-th of every row, and where it is
  * (torch.kthvalue, the lower median, nearest-rank quantiles, the threshold of top-k masking with a

@@ -31,7 +31,8 @@ ALGO = {"radix": 0, "merge": 1, "radix1": 2, "auto": 3}
 # "f32": IEEE-754 order with -0.0 < +0.0 and every NaN equal and last; the device sorts, the segmented
 # sorts and top-k take it, the host-pointer and multi-GPU entries do not (labsort.h)
 # "bf16", "f16": 16-bit elements, the same order at 16 bits; top-k, the row sort and sort16 alone take them
-KEY = {"u32": 0, "i32": 1, "f32": 2, "bf16": 3, "f16": 4}
+# "u64", "i64", "f64": 8-byte elements, sort64 alone takes them (5 to 7 are not assigned)
+KEY = {"u32": 0, "i32": 1, "f32": 2, "bf16": 3, "f16": 4, "u64": 8, "i64": 9, "f64": 10}
 DIST = {"u32": 0, "u31": 1, "mod100": 2, "mod1000": 3, "sorted": 4, "reversed": 5, "const": 6, "lowbits": 7}
 KCLASS = {"histogram": 0, "onesweep": 1, "tile_sort": 2, "merge": 3, "partition": 4, "gsweep": 5, "gcopy": 6,
           "copy": 7, "merge4": 8, "segsort": 9, "topk": 10}
@@ -62,6 +63,9 @@ C_SYMBOLS = [
     "labsort_sort_rows_workspace_bytes", "labsort_sort_rows_device", "labsort_sort_rows_workspace_status",
     "labsort_sort16_chunk_keys", "labsort_sort16_workspace_bytes", "labsort_sort16_device",
     "labsort_sort16_workspace_status",
+    "labsort_sort64_chunk_keys", "labsort_sort64_workspace_bytes", "labsort_sort64_device",
+    "labsort_sort64_workspace_status", "labsort_sort64_passes",
+    "labsort_key_order_bits64", "labsort_key_from_order_bits64",
     "labsort_kth_row_keys", "labsort_kth_workspace_bytes", "labsort_kth_device", "labsort_kth_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
 ]
@@ -211,6 +215,17 @@ def _load() -> ctypes.CDLL:
         L.labsort_sort16_workspace_bytes.argtypes = [sz, sz, i]
         L.labsort_sort16_device.argtypes = [p, sz, sz, i, i, p, p, p, sz, p]
         L.labsort_sort16_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_sort64_device"):  # (as labsort_radix_path above)
+        L.labsort_sort64_chunk_keys.restype = sz
+        L.labsort_sort64_chunk_keys.argtypes = []
+        L.labsort_sort64_workspace_bytes.restype = sz
+        L.labsort_sort64_workspace_bytes.argtypes = [sz, sz, i]
+        L.labsort_sort64_device.argtypes = [p, sz, sz, i, i, p, p, p, sz, p]
+        L.labsort_sort64_workspace_status.argtypes = [p, p]
+        L.labsort_sort64_passes.argtypes = [p, p]
+        for f in ("labsort_key_order_bits64", "labsort_key_from_order_bits64"):
+            getattr(L, f).restype = u64
+            getattr(L, f).argtypes = [u64, i]
     if hasattr(L, "labsort_kth_device"):  # (as labsort_radix_path above)
         L.labsort_kth_row_keys.restype = sz
         L.labsort_kth_row_keys.argtypes = []
@@ -714,12 +729,18 @@ def topk_device(d_keys, rows: int, cols: int, k: int, d_keys_out, d_idx_out=None
         topk_workspace_status(workspace, stream)
 
 
-def _dense_rows(what: str, x):
-    """(rows, cols, key) of the tensor topk() and sort() take, or their TypeError."""
+def _dense_rows(what: str, x, wide: bool = False):
+    """(rows, cols, key) of the tensor topk(), kthvalue() and sort() take, or their TypeError.  wide:
+    the caller also takes the 8-byte dtypes (sort and argsort alone)."""
     import torch
     keys = {torch.int32: "i32", torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+    if wide and hasattr(lib, "labsort_sort64_device"):  # (an older build loaded through LABSORT_LIBRARY has none)
+        keys.update({torch.int64: "i64", torch.float64: "f64"})
+        if hasattr(torch, "uint64"):
+            keys[torch.uint64] = "u64"
     if not isinstance(x, torch.Tensor) or x.dtype not in keys:
-        raise TypeError(f"{what}: int32, float32, bfloat16 or float16 tensor expected, got {getattr(x, 'dtype', type(x))}")
+        names = "int32, float32, bfloat16" + (", float16, int64, uint64 or float64" if wide else " or float16")
+        raise TypeError(f"{what}: {names} tensor expected, got {getattr(x, 'dtype', type(x))}")
     if x.dim() not in (1, 2) or not x.is_contiguous():
         raise TypeError(f"{what}: a contiguous 1-D or 2-D tensor expected")
     if not x.is_cuda:
@@ -807,6 +828,48 @@ def sort16_workspace_status(workspace, stream=None) -> None:
     _check(lib.labsort_sort16_workspace_status(_ptr(workspace), _stream(stream)), "sort16 (status)")
 
 
+def sort64_chunk_keys() -> int:
+    """C: keys per (row, chunk) workgroup of sort64_device; rows of up to C keys are sorted by one
+    workgroup in LDS."""
+    return int(lib.labsort_sort64_chunk_keys())
+
+
+def sort64_workspace_bytes(rows: int, cols: int, positions: bool = True) -> int:
+    return int(lib.labsort_sort64_workspace_bytes(rows, cols, 1 if positions else 0))
+
+
+def sort64_device(d_keys, rows: int, cols: int, d_keys_out, d_idx_out=None, descending: bool = False,
+                  key: str = "i64", workspace=None, stream=None) -> None:
+    """sort_rows_device's contract for key="u64" / "i64" / "f64" alone: d_keys and d_keys_out hold 8-byte
+    elements, d_idx_out stays 32-bit.  Stable radix passes with 8-bit digits over the keys' 64-bit
+    order images, of which only those whose digit varies run (decided on the device: keys below 2^32
+    take four passes).  Workspace and status as sort_rows_device: with a caller-owned `workspace` (>=
+    sort64_workspace_bytes(rows, cols, d_idx_out is not None)) the call stays asynchronous; without
+    one it allocates, synchronises and checks."""
+    workspace, wsb, own = _workspace(workspace, lambda: sort64_workspace_bytes(rows, cols, d_idx_out is not None))
+    _check(lib.labsort_sort64_device(_ptr(d_keys), rows, cols, 1 if descending else 0, KEY[key], _ptr(d_keys_out),
+                                     None if d_idx_out is None else _ptr(d_idx_out), _ptr(workspace), wsb,
+                                     _stream(stream)), "sort64_device")
+    if own:
+        sort64_workspace_status(workspace, stream)
+
+
+def sort64_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream` and check the workspace's status word, as sort_rows_workspace_status
+    (no kernel of sort64_device sets it)."""
+    _check(lib.labsort_sort64_workspace_status(_ptr(workspace), _stream(stream)), "sort64 (status)")
+
+
+def sort64_passes(workspace, stream=None) -> int:
+    """Synchronise `stream`; the plan of the last sort64_device call on `workspace` as a bitmask: bit p
+    set if the pass on byte p of the order image ran.  0 after a call with cols <= sort64_chunk_keys()
+    (each row plans for itself in LDS)."""
+    r = int(lib.labsort_sort64_passes(_ptr(workspace), _stream(stream)))
+    if r < 0:
+        _check(-r, "sort64_passes")
+    return r
+
+
 def _sort16_routed(rows: int, cols: int, key: str, workspace) -> bool:
     """Does sort() hand this call to sort16_device?  bfloat16 / float16 rows past the LDS tile, when
     the caller passed no workspace (one sized by sort_rows_workspace_bytes belongs to
@@ -821,12 +884,16 @@ def sort(x, descending: bool = False, workspace=None, stream=None):
     values has x's dtype and shape, indices is int32 of the same shape.  TypeError for another dtype,
     a non-contiguous or a CPU tensor, before the device is touched.  Workspace and status as
     sort_rows_device.  bfloat16 / float16 rows longer than segment_tile_keys() without a caller's
-    workspace are sorted by sort16_device: the same result by contract."""
+    workspace are sorted by sort16_device: the same result by contract.  int64, float64 and (where
+    torch has it) uint64 tensors are sorted by sort64_device; a caller's workspace for them is one
+    sized by sort64_workspace_bytes.  indices is int32 for every dtype."""
     import torch
-    rows, cols, key = _dense_rows("sort", x)
+    rows, cols, key = _dense_rows("sort", x, wide=True)
     values = torch.empty_like(x)
     indices = torch.empty(x.shape, dtype=torch.int32, device=x.device)
-    if _sort16_routed(rows, cols, key, workspace):
+    if key in ("u64", "i64", "f64"):
+        sort64_device(x, rows, cols, values, indices, descending=descending, key=key, workspace=workspace, stream=stream)
+    elif _sort16_routed(rows, cols, key, workspace):
         sort16_device(x, rows, cols, values, indices, descending=descending, key=key, stream=stream)
     else:
         sort_rows_device(x, rows, cols, values, indices, descending=descending, key=key, workspace=workspace,

@@ -181,6 +181,34 @@ __device__ __forceinline__ uint32_t block_diff_bits(uint32_t a, uint32_t o, uint
     return aa ^ oo;
 }
 
+// OR of a 64-bit pair over the wave (all lanes get both)
+__device__ __forceinline__ void wave_or2(uint64_t &a, uint64_t &b) {
+    uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] |= __shfl_xor(w[i], off);
+    a = ((uint64_t)w[1] << 32) | w[0];
+    b = ((uint64_t)w[3] << 32) | w[2];
+}
+// ... and over the workgroup's W waves, through red (2 * W words of 64 bits).  Contains a barrier.
+template <int W>
+__device__ __forceinline__ void block_or2(uint64_t &a, uint64_t &b, uint64_t *red, uint32_t lane, uint32_t wid) {
+    wave_or2(a, b);
+    if (lane == 0) {
+        red[2 * wid] = a;
+        red[2 * wid + 1] = b;
+    }
+    __syncthreads();
+    a = 0ull;
+    b = 0ull;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        a |= red[2 * w];
+        b |= red[2 * w + 1];
+    }
+}
+
 // Inclusive prefix sum of x over the wave's lanes (all 64 active).
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
 #pragma unroll

@@ -1,5 +1,6 @@
-// host.h -- what every host driver of liblabsort.so needs, each defined once (internal:
-// api.hip, kernels.hip, merge4.hip, gsweep.hip, segsort.hip, topk.hip, rowsort.hip).
+// host.h -- what every host driver of liblabsort.so needs, each defined once (internal: every
+// .hip file with an entry of the C ABI or a launch, and the headers that launch: seg_kernels.h,
+// chunk_pass.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,7 @@ inline bool device_key_type_ok(int key_type) { return key_type_ok(key_type) || k
 inline bool key_type_is16(int key_type) { return key_type == LABSORT_KEY_BF16 || key_type == LABSORT_KEY_F16; }
 inline uint32_t nan_t16(int key_type) { return key_type == LABSORT_KEY_BF16 ? BF16_NAN_T : F16_NAN_T; }
 inline bool topk_key_type_ok(int key_type) { return device_key_type_ok(key_type) || key_type_is16(key_type); }
+inline bool key_type_is64(int kt) { return kt == LABSORT_KEY_U64 || kt == LABSORT_KEY_I64 || kt == LABSORT_KEY_F64; }  // (sort64.hip alone)
 // Key/value calls are in place only as a whole: one side aliased and the other not would
 // read payloads that the key side's passes already overwrote.  Keys and payloads never
 // share their output.
@@ -55,15 +57,15 @@ inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t b
     return a0 < b0 + bbytes && b0 < a0 + abytes;
 }
 
-// The argument checks of a dense call (top-k, row sort) that reads rows x cols keys and writes
-// rows x k keys and, with idx_out, as many 32-bit positions; rows, k != 0.  LABSORT_OK or LABSORT_ERR_ARG.
+// The argument checks of a dense call (top-k, row sort, the 16- and 64-bit sorts) that reads rows x
+// cols keys and writes rows x k keys and, with idx_out, as many 32-bit positions; rows, k != 0, and
+// key_type is one that the entry takes: it gives the element's size, to which 2- and 8-byte keys
+// must be aligned.  LABSORT_OK or LABSORT_ERR_ARG.
 inline int dense_rows_args(const void *keys, size_t rows, size_t cols, size_t k, int key_type, const void *keys_out,
                            const void *idx_out) {
     if (!keys || !keys_out) return LABSORT_ERR_ARG;
-    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
-    const bool k16 = key_type_is16(key_type);
-    const size_t esz = k16 ? 2 : 4;  // bytes per key
-    if (k16 && (((uintptr_t)keys | (uintptr_t)keys_out) & 1u)) return LABSORT_ERR_ARG;
+    const size_t esz = key_type_is16(key_type) ? 2 : key_type_is64(key_type) ? 8 : 4;  // bytes per key
+    if (esz != 4 && (((uintptr_t)keys | (uintptr_t)keys_out) & (esz - 1))) return LABSORT_ERR_ARG;
     if (k > cols || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
     if (idx_out == keys_out) return LABSORT_ERR_ARG;
     if (ranges_overlap(keys, rows * cols * esz, keys_out, rows * k * esz)) return LABSORT_ERR_ARG;

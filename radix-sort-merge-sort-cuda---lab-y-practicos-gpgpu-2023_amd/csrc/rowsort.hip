@@ -283,6 +283,7 @@ int labsort_sort_rows_device(const void *d_keys, size_t rows, size_t cols, int d
                              uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
     static_assert(TK_HDR_BYTES == SEG_HDR_BYTES, "one header, one status word, on both paths");
     if (rows == 0 || cols == 0) return LABSORT_OK;
+    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (const int rc = dense_rows_args(d_keys, rows, cols, cols, key_type, d_keys_out, d_idx_out)) return rc;
     const bool k16 = key_type_is16(key_type);
     if (!d_ws || ws_bytes < labsort_sort_rows_workspace_bytes(rows, cols)) return LABSORT_ERR_ARG;

@@ -14,21 +14,10 @@ namespace labsort {
 #ifndef LABSORT_S16_KPT
 #define LABSORT_S16_KPT 16  // keys per thread (A/B build knob: 8 = 8192-key chunks of 1024 threads, two per CU)
 #endif
-#ifndef LABSORT_S16_PAIR
-#define LABSORT_S16_PAIR 0  // 1: aligned neighbours of a run leave the scatter as one 4-byte store (A/B build knob)
-#endif
-constexpr int S16_PAIR = LABSORT_S16_PAIR;
 constexpr int S16_BLOCK = LABSORT_S16_BLOCK;
 constexpr int S16_KPT = LABSORT_S16_KPT;
 constexpr int S16_CHUNK = S16_BLOCK * S16_KPT;  // 16384 keys
-static_assert(S16_KPT % 2 == 0 && S16_BLOCK % 256 == 0, "ranks are packed in pairs; 256 threads hold the digits");
-static_assert(S16_CHUNK <= 65536, "a key's place in its chunk travels through LDS as 16 bits");
-constexpr int S16_SLOTS = 32;  // LDS counter replicas per digit in the count kernel: one per bank, as k_tk_hist
-// The scan along the chunk axis of the count table [row][digit][chunk]: up to S16_SCAN_SERIAL
-// chunks per row one thread per (row, digit) walks its run of the table; above, one workgroup per
-// (row, digit) scans it in steps of S16_SCAN_BLOCK chunks.
-constexpr uint32_t S16_SCAN_SERIAL = 64;
-constexpr int S16_SCAN_BLOCK = 1024;
+// (the count table, its scan and their constants, what the shapes must satisfy: chunk_pass.h)
 
 // rowsort.hip: the LDS path of labsort_sort_rows_device behind its argument checks, for a shape
 // that rs_lds_path takes; d_ws: the 256-byte header.  labsort_sort16_device forwards its short

@@ -37,13 +37,7 @@ __host__ __device__ inline uint64_t key64_unord(uint64_t o, int kt) {
 constexpr int S64_BLOCK = LABSORT_S64_BLOCK;
 constexpr int S64_KPT = LABSORT_S64_KPT;
 constexpr int S64_CHUNK = S64_BLOCK * S64_KPT;  // 8192 keys
-static_assert(S64_KPT % 2 == 0 && S64_BLOCK % 256 == 0, "ranks are packed in pairs; 256 threads hold the digits");
-static_assert(S64_CHUNK <= 65536, "a key's place in its row or chunk travels through LDS as 16 bits");
-constexpr int S64_SLOTS = 32;  // LDS counter replicas per digit in the count kernel (as sort16's)
-// The scan along the chunk axis of the count table, as sort16's: a thread per (row, digit) up to
-// S64_SCAN_SERIAL chunks per row, above it a workgroup per (row, digit) in steps of S64_SCAN_BLOCK.
-constexpr uint32_t S64_SCAN_SERIAL = 64;
-constexpr int S64_SCAN_BLOCK = 1024;
+// (the count table, its scan and their constants, what the shapes must satisfy: chunk_pass.h)
 
 // ---- the plan of a long-path call, decided on the device (k_s64_plan) from the OR of u and the
 // OR of ~u over every key of the call: byte p varies where (or_u & or_n) has a bit of byte p.

@@ -10,13 +10,14 @@
 //                      S64_BLOCK threads, the fewest whose S64_KPT keys each hold the row.
 //   longer rows        cut into chunks of up to S64_CHUNK consecutive keys.  k_s64_bits ORs u and ~u
 //                      of every chunk into two plan words, k_s64_plan writes the plan of the call
-//                      (sort64.h, S64Plan), then for each byte p the three launches of sort16.hip --
+//                      (sort64.h, S64Plan), then for each byte p the three launches of chunk_pass.h --
 //                      count, scan, scatter -- each of which reads the plan and returns if pass p is
 //                      inactive, and k_s64_same, which works only when no pass is active.  The
 //                      first active pass reads the input and maps it, the last one maps back; the
 //                      passes between carry u and the positions through the outputs and the
 //                      temporaries in turn, so that the last one lands in the outputs.
 // No kernel waits on another workgroup.  Without positions none is stored or loaded anywhere.
+#include "chunk_pass.h"
 #include "devutil.h"
 #include "host.h"
 #include "segsort.h"
@@ -28,7 +29,6 @@ namespace labsort {
 namespace {
 
 constexpr int S64_W = S64_BLOCK / WAVE;
-constexpr uint32_t S64_KPW = (uint32_t)WAVE * S64_KPT;  // keys of a chunk that one wave ranks: a contiguous stripe
 
 struct S64Args {
     const uint64_t *kin;  // the input
@@ -44,51 +44,6 @@ struct S64Args {
     uint32_t cols, nch;
     int kt;
 };
-
-__device__ __forceinline__ uint32_t digit_of(uint64_t u, uint32_t shift) { return (uint32_t)(u >> shift) & 0xFFu; }
-
-// OR of a 64-bit pair over the wave (all lanes get both)
-__device__ __forceinline__ void wave_or2(uint64_t &a, uint64_t &b) {
-    uint32_t w[4] = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] |= __shfl_xor(w[i], off);
-    a = ((uint64_t)w[1] << 32) | w[0];
-    b = ((uint64_t)w[3] << 32) | w[2];
-}
-// ... and over the workgroup's W waves, through red (2 * W words of 64 bits).  Contains a barrier.
-template <int W>
-__device__ __forceinline__ void block_or2(uint64_t &a, uint64_t &b, uint64_t *red, uint32_t lane, uint32_t wid) {
-    wave_or2(a, b);
-    if (lane == 0) {
-        red[2 * wid] = a;
-        red[2 * wid + 1] = b;
-    }
-    __syncthreads();
-    a = 0ull;
-    b = 0ull;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        a |= red[2 * w];
-        b |= red[2 * w + 1];
-    }
-}
-
-// the chunk of a (row, chunk) workgroup: its first column and its length 1 .. S64_CHUNK
-struct S64Chunk {
-    uint32_t row, beg, n;
-    size_t rowoff;
-};
-__device__ __forceinline__ S64Chunk s64_chunk(const S64Args &a) {
-    S64Chunk c;
-    c.row = blockIdx.x / a.nch;
-    const uint32_t chunk = blockIdx.x - c.row * a.nch;
-    c.rowoff = (size_t)c.row * a.cols;
-    c.beg = chunk * (uint32_t)S64_CHUNK;
-    c.n = a.cols - c.beg > (uint32_t)S64_CHUNK ? (uint32_t)S64_CHUNK : a.cols - c.beg;
-    return c;
-}
 
 // ---------------------------------------------------------------------------------
 // short rows: one workgroup of BLOCK threads per row of up to BLOCK * S64_KPT keys
@@ -113,18 +68,15 @@ __global__ __launch_bounds__(BLOCK) void k_s64_row(S64Args a) {
     const size_t rowoff = (size_t)blockIdx.x * a.cols;
     const uint32_t n = a.cols;  // 1 .. BLOCK * S64_KPT
     probe_lane_order(sm.probe, &sm.ordered, lane, wid);
-    // wave wid holds slots ws0 .. ws0 + S64_KPW - 1, slot ws0 + j * 64 + lane in k[j]: in order of
-    // position over (wave, j, lane).  Slots from n on are padding, u = ~0: digit 255 in every pass
-    // and behind every key, so the first n slots of every digit order hold the keys.
-    const uint32_t ws0 = wid * S64_KPW;
-    uint32_t ng = ws0 < n ? (n - ws0 + 63u) / 64u : 0u;  // 64-key groups of this wave that hold keys (wave-uniform)
-    if (ng > (uint32_t)S64_KPT) ng = S64_KPT;
+    // the row into registers (chunk_pass.h, WaveStripe); the padding is u = ~0
+    const WaveStripe<S64_KPT> w(wid, n);
+    using Carry = std::conditional_t<IDX, uint16_t, NoCarry>;
     uint64_t k[S64_KPT];
     uint32_t v[IDX ? S64_KPT : 1];
     uint64_t ou = 0ull, on = 0ull;
 #pragma unroll
     for (int j = 0; j < S64_KPT; ++j) {
-        const uint32_t i = ws0 + (uint32_t)j * WAVE + lane;
+        const uint32_t i = w.slot(j, lane);
         k[j] = ~0ull;
         if (i < n) {
             k[j] = key64_ord(a.kin[rowoff + i], a.kt) ^ a.x64;
@@ -136,33 +88,18 @@ __global__ __launch_bounds__(BLOCK) void k_s64_row(S64Args a) {
     block_or2<W>(ou, on, sm.red, lane, wid);  // (its barrier publishes the probe's answer too)
     const uint64_t vary = ou & on;
     const bool atomic_rank = lane_order_probed(&sm.ordered);
-    uint32_t *wh = sm.whist + wid * 256u;
     for (uint32_t p = 0; p < 8u; ++p) {  // (uniform over the workgroup)
         const uint32_t shift = 8u * p;
         if (((vary >> shift) & 0xFFull) == 0ull) continue;
-        for (uint32_t i = lane; i < 256u; i += WAVE) wh[i] = 0u;
         uint32_t rank[S64_KPT / 2] = {};
-#pragma unroll
-        for (int j = 0; j < S64_KPT; ++j) {
-            uint32_t r = 0u;
-            if ((uint32_t)j < ng) r = rank8(wh, digit_of(k[j], shift), lane, atomic_rank);
-            set16(rank, j, r);
-        }
-        __syncthreads();  // every wave's counters are complete
-        fold_digit_offsets<BLOCK, W>(sm.whist, sm.wsum);
+        chunk_rank<BLOCK>(k, shift, w.ng, sm.whist, sm.wsum, rank, atomic_rank, lane, wid);
+        __syncthreads();
+        chunk_reorder<false>(k, v, shift, w.ng, sm.whist + wid * 256u, rank, sm.keys, reinterpret_cast<Carry *>(sm.pay));
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < S64_KPT; ++j)
-            if ((uint32_t)j < ng) {  // (ranked slots number the keys and the padding of the last group: dst < BLOCK * S64_KPT)
-                const uint32_t dst = wh[digit_of(k[j], shift)] + get16(rank, j);
-                sm.keys[dst] = k[j];
-                if constexpr (IDX) sm.pay[dst] = (uint16_t)v[j];
-            }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < S64_KPT; ++j)
-            if ((uint32_t)j < ng) {
-                const uint32_t i = ws0 + (uint32_t)j * WAVE + lane;
+            if ((uint32_t)j < w.ng) {
+                const uint32_t i = w.slot(j, lane);
                 k[j] = sm.keys[i];
                 if constexpr (IDX) v[j] = sm.pay[i];
             }
@@ -170,7 +107,7 @@ __global__ __launch_bounds__(BLOCK) void k_s64_row(S64Args a) {
     }
 #pragma unroll
     for (int j = 0; j < S64_KPT; ++j) {
-        const uint32_t i = ws0 + (uint32_t)j * WAVE + lane;
+        const uint32_t i = w.slot(j, lane);
         if (i < n) {
             a.kout[rowoff + i] = key64_unord(k[j] ^ a.x64, a.kt);
             if constexpr (IDX) a.pout[rowoff + i] = v[j];
@@ -184,7 +121,7 @@ __global__ __launch_bounds__(BLOCK) void k_s64_row(S64Args a) {
 __global__ __launch_bounds__(S64_BLOCK) void k_s64_bits(S64Args a) {
     __shared__ uint64_t red[2 * S64_W];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-    const S64Chunk c = s64_chunk(a);
+    const Chunk c = chunk_of<S64_CHUNK>(a.cols, a.nch);
     const uint64_t *base = a.kin + c.rowoff + c.beg;
     uint64_t ou = 0ull, on = 0ull;
 #pragma unroll
@@ -253,19 +190,24 @@ __device__ __forceinline__ S64Pass s64_pass(const S64Args &a, uint32_t p) {
     q.pd = dst == S64_OUT ? a.pout : a.tp;
     return q;
 }
-__device__ __forceinline__ bool s64_active(const S64Args &a, uint32_t p) { return (a.plan->mask >> p) & 1u; }
+// does pass p run?  (the gate of chunk_pass.h's scan, and of the count and the scatter)
+struct S64Gate {
+    const S64Plan *plan;
+    uint32_t p;
+    __device__ __forceinline__ bool operator()() const { return (plan->mask >> p) & 1u; }
+};
 
 // ---------------------------------------------------------------------------------
 // long rows: a pass
 // ---------------------------------------------------------------------------------
 // count: digit p of the chunk's keys
 __global__ __launch_bounds__(S64_BLOCK) void k_s64_count(S64Args a, uint32_t p) {
-    if (!s64_active(a, p)) return;
-    __shared__ uint32_t h[256 * S64_SLOTS];
+    if (!S64Gate{a.plan, p}()) return;
+    __shared__ uint32_t h[256 * CP_SLOTS];
     const S64Pass q = s64_pass(a, p);
     const uint32_t shift = 8u * p, tid = threadIdx.x;
-    const S64Chunk c = s64_chunk(a);
-    slot_hist_clear<S64_SLOTS, S64_BLOCK>(h, tid);
+    const Chunk c = chunk_of<S64_CHUNK>(a.cols, a.nch);
+    slot_hist_clear<CP_SLOTS, S64_BLOCK>(h, tid);
     __syncthreads();
     const uint64_t *base = q.ks + c.rowoff + c.beg;
     uint64_t u[S64_KPT];
@@ -277,53 +219,10 @@ __global__ __launch_bounds__(S64_BLOCK) void k_s64_count(S64Args a, uint32_t p) 
 #pragma unroll
     for (int j = 0; j < S64_KPT; ++j) {
         const uint32_t i = (uint32_t)j * S64_BLOCK + tid;
-        if (i < c.n) slot_hist_add<S64_SLOTS>(h, digit_of(q.first ? key64_ord(u[j], a.kt) ^ a.x64 : u[j], shift), tid);
+        if (i < c.n) slot_hist_add<CP_SLOTS>(h, digit_of(q.first ? key64_ord(u[j], a.kt) ^ a.x64 : u[j], shift), tid);
     }
     __syncthreads();
-    if (tid < 256u) a.cnt[((size_t)c.row * 256u + tid) * a.nch + (blockIdx.x - c.row * a.nch)] = slot_hist_fold<S64_SLOTS>(h, tid);
-}
-
-// scan, few chunks per row: thread i walks the nch words of (row, digit) i = row * 256 + digit
-__global__ __launch_bounds__(256) void k_s64_scan_serial(S64Args a, uint32_t p, uint32_t nrd) {
-    if (!s64_active(a, p)) return;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= nrd) return;
-    uint32_t *w = a.cnt + (size_t)i * a.nch;
-    uint32_t run = 0u;
-    for (uint32_t c = 0; c < a.nch; ++c) {
-        const uint32_t t = w[c];
-        w[c] = run;
-        run += t;
-    }
-    a.tot[i] = run;
-}
-
-// scan, many chunks per row: workgroup i scans the nch words of (row, digit) i in steps of its width
-__global__ __launch_bounds__(S64_SCAN_BLOCK) void k_s64_scan_block(S64Args a, uint32_t p) {
-    if (!s64_active(a, p)) return;
-    constexpr int NW = S64_SCAN_BLOCK / WAVE;
-    __shared__ uint32_t wsum[NW];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6, nch = a.nch;
-    uint32_t *w = a.cnt + (size_t)blockIdx.x * nch;
-    uint32_t carry = 0u;
-    for (uint32_t c0 = 0; c0 < nch; c0 += (uint32_t)S64_SCAN_BLOCK) {  // (uniform over the workgroup)
-        const uint32_t c = c0 + tid;
-        const uint32_t v = c < nch ? w[c] : 0u;
-        const uint32_t x = wave_incl_scan(v, lane);
-        if (lane == 63u) wsum[wid] = x;
-        __syncthreads();
-        uint32_t add = 0u, total = 0u;
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            const uint32_t t = wsum[i];
-            if ((uint32_t)i < wid) add += t;
-            total += t;
-        }
-        if (c < nch) w[c] = carry + add + x - v;
-        carry += total;
-        __syncthreads();  // (wsum is written again in the next step)
-    }
-    if (tid == 0u) a.tot[blockIdx.x] = carry;
+    if (tid < 256u) a.cnt[chunk_cnt_at(c, tid, a.nch)] = slot_hist_fold<CP_SLOTS>(h, tid);
 }
 
 template <bool IDX>
@@ -340,83 +239,57 @@ struct S64Smem {
 
 template <bool IDX>
 __global__ __launch_bounds__(S64_BLOCK) void k_s64_scatter(S64Args a, uint32_t p) {
-    if (!s64_active(a, p)) return;
+    if (!S64Gate{a.plan, p}()) return;
     __shared__ S64Smem<IDX> sm;
     const S64Pass q = s64_pass(a, p);
     const uint32_t shift = 8u * p;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const S64Chunk c = s64_chunk(a);
-    const uint32_t n = c.n, chunk = blockIdx.x - c.row * a.nch;
+    const Chunk c = chunk_of<S64_CHUNK>(a.cols, a.nch);
+    const uint32_t n = c.n;
     probe_lane_order(sm.probe, &sm.ordered, lane, wid);
-    // wave wid ranks slots ws0 .. ws0 + S64_KPW - 1, slot ws0 + j * 64 + lane in k[j] (k_s64_row):
-    // element beg + slot of the row, read here and held across the reorder
-    const uint32_t ws0 = wid * S64_KPW;
-    uint32_t ng = ws0 < n ? (n - ws0 + 63u) / 64u : 0u;
-    if (ng > (uint32_t)S64_KPT) ng = S64_KPT;
+    // the chunk into registers (chunk_pass.h, WaveStripe): slot i is element beg + i of the row, read
+    // here and held across the reorder; the padding is u = ~0
+    const WaveStripe<S64_KPT> w(wid, n);
+    using Carry = std::conditional_t<IDX, uint32_t, NoCarry>;
     const uint64_t *kbase = q.ks + c.rowoff + c.beg;
     const uint32_t *pbase = q.ps + c.rowoff + c.beg;  // (read only in a later pass with positions)
     uint64_t k[S64_KPT];
     uint32_t v[IDX ? S64_KPT : 1];
 #pragma unroll
     for (int j = 0; j < S64_KPT; ++j) {
-        const uint32_t i = ws0 + (uint32_t)j * WAVE + lane;
+        const uint32_t i = w.slot(j, lane);
         k[j] = i < n ? kbase[i] : ~0ull;
         if constexpr (IDX) v[j] = q.first ? c.beg + i : i < n ? pbase[i] : 0u;
     }
     if (q.first) {
 #pragma unroll
         for (int j = 0; j < S64_KPT; ++j) {
-            const uint32_t i = ws0 + (uint32_t)j * WAVE + lane;
-            if (i < n) k[j] = key64_ord(k[j], a.kt) ^ a.x64;
+            if (w.slot(j, lane) < n) k[j] = key64_ord(k[j], a.kt) ^ a.x64;
         }
     }
-    // digit d = tid: the row's total and what the chunks before this one hold of it
-    uint32_t tot = 0u, pre = 0u;
-    if (tid < 256u) {
-        tot = a.tot[(size_t)c.row * 256u + tid];
-        pre = a.cnt[((size_t)c.row * 256u + tid) * a.nch + chunk];
-    }
-    const uint32_t dbase = block_excl_scan<S64_BLOCK, 256>(tot, sm.wsum2);
+    const uint32_t dbase = chunk_digit_base<S64_BLOCK>(a.cnt, a.tot, c, a.nch, sm.wsum2);
     __syncthreads();  // the probe's answer is published
     const bool atomic_rank = lane_order_probed(&sm.ordered);
-    uint32_t *wh = sm.whist + wid * 256u;
-    for (uint32_t i = lane; i < 256u; i += WAVE) wh[i] = 0u;
     uint32_t rank[S64_KPT / 2] = {};
-#pragma unroll
-    for (int j = 0; j < S64_KPT; ++j) {
-        uint32_t r = 0u;
-        if ((uint32_t)j < ng) r = rank8(wh, digit_of(k[j], shift), lane, atomic_rank);
-        set16(rank, j, r);
-    }
-    __syncthreads();  // every wave's counters are complete
-    const DigitSpan sp = fold_digit_offsets<S64_BLOCK, S64_W>(sm.whist, sm.wsum);
-    if (tid < 256u) sm.goff[tid] = dbase + pre - sp.start;  // (mod 2^32: goff[d] + slot >= 0 for slot >= sp.start)
+    const DigitSpan sp = chunk_rank<S64_BLOCK>(k, shift, w.ng, sm.whist, sm.wsum, rank, atomic_rank, lane, wid);
+    if (tid < 256u) sm.goff[tid] = dbase - sp.start;  // (mod 2^32: goff[d] + slot >= 0 for slot >= sp.start)
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < S64_KPT; ++j)
-        if ((uint32_t)j < ng) {  // (ranked slots number the keys and the padding of the last group: dst < S64_CHUNK)
-            const uint32_t dst = wh[digit_of(k[j], shift)] + get16(rank, j);
-            sm.keys[dst] = k[j];
-            if constexpr (IDX) sm.pay[dst] = v[j];
-        }
+    chunk_reorder<false>(k, v, shift, w.ng, sm.whist + wid * 256u, rank, sm.keys, reinterpret_cast<Carry *>(sm.pay));
     __syncthreads();
     // slot i of the digit order: consecutive slots of one digit are consecutive elements of the row
     uint64_t *kd = q.kd + c.rowoff;
     uint32_t *pd = q.pd + c.rowoff;
-    for (uint32_t i = tid; i < n; i += S64_BLOCK) {
-        const uint64_t u = sm.keys[i];
-        const uint32_t o = sm.goff[digit_of(u, shift)] + i;
-        if (o >= a.cols) continue;  // (cannot happen while the count and the scatter read the same keys)
+    chunk_store<S64_BLOCK>(sm.keys, sm.goff, shift, n, a.cols, [&](uint32_t i, uint64_t u, uint32_t o) {
         kd[o] = q.last ? key64_unord(u ^ a.x64, a.kt) : u;
         if constexpr (IDX) pd[o] = sm.pay[i];
-    }
+    });
 }
 
 // every key of the call has one image (m == 0): the input in place, NaNs canonical
 template <bool IDX>
 __global__ __launch_bounds__(S64_BLOCK) void k_s64_same(S64Args a) {
     if (a.plan->m != 0u) return;
-    const S64Chunk c = s64_chunk(a);
+    const Chunk c = chunk_of<S64_CHUNK>(a.cols, a.nch);
 #pragma unroll
     for (int j = 0; j < S64_KPT; ++j) {
         const uint32_t i = (uint32_t)j * S64_BLOCK + threadIdx.x;
@@ -428,7 +301,6 @@ __global__ __launch_bounds__(S64_BLOCK) void k_s64_same(S64Args a) {
     }
 }
 
-inline bool key_type_is64(int kt) { return kt == LABSORT_KEY_U64 || kt == LABSORT_KEY_I64 || kt == LABSORT_KEY_F64; }
 inline size_t s64_chunks(size_t cols) { return (cols + S64_CHUNK - 1) / S64_CHUNK; }
 inline bool s64_row_path(size_t cols) { return cols <= (size_t)S64_CHUNK; }
 
@@ -443,15 +315,15 @@ hipError_t s64_launch_row(const S64Args &a, size_t rows, hipStream_t s) {
 }
 
 struct S64Layout {
-    size_t off_plan, off_cnt, off_tot, off_keys, off_pos, total;
+    ChunkTable t;
+    size_t off_plan, off_keys, off_pos, total;
 };
 S64Layout s64_layout(size_t rows, size_t cols, bool idx) {
     S64Layout L;
     Carver c;
     c.take(SEG_HDR_BYTES);
     L.off_plan = c.take(S64_PLAN_BYTES);
-    L.off_cnt = c.take(rows * 256 * s64_chunks(cols) * sizeof(uint32_t));
-    L.off_tot = c.take(rows * 256 * sizeof(uint32_t));
+    L.t = carve_chunk_table(c, rows, s64_chunks(cols));
     L.off_keys = c.take(rows * cols * 8);
     L.off_pos = idx ? c.take(rows * cols * 4) : 0;
     L.total = c.o;
@@ -482,13 +354,7 @@ int labsort_sort64_device(const void *d_keys, size_t rows, size_t cols, int desc
     static_assert(S64_HDR_MASK * 4 < SEG_HDR_BYTES, "a word of the header");
     if (rows == 0 || cols == 0) return LABSORT_OK;
     if (!key_type_is64(key_type)) return LABSORT_ERR_ARG;
-    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
-    if (rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
-    if (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 7u) return LABSORT_ERR_ARG;
-    if (static_cast<const void *>(d_idx_out) == d_keys_out) return LABSORT_ERR_ARG;
-    const size_t n = rows * cols;
-    if (ranges_overlap(d_keys, n * 8, d_keys_out, n * 8)) return LABSORT_ERR_ARG;
-    if (d_idx_out && ranges_overlap(d_keys, n * 8, d_idx_out, n * 4)) return LABSORT_ERR_ARG;
+    if (const int rc = dense_rows_args(d_keys, rows, cols, cols, key_type, d_keys_out, d_idx_out)) return rc;
     const bool idx = d_idx_out != nullptr;
     if (!d_ws || ws_bytes < labsort_sort64_workspace_bytes(rows, cols, idx)) return LABSORT_ERR_ARG;
     hipStream_t s = as_stream(stream);
@@ -513,19 +379,17 @@ int labsort_sort64_device(const void *d_keys, size_t rows, size_t cols, int desc
     HIP_TRY(launch_zero(d_ws, SEG_HDR_BYTES + S64_PLAN_BYTES, s));
     TimingScope ts(LABSORT_K_SEGSORT, s);
     a.plan = reinterpret_cast<S64Plan *>(ws + L.off_plan);
-    a.cnt = reinterpret_cast<uint32_t *>(ws + L.off_cnt);
-    a.tot = reinterpret_cast<uint32_t *>(ws + L.off_tot);
+    a.cnt = reinterpret_cast<uint32_t *>(ws + L.t.off_cnt);
+    a.tot = reinterpret_cast<uint32_t *>(ws + L.t.off_tot);
     a.tk = reinterpret_cast<uint64_t *>(ws + L.off_keys);
     a.tp = idx ? reinterpret_cast<uint32_t *>(ws + L.off_pos) : nullptr;
     a.nch = (uint32_t)s64_chunks(cols);
     const unsigned grid = (unsigned)(rows * a.nch);
-    const uint32_t nrd = (uint32_t)(rows * 256);
     k_s64_bits<<<grid, S64_BLOCK, 0, s>>>(a);
     k_s64_plan<<<1, WAVE, 0, s>>>(a.plan, a.hdr);
     for (uint32_t p = 0; p < 8u; ++p) {
         k_s64_count<<<grid, S64_BLOCK, 0, s>>>(a, p);
-        if (a.nch <= S64_SCAN_SERIAL) k_s64_scan_serial<<<(nrd + 255u) / 256u, 256, 0, s>>>(a, p, nrd);
-        else k_s64_scan_block<<<nrd, S64_SCAN_BLOCK, 0, s>>>(a, p);
+        launch_chunk_scan(a.cnt, a.tot, rows, a.nch, S64Gate{a.plan, p}, s);
         if (idx) k_s64_scatter<true><<<grid, S64_BLOCK, 0, s>>>(a, p);
         else k_s64_scatter<false><<<grid, S64_BLOCK, 0, s>>>(a, p);
         HIP_TRY(hipGetLastError());

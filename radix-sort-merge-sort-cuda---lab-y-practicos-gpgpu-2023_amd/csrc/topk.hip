@@ -636,6 +636,7 @@ size_t labsort_topk_workspace_bytes(size_t rows, size_t cols, size_t k) {
 int labsort_topk_device(const void *d_keys, size_t rows, size_t cols, size_t k, int largest, int key_type,
                         void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
     if (rows == 0 || k == 0) return LABSORT_OK;
+    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
     if (const int rc = dense_rows_args(d_keys, rows, cols, k, key_type, d_keys_out, d_idx_out)) return rc;
     const bool k16 = key_type_is16(key_type);
     const int path = topk_path(rows, cols, k);

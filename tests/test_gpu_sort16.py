@@ -126,6 +126,19 @@ def test_one_row_many_chunks(ls, torch_gpu):
     check(ls, torch, x, False, "bf16")
 
 
+@pytest.mark.parametrize("extra", [0, 1])
+def test_scan_edge(ls, torch_gpu, extra):
+    """One row of 64 C and of 64 C + 1 keys, bfloat16, descending, with positions: the most chunks that
+    a thread per (row, digit) walks, and the fewest that a workgroup per (row, digit) scans, in one
+    partial step, the last chunk one key long."""
+    C = ls.sort16_chunk_keys()
+    cols = 64 * C + extra
+    x = M.random_words((1, cols), 0x5163 + extra, "bf16")
+    x[0, 1000:cols:997] = M.specials("bf16")["-qnan1"]
+    x[0, ::4099] = x[0, 7]
+    check(ls, torch_gpu, x, True, "bf16")
+
+
 @KINDS
 @pytest.mark.parametrize("what", ["all_equal", "all_nan", "low_byte_equal", "high_byte_equal"])
 def test_degenerate_digits(ls, torch_gpu, what, kind):

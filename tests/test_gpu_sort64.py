@@ -111,6 +111,22 @@ def test_one_row_many_chunks(ls, torch_gpu):
     check(ls, torch_gpu, x, True, "i64", with_idx=False)
 
 
+def test_one_row_64_chunks(ls, torch_gpu):
+    """One row of exactly 64 chunks, u64, with positions: the most chunks that a thread per (row, digit)
+    walks."""
+    C = ls.sort64_chunk_keys()
+    x = M.planted((1, 64 * C), 0x6452, "u64")
+    check(ls, torch_gpu, x, False, "u64")
+
+
+def test_rows_of_65_chunks(ls, torch_gpu):
+    """(3, 64 C + 1), keys only: the scan by a workgroup per (row, digit) over more than one row, whose
+    carry must stay inside its (row, digit); every row's last chunk one key long."""
+    C = ls.sort64_chunk_keys()
+    x = M.planted((3, 64 * C + 1), 0x6453, "u64")
+    check(ls, torch_gpu, x, False, "u64", with_idx=False)
+
+
 @pytest.mark.parametrize("part", range(4))
 def test_digit_masks_long(ls, torch_gpu, part):
     """One row of 2C + 1 u64 keys whose images vary in exactly a chosen set of bytes, all 256 sets (64

@@ -75,7 +75,8 @@ extern "C" {
  * input write the original word (the segmented sorts' general path in its pairs form), where
  *   unord(o) = (o & 0x80000000) ? (o & 0x7FFFFFFF) : ~o.
  * Accepted by labsort_sort_device, labsort_sort_pairs_device, labsort_sort_segments_device,
- * labsort_sort_segments_pairs_device, labsort_topk_device and labsort_sort_rows_device only; every other entry that
+ * labsort_sort_segments_pairs_device, labsort_topk_device, labsort_sort_rows_device, labsort_kth_device and
+ * labsort_unique_device only; every other entry that
  * checks its key type returns LABSORT_ERR_ARG for it (host-pointer, multi-GPU and distributed
  * sorts, labsort_merge_runs, labsort_upper_bound, the C++ drop-ins).  The building blocks
  * that take a key type without checking it order U32 / I32 words only. */
@@ -98,7 +99,8 @@ extern "C" {
  * gives the word back. */
 uint32_t labsort_key_order_bits(uint32_t word, int key_type);
 uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type);
-/* 8-byte keys: uint64, int64 and IEEE-754 binary64, accepted by labsort_sort64_device ONLY (every
+/* 8-byte keys: uint64, int64 and IEEE-754 binary64, accepted by labsort_sort64_device and
+ * labsort_unique_device ONLY (every
  * other entry that checks its key type returns LABSORT_ERR_ARG for them; values 5 to 7 are not
  * assigned).  The order image is a uint64_t: U64 the word, I64 the word ^ (1 << 63), F64 the
  * float32 contract at 64 bits,
@@ -607,6 +609,61 @@ int labsort_kth_device(const void *d_keys, size_t rows, size_t cols, size_t k, c
                        int key_type, void *d_keys_out, uint32_t *d_idx_out, void *d_workspace,
                        size_t workspace_bytes, void *stream);
 int labsort_kth_workspace_status(const void *d_workspace, void *stream);
+
+/* ---- unique: the distinct keys of an array with their counts, the position of each one's first
+ * occurrence and every element's index into them (torch.unique(return_inverse, return_counts) on
+ * index tensors, vocabulary and id compaction, edge deduplication on packed (src << 32) | dst keys,
+ * group-by counts; no lab.cu counterpart) ----
+ * d_keys holds n elements of the key type, never written.  key_type: U32, I32, F32 (4-byte elements)
+ * or U64, I64, F64 (8-byte elements, d_keys and d_unique_out 8-byte aligned); BF16 and F16 are not
+ * taken.  Two keys are equal when their order images are equal (labsort_key_order_bits,
+ * labsort_key_order_bits64): every NaN is one value, -0.0 and +0.0 are two.
+ * flags == 0: d_unique_out[0..m) holds the distinct keys in ascending image order, non-NaN keys
+ * untransformed, a NaN as 0x7FFFFFFF / 0x7FFFFFFFFFFFFFFF; d_counts_out[j] the number of occurrences
+ * of key j; d_first_out[j] the lowest position i with d_keys[i] equal to it; d_inverse_out[i] = j such
+ * that d_unique_out[j] equals d_keys[i]; *d_num_out = m.
+ * flags == LABSORT_UNIQUE_CONSECUTIVE: nothing is sorted; entry j describes the j-th run of equal
+ * neighbours of d_keys in input order (torch.unique_consecutive under the same equality): the key is
+ * from_order_bits(image), the count the run's length, first the run's start, d_inverse_out[i] the run
+ * that i lies in, m the number of runs.
+ * d_unique_out has room for n elements of the key type, d_counts_out and d_first_out for n words
+ * each (the first m are written, nothing behind them is), d_inverse_out for n words, d_num_out for
+ * one; d_counts_out, d_first_out and d_inverse_out may each be NULL.  No output may share a byte with
+ * the input or with another output, by these extents.
+ * n <= labsort_max_keys(LABSORT_ALGO_RADIX) for 4-byte keys, n <= 2^31 - 1 for 8-byte keys.
+ * LABSORT_ERR_ARG before any launch: NULL d_keys (n != 0), d_unique_out or d_num_out, a bad key type,
+ * an unknown flag bit, a misaligned pointer, an overlap, n past the limit, a missing or short
+ * workspace.  n == 0 writes 0 to *d_num_out by one hipMemsetAsync on the stream and nothing else;
+ * d_keys may then be NULL and the workspace is not looked at.
+ * The default call first sorts: 4-byte keys with d_first_out or d_inverse_out by
+ * labsort_sort_pairs_device(LABSORT_ALGO_AUTO) in place on a (key, 0 .. n-1) copy in the workspace,
+ * 4-byte keys without them by labsort_sort_device(LABSORT_ALGO_AUTO) into the workspace (no position
+ * is stored or loaded anywhere), 8-byte keys by labsort_sort64_device(rows = 1), with or without
+ * positions likewise.  Then, over the sorted array (the input in consecutive mode) cut into chunks
+ * of C = labsort_unique_chunk_keys() elements: a count of every chunk's run heads (element i is one
+ * if i == 0 or its image differs from that of element i - 1, which a chunk's first reads from
+ * memory), an exclusive scan of the counts that leaves m in *d_num_out, a kernel that ranks each
+ * chunk's heads again and writes keys, first positions, run starts and the inverse, and, with
+ * d_counts_out, one that takes the run lengths from the starts (its grid is sized for n; workgroups
+ * past m return).  No kernel waits on another workgroup.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on the
+ * host arguments only, so a captured call may be replayed on new keys in the same buffers and leaves
+ * a new m.  labsort_unique_workspace_bytes: with_positions is non-zero when d_first_out or
+ * d_inverse_out will be passed; a workspace sized with positions serves a call without them, and the
+ * size never shrinks as n grows.  The call clears or overwrites what it relies on: garbage or a
+ * reused workspace is fine.
+ * labsort_unique_workspace_status synchronises `stream` and passes on the status of the inner sort of
+ * the last call on the workspace (labsort_pairs_workspace_status or labsort_workspace_status for the
+ * 4-byte types); LABSORT_OK for the 8-byte types, in consecutive mode and for n == 0.
+ * Timing hooks: the kernels of this entry count under LABSORT_K_SEGSORT, the inner sorts' under
+ * their own classes. */
+#define LABSORT_UNIQUE_CONSECUTIVE 1   /* flags bit 0: do not sort; collapse runs of equal neighbours */
+size_t labsort_unique_chunk_keys(void);   /* C: keys per workgroup of the edge passes; info for tests */
+size_t labsort_unique_workspace_bytes(size_t n, int key_type, int flags, int with_positions);
+int labsort_unique_device(const void *d_keys, size_t n, int key_type, int flags, void *d_unique_out,
+                          uint32_t *d_counts_out, uint32_t *d_first_out, uint32_t *d_inverse_out,
+                          uint32_t *d_num_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int labsort_unique_workspace_status(const void *d_workspace, size_t n, int key_type, int flags, void *stream);
 
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +

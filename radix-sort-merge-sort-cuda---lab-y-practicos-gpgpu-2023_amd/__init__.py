@@ -68,7 +68,10 @@ C_SYMBOLS = [
     "labsort_key_order_bits64", "labsort_key_from_order_bits64",
     "labsort_kth_row_keys", "labsort_kth_workspace_bytes", "labsort_kth_device", "labsort_kth_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
+    "labsort_unique_chunk_keys", "labsort_unique_workspace_bytes", "labsort_unique_device",
+    "labsort_unique_workspace_status",
 ]
+UNIQUE_CONSECUTIVE = 1  # LABSORT_UNIQUE_CONSECUTIVE
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
 MULTI_PHASES = ["h2d", "local_sort", "plan", "exchange", "merge", "d2h", "total", "plan_work", "plan_wait"]
 COLLECTIVES = ["samples", "counts", "grow"]  # the schedule's collectives, in order (labsort.h)
@@ -233,6 +236,13 @@ def _load() -> ctypes.CDLL:
         L.labsort_kth_workspace_bytes.argtypes = [sz, sz]
         L.labsort_kth_device.argtypes = [p, sz, sz, sz, p, i, i, p, p, p, sz, p]
         L.labsort_kth_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_unique_device"):  # (as labsort_radix_path above)
+        L.labsort_unique_chunk_keys.restype = sz
+        L.labsort_unique_chunk_keys.argtypes = []
+        L.labsort_unique_workspace_bytes.restype = sz
+        L.labsort_unique_workspace_bytes.argtypes = [sz, i, i, i]
+        L.labsort_unique_device.argtypes = [p, sz, i, i, p, p, p, p, p, p, sz, p]
+        L.labsort_unique_workspace_status.argtypes = [p, sz, i, i, p]
     if hasattr(L, "labsort_key_order_bits"):  # (as labsort_radix_path above)
         for f in ("labsort_key_order_bits", "labsort_key_from_order_bits"):
             getattr(L, f).restype = ctypes.c_uint32
@@ -966,6 +976,95 @@ def kthvalue(x, k, largest: bool = False, workspace=None, stream=None):
     indices = torch.empty((rows,), dtype=torch.int32, device=x.device)
     kth_device(x, rows, cols, k, values, indices, largest=largest, key=key, workspace=workspace, stream=stream)
     return values, indices
+
+
+def unique_chunk_keys() -> int:
+    """C: elements per workgroup of unique_device's run-edge passes (the sorted array, or the input
+    in consecutive mode, is cut into chunks of C)."""
+    return int(lib.labsort_unique_chunk_keys())
+
+
+def unique_workspace_bytes(n: int, key: str = "u32", consecutive: bool = False, positions: bool = True) -> int:
+    """Workspace of unique_device for n keys; positions: d_first_out or d_inverse_out will be passed
+    (a workspace sized with them serves a call without)."""
+    return int(lib.labsort_unique_workspace_bytes(n, KEY[key], UNIQUE_CONSECUTIVE if consecutive else 0,
+                                                  1 if positions else 0))
+
+
+def unique_device(d_keys, n: int, d_unique_out, d_num_out, d_counts_out=None, d_first_out=None, d_inverse_out=None,
+                  key: str = "u32", consecutive: bool = False, workspace=None, stream=None) -> None:
+    """The distinct keys of d_keys[0..n) into d_unique_out (room for n elements of the key type; the
+    first m are written, in ascending order), m into the one word d_num_out, and on request each
+    key's number of occurrences (d_counts_out), the position of its first occurrence (d_first_out)
+    and every element's index into d_unique_out (d_inverse_out): int32 / uint32 buffers of n words.
+    key: "u32", "i32", "f32", "u64", "i64" or "f64"; keys are equal when their order images are, so
+    every NaN is one value (written as 0x7FFF..) and -0.0 and +0.0 are two.  consecutive: nothing is
+    sorted, entry j describes the j-th run of equal neighbours in input order.  d_keys is never
+    written, nor anything past m in the outputs.  The call does not synchronise and reads nothing
+    back, so it can be captured in a graph; without `workspace` one of unique_workspace_bytes(...)
+    bytes is taken from torch's allocator, which orders its reuse on the current stream only.
+    unique_workspace_status reports the inner sort's status once the result is needed."""
+    pos = d_first_out is not None or d_inverse_out is not None
+    workspace, wsb, _ = _workspace(workspace, lambda: unique_workspace_bytes(n, key, consecutive, pos))
+    opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
+    _check(lib.labsort_unique_device(None if d_keys is None else _ptr(d_keys), n, KEY[key],
+                                     UNIQUE_CONSECUTIVE if consecutive else 0, _ptr(d_unique_out), opt(d_counts_out),
+                                     opt(d_first_out), opt(d_inverse_out), _ptr(d_num_out), _ptr(workspace), wsb,
+                                     _stream(stream)), "unique_device")
+
+
+def unique_workspace_status(workspace, n: int, key: str = "u32", consecutive: bool = False, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_DEVICE if the inner sort of the last
+    unique_device(n, key, consecutive) call on `workspace` reported an error."""
+    _check(lib.labsort_unique_workspace_status(_ptr(workspace), n, KEY[key], UNIQUE_CONSECUTIVE if consecutive else 0,
+                                               _stream(stream)), "unique (status)")
+
+
+def unique(x, return_inverse: bool = False, return_counts: bool = False, return_index: bool = False,
+           consecutive: bool = False, workspace=None, stream=None):
+    """The distinct values of x in ascending order (consecutive: the runs of equal neighbours in input
+    order): unique_device with its outputs allocated.  x: a contiguous 1-D CUDA tensor of dtype int32,
+    float32, int64 or float64, or torch.uint32 / torch.uint64 where torch has them.  Returns values,
+    or the tuple (values, inverse, counts, index) of what was asked for, in that order (torch.unique's,
+    with index last); inverse has x's length, the others m elements; all three are int32.  Equality
+    is that of unique_device: on integers torch.unique's, on floats every NaN one value (torch keeps
+    each) and -0.0 apart from +0.0 (torch merges them).  The number of distinct values is read back
+    from the device to slice the outputs: one synchronisation of `stream`; unique_device has none.
+    TypeError for another dtype, a tensor that is not 1-D and contiguous, or a CPU tensor, before the
+    device is touched."""
+    import torch
+    keys = {torch.int32: "i32", torch.float32: "f32", torch.int64: "i64", torch.float64: "f64"}
+    for name, key in (("uint32", "u32"), ("uint64", "u64")):
+        if hasattr(torch, name):
+            keys[getattr(torch, name)] = key
+    if not isinstance(x, torch.Tensor) or x.dtype not in keys:
+        raise TypeError("unique: int32, float32, int64, float64, uint32 or uint64 tensor expected, "
+                        f"got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 1 or not x.is_contiguous():
+        raise TypeError("unique: a contiguous 1-D tensor expected")
+    if not x.is_cuda:
+        raise TypeError("unique: a CUDA tensor expected")
+    n, key = x.shape[0], keys[x.dtype]
+    words = lambda on: torch.empty(n, dtype=torch.int32, device=x.device) if on else None  # noqa: E731
+    values = torch.empty_like(x)
+    num = torch.empty(1, dtype=torch.int32, device=x.device)
+    inverse, counts, index = words(return_inverse), words(return_counts), words(return_index)
+    m = 0
+    if n:  # (an empty tensor has no address to pass)
+        pos = return_inverse or return_index
+        workspace, _, _ = _workspace(workspace, lambda: unique_workspace_bytes(n, key, consecutive, pos))
+        unique_device(x, n, values, num, counts, index, inverse, key=key, consecutive=consecutive, workspace=workspace,
+                      stream=stream)
+        unique_workspace_status(workspace, n, key, consecutive, stream)  # (synchronises)
+        m = int(num.item())
+    out = [values[:m]]
+    if return_inverse:
+        out.append(inverse)
+    if return_counts:
+        out.append(counts[:m])
+    if return_index:
+        out.append(index[:m])
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def key_order_bits(word: int, key: str = "u32") -> int:

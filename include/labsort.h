@@ -76,13 +76,13 @@ extern "C" {
  *   unord(o) = (o & 0x80000000) ? (o & 0x7FFFFFFF) : ~o.
  * Accepted by labsort_sort_device, labsort_sort_pairs_device, labsort_sort_segments_device,
  * labsort_sort_segments_pairs_device, labsort_topk_device, labsort_sort_rows_device, labsort_kth_device and
- * labsort_unique_device only; every other entry that
+ * labsort_unique_device and labsort_searchsorted_device only; every other entry that
  * checks its key type returns LABSORT_ERR_ARG for it (host-pointer, multi-GPU and distributed
  * sorts, labsort_merge_runs, labsort_upper_bound, the C++ drop-ins).  The building blocks
  * that take a key type without checking it order U32 / I32 words only. */
 #define LABSORT_KEY_F32 2
 /* bfloat16 and IEEE-754 binary16: 16-bit elements, accepted by labsort_topk_device,
- * labsort_sort_rows_device and labsort_sort16_device ONLY (every other entry that checks its key type returns
+ * labsort_sort_rows_device, labsort_sort16_device and labsort_searchsorted_device ONLY (every other entry that checks its key type returns
  * LABSORT_ERR_ARG for them, the segmented and whole-array device sorts included).  The float32 contract at 16 bits: with T = 0x7F80 (bfloat16)
  * or 0x7C00 (binary16), an element x is ordered by
  *   ord16(x) = 0xFFFF         if (x & 0x7FFF) > T   (every NaN, either sign)
@@ -99,8 +99,8 @@ extern "C" {
  * gives the word back. */
 uint32_t labsort_key_order_bits(uint32_t word, int key_type);
 uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type);
-/* 8-byte keys: uint64, int64 and IEEE-754 binary64, accepted by labsort_sort64_device and
- * labsort_unique_device ONLY (every
+/* 8-byte keys: uint64, int64 and IEEE-754 binary64, accepted by labsort_sort64_device,
+ * labsort_unique_device and labsort_searchsorted_device ONLY (every
  * other entry that checks its key type returns LABSORT_ERR_ARG for them; values 5 to 7 are not
  * assigned).  The order image is a uint64_t: U64 the word, I64 the word ^ (1 << 63), F64 the
  * float32 contract at 64 bits,
@@ -664,6 +664,59 @@ int labsort_unique_device(const void *d_keys, size_t n, int key_type, int flags,
                           uint32_t *d_counts_out, uint32_t *d_first_out, uint32_t *d_inverse_out,
                           uint32_t *d_num_out, void *d_workspace, size_t workspace_bytes, void *stream);
 int labsort_unique_workspace_status(const void *d_workspace, size_t n, int key_type, int flags, void *stream);
+
+/* ---- searchsorted: the rank of every value in a sorted sequence (torch.searchsorted, torch.bucketize:
+ * ids into a compacted vocabulary, isin, CSR row pointers from sorted edge keys, histogram and
+ * quantile bins against explicit edges; no lab.cu counterpart) ----
+ * d_sorted is seq_rows x cols elements of the key type, each row ascending in image order; d_values
+ * is rows x nv elements of the same key type; d_out is rows x nv words.  Neither input is written.
+ * seq_rows is rows or 1: with rows, row r of the values is searched in row r of the sequences; with
+ * 1, every value is searched in the one sequence (torch.bucketize, and torch.searchsorted with a 1-D
+ * sequence).
+ * With u the order image (labsort_key_order_bits, labsort_key_order_bits64), d_out[r][j] is the
+ * number of elements e of the sequence with u(e) < u(d_values[r][j]) for right == 0, with
+ * u(e) <= u(d_values[r][j]) for right != 0.  So every NaN is one value and lies past every number,
+ * and -0.0 < +0.0.  torch.searchsorted differs there: it compares floats as the hardware does, so a
+ * NaN value ranks by comparisons that are all false and the two zeros are one value.
+ * d_sorter is NULL, or seq_rows x cols words: the i-th element of row r in order is
+ * d_sorted[r][d_sorter[r][i]], which is what an argsort of the row gives.  A sorter entry >= cols is
+ * a caller error; the kernels clamp it to cols - 1, so nothing is read out of bounds.
+ * key_type: U32, I32, F32 (4-byte elements, 4-byte aligned), BF16, F16 (2-byte elements, 2-byte
+ * aligned), U64, I64, F64 (8-byte elements, 8-byte aligned); d_out and d_sorter are 4-byte aligned.
+ * A sequence that is not ascending gives unspecified ranks, yet every rank lies in [0, cols],
+ * nothing is read or written out of bounds and nothing hangs: every search makes a number of probes
+ * fixed by cols, each clamped into the sequence, whatever the data.
+ * Limits: seq_rows * cols <= 2^31 - 1 and rows * nv <= 2^31 - 1.
+ * rows == 0 or nv == 0 launches nothing and returns LABSORT_OK before anything else is looked at.
+ * cols == 0 writes zeros (one hipMemsetAsync on the stream; d_sorted may then be NULL).
+ * LABSORT_ERR_ARG before any launch: a NULL d_sorted (cols != 0), d_values or d_out, a bad key type,
+ * seq_rows neither 1 nor rows, a misaligned pointer, d_out sharing a byte with d_sorted, d_sorter,
+ * d_values or the workspace by the real extents, a size past the limits, a missing or short workspace
+ * (or one not 16-byte aligned) where one is needed.
+ * cols <= labsort_searchsorted_row_keys(key_type) (64 KB of images: 16384 4-byte, 8192 8-byte, 32768
+ * 2-byte keys): one launch, no workspace (labsort_searchsorted_workspace_bytes is 0, d_workspace may
+ * be NULL).  A workgroup stages its sequence's images in LDS once, by 16-byte loads (element by
+ * element on an unaligned row or a partial tail, gathered through the sorter), then walks chunks of
+ * V = labsort_searchsorted_chunk_values() values: 16-byte loads, eight searches per thread side by
+ * side over the LDS array, 16-byte stores.  With one shared sequence the grid is two workgroups per
+ * CU, each striding over the chunks; with a sequence per row it is (row, slice of the row's values).
+ * Longer sequences: two launches.  The first writes 4096 sample images per sequence, the last
+ * element of each of 4096 equal strides (through the sorter), to the workspace: a 256-byte header and
+ * seq_rows tables of 4096 images, each 256-byte aligned.  The second stages the table in LDS, finds
+ * each value's stride there and finishes inside that stride in global memory by at most
+ * floor(log2(stride - 1)) + 1 probes (16 for 2^28 keys), the same predicate on both levels, so that
+ * left and right land on the two ends of a run longer than a stride.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on the host
+ * arguments only, so a captured call may be replayed on new sequences and new values in the same
+ * buffers.  No kernel waits on another workgroup.  The workspace size never shrinks as seq_rows or
+ * cols grow, and the call overwrites what it relies on: garbage or a reused workspace is fine.
+ * Timing hooks: the kernels count under LABSORT_K_SEGSORT. */
+size_t labsort_searchsorted_row_keys(int key_type);    /* longest sequence the LDS path takes; info for tests */
+size_t labsort_searchsorted_chunk_values(void);        /* V: values per workgroup step; info for tests */
+size_t labsort_searchsorted_workspace_bytes(size_t seq_rows, size_t cols, int key_type);
+int labsort_searchsorted_device(const void *d_sorted, size_t seq_rows, size_t cols, const uint32_t *d_sorter,
+                                const void *d_values, size_t rows, size_t nv, int right, int key_type,
+                                uint32_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +

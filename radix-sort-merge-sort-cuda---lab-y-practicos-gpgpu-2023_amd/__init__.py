@@ -70,6 +70,8 @@ C_SYMBOLS = [
     "labsort_key_order_bits", "labsort_key_from_order_bits",
     "labsort_unique_chunk_keys", "labsort_unique_workspace_bytes", "labsort_unique_device",
     "labsort_unique_workspace_status",
+    "labsort_searchsorted_row_keys", "labsort_searchsorted_chunk_values", "labsort_searchsorted_workspace_bytes",
+    "labsort_searchsorted_device",
 ]
 UNIQUE_CONSECUTIVE = 1  # LABSORT_UNIQUE_CONSECUTIVE
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
@@ -243,6 +245,14 @@ def _load() -> ctypes.CDLL:
         L.labsort_unique_workspace_bytes.argtypes = [sz, i, i, i]
         L.labsort_unique_device.argtypes = [p, sz, i, i, p, p, p, p, p, p, sz, p]
         L.labsort_unique_workspace_status.argtypes = [p, sz, i, i, p]
+    if hasattr(L, "labsort_searchsorted_device"):  # (as labsort_radix_path above)
+        L.labsort_searchsorted_row_keys.restype = sz
+        L.labsort_searchsorted_row_keys.argtypes = [i]
+        L.labsort_searchsorted_chunk_values.restype = sz
+        L.labsort_searchsorted_chunk_values.argtypes = []
+        L.labsort_searchsorted_workspace_bytes.restype = sz
+        L.labsort_searchsorted_workspace_bytes.argtypes = [sz, sz, i]
+        L.labsort_searchsorted_device.argtypes = [p, sz, sz, p, p, sz, sz, i, i, p, p, sz, p]
     if hasattr(L, "labsort_key_order_bits"):  # (as labsort_radix_path above)
         for f in ("labsort_key_order_bits", "labsort_key_from_order_bits"):
             getattr(L, f).restype = ctypes.c_uint32
@@ -1065,6 +1075,118 @@ def unique(x, return_inverse: bool = False, return_counts: bool = False, return_
     if return_index:
         out.append(index[:m])
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def searchsorted_row_keys(key: str = "u32") -> int:
+    """The longest sequence that searchsorted_device stages in LDS (one launch, no workspace): 64 KB of
+    images of the key type."""
+    return int(lib.labsort_searchsorted_row_keys(KEY[key]))
+
+
+def searchsorted_chunk_values() -> int:
+    """V: values per workgroup step of searchsorted_device's kernels."""
+    return int(lib.labsort_searchsorted_chunk_values())
+
+
+def searchsorted_workspace_bytes(seq_rows: int, cols: int, key: str = "u32") -> int:
+    """Workspace of searchsorted_device: 0 up to searchsorted_row_keys(key) columns, above that a header
+    and one table of 4096 sample images per sequence."""
+    return int(lib.labsort_searchsorted_workspace_bytes(seq_rows, cols, KEY[key]))
+
+
+def searchsorted_device(d_sorted, seq_rows: int, cols: int, d_values, rows: int, nv: int, d_out, right: bool = False,
+                        key: str = "u32", d_sorter=None, workspace=None, stream=None) -> None:
+    """d_out[r][j] = the number of elements of the row's sequence whose order image is below (right:
+    not above) that of d_values[r][j].  d_sorted: seq_rows x cols keys, every row ascending in image
+    order, seq_rows == rows (row r searched in sequence r) or 1 (every value in the one sequence);
+    d_values: rows x nv keys of the same type; d_out: rows x nv int32 / uint32 words; d_sorter: None or
+    seq_rows x cols int32 positions that put the rows in order (argsort's output).  key: any of KEY.
+    NaNs are one value past every number and -0.0 < +0.0.  The call does not synchronise and reads
+    nothing back, so it can be captured in a graph; a workspace is needed past searchsorted_row_keys(key)
+    columns only and is then, without `workspace`, taken from torch's allocator, which orders its
+    reuse on the current stream only."""
+    need = searchsorted_workspace_bytes(seq_rows, cols, key)
+    wsb = 0
+    if need or workspace is not None:
+        workspace, wsb, _ = _workspace(workspace, lambda: need)
+    opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
+    _check(lib.labsort_searchsorted_device(opt(d_sorted), seq_rows, cols, opt(d_sorter), opt(d_values), rows, nv,
+                                           1 if right else 0, KEY[key], opt(d_out), opt(workspace), wsb,
+                                           _stream(stream)), "searchsorted_device")
+
+
+def _search_tensor(what: str, name: str, x):
+    """The key of a tensor searchsorted() and bucketize() take, or the TypeError for its dtype."""
+    import torch
+    keys = {torch.int32: "i32", torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16", torch.int64: "i64",
+            torch.float64: "f64"}
+    for tname, key in (("uint32", "u32"), ("uint64", "u64")):
+        if hasattr(torch, tname):
+            keys[getattr(torch, tname)] = key
+    if not isinstance(x, torch.Tensor) or x.dtype not in keys:
+        raise TypeError(f"{what}: {name}: int32, float32, bfloat16, float16, int64, float64, uint32 or uint64 tensor "
+                        f"expected, got {getattr(x, 'dtype', type(x))}")
+    return keys[x.dtype]
+
+
+def searchsorted(sorted_sequence, values, right: bool = False, side=None, sorter=None, workspace=None, stream=None,
+                 _what: str = "searchsorted"):
+    """torch.searchsorted(sorted_sequence, values, out_int32=True) under the library's order:
+    searchsorted_device with its output allocated.  Both are contiguous CUDA tensors of one dtype out
+    of int32, float32, bfloat16, float16, int64, float64 and torch.uint32 / torch.uint64; the result is
+    an int32 tensor of values' shape.  A 1-D sequence takes values of any shape; an N-D sequence needs
+    values of N dimensions with the same leading ones, row by row.  sorter: a contiguous int32 CUDA
+    tensor of the sequence's shape that puts it in order (argsort's).  side="right" means right=True;
+    side="left" with right=True is a ValueError, as is an unknown side.  On integers and on floats free
+    of NaNs and of zeros of both signs the result is torch's; a NaN is one value past every number and
+    -0.0 < +0.0.  TypeError for a dtype that is not taken or differs between the two, a CPU tensor or a
+    non-contiguous one; ValueError for shapes that do not match; all before the device is touched."""
+    import torch
+    if side is not None:
+        if side not in ("left", "right"):
+            raise ValueError(f"{_what}: side is 'left' or 'right', got {side!r}")
+        if side == "left" and right:
+            raise ValueError(f"{_what}: side='left' contradicts right=True")
+        right = side == "right"
+    key = _search_tensor(_what, "sorted_sequence", sorted_sequence)
+    if _search_tensor(_what, "values", values) != key:
+        raise TypeError(f"{_what}: sorted_sequence is {sorted_sequence.dtype}, values {values.dtype}: one dtype expected")
+    seq = sorted_sequence
+    if sorter is not None and (not isinstance(sorter, torch.Tensor) or sorter.dtype != torch.int32):
+        raise TypeError(f"{_what}: sorter: int32 tensor expected, got {getattr(sorter, 'dtype', type(sorter))}")
+    named = [("sorted_sequence", seq), ("values", values)] + ([("sorter", sorter)] if sorter is not None else [])
+    for name, t in named:
+        if not t.is_contiguous():
+            raise TypeError(f"{_what}: {name}: a contiguous tensor expected")
+    for name, t in named:
+        if not t.is_cuda:
+            raise TypeError(f"{_what}: {name}: a CUDA tensor expected")
+    if seq.dim() < 1:
+        raise ValueError(f"{_what}: a sequence of at least one dimension expected")
+    if sorter is not None and sorter.shape != seq.shape:
+        raise ValueError(f"{_what}: sorter has shape {tuple(sorter.shape)}, the sequence {tuple(seq.shape)}")
+    cols = seq.shape[-1]
+    if seq.dim() == 1:
+        seq_rows, rows, nv = 1, 1, values.numel()
+    else:
+        if values.dim() != seq.dim() or values.shape[:-1] != seq.shape[:-1]:
+            raise ValueError(f"{_what}: values of shape {tuple(values.shape)} do not match the leading dimensions of "
+                             f"the sequence's {tuple(seq.shape)}")
+        nv = values.shape[-1]
+        rows = seq_rows = values.numel() // nv if nv else 0
+    out = torch.empty(values.shape, dtype=torch.int32, device=values.device)
+    if rows and nv:  # (an empty tensor has no address to pass)
+        searchsorted_device(seq if cols else None, seq_rows, cols, values, rows, nv, out, right=right, key=key,
+                            d_sorter=sorter if cols else None, workspace=workspace, stream=stream)
+    return out
+
+
+def bucketize(input, boundaries, right: bool = False, workspace=None, stream=None):  # noqa: A002
+    """torch.bucketize(input, boundaries, out_int32=True, right=right): searchsorted(boundaries, input)
+    for a 1-D tensor of boundaries, under the same order and with the same errors."""
+    if getattr(boundaries, "dim", lambda: 1)() != 1:
+        raise ValueError("bucketize: 1-D boundaries expected")
+    return searchsorted(boundaries, input, right=right, workspace=workspace, stream=stream, _what="bucketize")
 
 
 def key_order_bits(word: int, key: str = "u32") -> int:

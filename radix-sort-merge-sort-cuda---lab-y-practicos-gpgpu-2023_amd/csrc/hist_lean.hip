@@ -240,10 +240,21 @@ __global__ __launch_bounds__(HIST_BLOCK) void k_hist_lean(const uint32_t *__rest
         atomicOr(&hy.ctl[HY_CTL_OR], red[1]);
     }
     // The last workgroup to get here evaluates the rule: everyone's counts are out before
-    // their ticket is drawn, and nobody waits for anybody.
-    __threadfence();
+    // their ticket is drawn, and nobody waits for anybody.  Every wave waits until its own count
+    // atomics (returnless device-scope RMWs, counted by vmcnt) have been performed -- the
+    // barrier's workgroup-scope release does not emit that wait -- then the barrier, then
+    // thread 0 alone fences at device scope and draws the ticket.  A fence in every thread is
+    // an L2 write-back and invalidate per wave, 4096 of them while other workgroups still
+    // stream, and cost 0.07 ms of the kernel's 0.24 (harness/exp/lean_count_probe.hip FENCE 3
+    // is this shape; profiles/count_pipeline_probe.txt, count_pipeline_isa.txt).
+    // (the immediate is the gfx9 encoding, gfx950 included: vmcnt in bits 3:0 and 15:14, expcnt in
+    // 6:4, lgkmcnt in 11:8; another family needs another number)
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // s_waitcnt vmcnt(0), expcnt and lgkmcnt left alone
     __syncthreads();
-    if (t == 0) red[3] = atomicAdd(&hy.ctl[HY_CTL_TICKET], 1u) == gridDim.x - 1u ? 1u : 0u;
+    if (t == 0) {
+        __threadfence();
+        red[3] = atomicAdd(&hy.ctl[HY_CTL_TICKET], 1u) == gridDim.x - 1u ? 1u : 0u;
+    }
     __syncthreads();
     if (red[3] == 0u) return;
     __threadfence();

@@ -76,13 +76,13 @@ extern "C" {
  *   unord(o) = (o & 0x80000000) ? (o & 0x7FFFFFFF) : ~o.
  * Accepted by labsort_sort_device, labsort_sort_pairs_device, labsort_sort_segments_device,
  * labsort_sort_segments_pairs_device, labsort_topk_device, labsort_sort_rows_device, labsort_kth_device and
- * labsort_unique_device and labsort_searchsorted_device only; every other entry that
- * checks its key type returns LABSORT_ERR_ARG for it (host-pointer, multi-GPU and distributed
+ * labsort_unique_device, labsort_searchsorted_device and labsort_bucket_counts_device only; every other entry that
+ * checks its key type returns LABSORT_ERR_ARG for it (labsort_bincount_device, host-pointer, multi-GPU and distributed
  * sorts, labsort_merge_runs, labsort_upper_bound, the C++ drop-ins).  The building blocks
  * that take a key type without checking it order U32 / I32 words only. */
 #define LABSORT_KEY_F32 2
 /* bfloat16 and IEEE-754 binary16: 16-bit elements, accepted by labsort_topk_device,
- * labsort_sort_rows_device, labsort_sort16_device and labsort_searchsorted_device ONLY (every other entry that checks its key type returns
+ * labsort_sort_rows_device, labsort_sort16_device, labsort_searchsorted_device and labsort_bucket_counts_device ONLY (every other entry that checks its key type returns
  * LABSORT_ERR_ARG for them, the segmented and whole-array device sorts included).  The float32 contract at 16 bits: with T = 0x7F80 (bfloat16)
  * or 0x7C00 (binary16), an element x is ordered by
  *   ord16(x) = 0xFFFF         if (x & 0x7FFF) > T   (every NaN, either sign)
@@ -100,7 +100,8 @@ extern "C" {
 uint32_t labsort_key_order_bits(uint32_t word, int key_type);
 uint32_t labsort_key_from_order_bits(uint32_t bits, int key_type);
 /* 8-byte keys: uint64, int64 and IEEE-754 binary64, accepted by labsort_sort64_device,
- * labsort_unique_device and labsort_searchsorted_device ONLY (every
+ * labsort_unique_device, labsort_searchsorted_device and labsort_bucket_counts_device ONLY, U64 and
+ * I64 by labsort_bincount_device too (every
  * other entry that checks its key type returns LABSORT_ERR_ARG for them; values 5 to 7 are not
  * assigned).  The order image is a uint64_t: U64 the word, I64 the word ^ (1 << 63), F64 the
  * float32 contract at 64 bits,
@@ -717,6 +718,77 @@ size_t labsort_searchsorted_workspace_bytes(size_t seq_rows, size_t cols, int ke
 int labsort_searchsorted_device(const void *d_sorted, size_t seq_rows, size_t cols, const uint32_t *d_sorter,
                                 const void *d_values, size_t rows, size_t nv, int right, int key_type,
                                 uint32_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---- bucket counts: the histogram of values over sorted edges (what torch.bincount of
+ * torch.bucketize's ranks gives, without the ranks ever being written; torch.histogram with explicit
+ * edges has no GPU form; no lab.cu counterpart) ----
+ * d_edges is edge_rows x nedges elements of the key type, each row ascending in image order;
+ * d_values is rows x nv elements of the same key type; d_counts_out is rows x (nedges + 1) words.
+ * Neither input is written.  edge_rows is rows or 1, as seq_rows is for searchsorted: with rows, row
+ * r of the values is counted on row r of the edges; with 1, every row on the one edge row.  The
+ * counts are per row of the values either way: a caller who wants one histogram of a whole tensor
+ * passes rows = 1.  There is no sorter.
+ * d_counts_out[r][b] is the number of j for which labsort_searchsorted_device with the same `right`
+ * would have written rank b for d_values[r][j]: bin 0 is "below the first edge", bin nedges "past the
+ * last edge"; with right == 0 a value equal to an edge falls in the bin below the edge, with
+ * right != 0 in the bin above it.  Every NaN is one value past every number, and -0.0 < +0.0.  Every
+ * row of counts sums to nv.
+ * key_type: the eight of labsort_searchsorted_device, with its alignment rules (elements aligned to
+ * their size, d_counts_out to 4 bytes).
+ * Edges that are not ascending give unspecified counts that still sum to nv; nothing is read or
+ * written out of bounds and nothing hangs: every search makes a number of probes fixed by nedges.
+ * Limits: edge_rows * nedges, rows * nv and rows * (nedges + 1) are each at most 2^31 - 1.
+ * rows == 0 launches nothing and returns LABSORT_OK before anything else is looked at.  nv == 0
+ * writes zeros (d_values may then be NULL).  nedges == 0 writes nv into each row's single word
+ * (d_edges may then be NULL).
+ * LABSORT_ERR_ARG before any launch: a NULL d_counts_out, d_values (nv != 0) or d_edges (nedges != 0),
+ * a bad key type, edge_rows neither 1 nor rows, a misaligned pointer, d_counts_out sharing a byte with
+ * d_edges, d_values or the workspace by the real extents, a size past the limits, a missing or short
+ * workspace (or one not 16-byte aligned) where one is needed.
+ * nedges <= labsort_bucket_counts_row_edges(key_type) (80 KB of images and counters: 10176 4-byte,
+ * 6784 8-byte, 13632 2-byte edges, so that two workgroups fit a CU): one kernel, no workspace
+ * (labsort_bucket_counts_workspace_bytes is 0, d_workspace may be NULL).  A workgroup stages its edge
+ * row's images in LDS as searchsorted does, keeps nedges + 1 32-bit counters beside them, walks chunks
+ * of labsort_searchsorted_chunk_values() values with the same loads and searches and adds each rank
+ * into its counter by an LDS atomic, equal neighbouring ranks of a thread first added together in
+ * registers.  The grid is (row, slice of the row's values) while the rows are fewer than two
+ * workgroups per CU, and the workgroups then add their non-zero counters to the output, zeroed by a
+ * kernel of its own (a captured hipMemsetAsync did not replay), with global atomics; with more rows,
+ * or rows of one chunk, a workgroup owns its row and stores the counters, zeros included (no zeroing
+ * launch then).
+ * Longer edge rows: labsort_searchsorted_device's sample kernel (a 256-byte header and edge_rows
+ * tables of 4096 images in the workspace), the zeroing of the output, and a kernel that makes
+ * searchsorted's two-level search and turns each final rank into a global atomic add, equal
+ * neighbouring ranks of a thread combined first.
+ * Asynchronous on `stream`, no allocation, nothing read back: the launch sequence depends on the host
+ * arguments only, so a captured call may be replayed on new edges and new values in the same
+ * buffers.  No kernel waits on another workgroup.  The call zeroes or overwrites the output itself
+ * and overwrites what it relies on in the workspace: garbage in either is fine.  The workspace size
+ * never shrinks as edge_rows or nedges grow.
+ * Timing hooks: the kernels count under LABSORT_K_SEGSORT. */
+size_t labsort_bucket_counts_row_edges(int key_type);   /* longest edge row the LDS path takes; info for tests */
+size_t labsort_bucket_counts_workspace_bytes(size_t edge_rows, size_t nedges, int key_type);
+int labsort_bucket_counts_device(const void *d_edges, size_t edge_rows, size_t nedges,
+                                 const void *d_values, size_t rows, size_t nv, int right, int key_type,
+                                 uint32_t *d_counts_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---- bincount: the same counting without the search (torch.bincount with the length given) ----
+ * d_values is rows x nv elements, key_type U32, I32, U64 or I64 only (any other: LABSORT_ERR_ARG);
+ * d_counts_out is rows x (nbins + 1) words.  d_counts_out[r][b] for b < nbins is the number of values
+ * of row r equal to b; word nbins holds the values outside [0, nbins): negative ones, and those at or
+ * past nbins.  Every row of counts sums to nv.  torch.bincount differs: its length follows the
+ * largest value, which it reads back, and a negative value is an error there.
+ * Limits: rows * nv and rows * (nbins + 1) are each at most 2^31 - 1.  rows == 0 returns LABSORT_OK
+ * before anything else is looked at; nv == 0 writes zeros (d_values may then be NULL).
+ * LABSORT_ERR_ARG before any launch: a NULL d_counts_out or d_values (nv != 0), a key type not listed,
+ * a misaligned pointer, d_counts_out sharing a byte with d_values, a size past the limits.
+ * nbins <= labsort_bincount_row_bins() (16384): the counters live in LDS and are flushed as above;
+ * past that every run of equal neighbouring values of a thread is one global atomic add on the zeroed
+ * output.  No workspace.  The zeroing, graph and timing rules are those of
+ * labsort_bucket_counts_device. */
+size_t labsort_bincount_row_bins(void);                 /* most bins the LDS path takes; info for tests */
+int labsort_bincount_device(const void *d_values, size_t rows, size_t nv, size_t nbins, int key_type,
+                            uint32_t *d_counts_out, void *stream);
 
 /* ---- building blocks (exposed for tests and the multi-GPU driver) ---- */
 /* Sort every 64-key tile of d_keys in place by 1-bit splits (ballot + mbcnt +

@@ -72,6 +72,8 @@ C_SYMBOLS = [
     "labsort_unique_workspace_status",
     "labsort_searchsorted_row_keys", "labsort_searchsorted_chunk_values", "labsort_searchsorted_workspace_bytes",
     "labsort_searchsorted_device",
+    "labsort_bucket_counts_row_edges", "labsort_bucket_counts_workspace_bytes", "labsort_bucket_counts_device",
+    "labsort_bincount_row_bins", "labsort_bincount_device",
 ]
 UNIQUE_CONSECUTIVE = 1  # LABSORT_UNIQUE_CONSECUTIVE
 XFER = {"auto": 0, "rccl": 1, "peer": 2}
@@ -253,6 +255,15 @@ def _load() -> ctypes.CDLL:
         L.labsort_searchsorted_workspace_bytes.restype = sz
         L.labsort_searchsorted_workspace_bytes.argtypes = [sz, sz, i]
         L.labsort_searchsorted_device.argtypes = [p, sz, sz, p, p, sz, sz, i, i, p, p, sz, p]
+    if hasattr(L, "labsort_bucket_counts_device"):  # (as labsort_radix_path above)
+        L.labsort_bucket_counts_row_edges.restype = sz
+        L.labsort_bucket_counts_row_edges.argtypes = [i]
+        L.labsort_bucket_counts_workspace_bytes.restype = sz
+        L.labsort_bucket_counts_workspace_bytes.argtypes = [sz, sz, i]
+        L.labsort_bucket_counts_device.argtypes = [p, sz, sz, p, sz, sz, i, i, p, p, sz, p]
+        L.labsort_bincount_row_bins.restype = sz
+        L.labsort_bincount_row_bins.argtypes = []
+        L.labsort_bincount_device.argtypes = [p, sz, sz, sz, i, p, p]
     if hasattr(L, "labsort_key_order_bits"):  # (as labsort_radix_path above)
         for f in ("labsort_key_order_bits", "labsort_key_from_order_bits"):
             getattr(L, f).restype = ctypes.c_uint32
@@ -1187,6 +1198,122 @@ def bucketize(input, boundaries, right: bool = False, workspace=None, stream=Non
     if getattr(boundaries, "dim", lambda: 1)() != 1:
         raise ValueError("bucketize: 1-D boundaries expected")
     return searchsorted(boundaries, input, right=right, workspace=workspace, stream=stream, _what="bucketize")
+
+
+def bucket_counts_row_edges(key: str = "u32") -> int:
+    """The longest edge row whose images bucket_counts_device keeps in LDS beside its counters (no
+    workspace): 10176 4-byte, 6784 8-byte, 13632 2-byte edges."""
+    return int(lib.labsort_bucket_counts_row_edges(KEY[key]))
+
+
+def bucket_counts_workspace_bytes(edge_rows: int, nedges: int, key: str = "u32") -> int:
+    """Workspace of bucket_counts_device: 0 up to bucket_counts_row_edges(key) edges, above that a header
+    and one table of 4096 sample images per edge row."""
+    return int(lib.labsort_bucket_counts_workspace_bytes(edge_rows, nedges, KEY[key]))
+
+
+def bucket_counts_device(d_edges, edge_rows: int, nedges: int, d_values, rows: int, nv: int, d_counts_out, right: bool = False,
+                         key: str = "u32", workspace=None, stream=None) -> None:
+    """d_counts_out[r][b] = the number of values of row r that searchsorted_device with the same
+    `right` ranks b in the row's edges: bin 0 lies below the first edge, bin nedges past the last, a
+    value equal to an edge goes below it (right: above).  d_edges: edge_rows x nedges keys, every row
+    ascending in image order, edge_rows == rows or 1 (every row counted on the one edge row);
+    d_values: rows x nv keys of the same type; d_counts_out: rows x (nedges + 1) int32 / uint32
+    words, which the call zeroes itself.  key: any of KEY.  NaNs are one value past every number and
+    -0.0 < +0.0.  The call does not synchronise and reads nothing back, so it can be captured in a
+    graph; a workspace is needed past bucket_counts_row_edges(key) edges only and is then, without
+    `workspace`, taken from torch's allocator, which orders its reuse on the current stream only."""
+    need = bucket_counts_workspace_bytes(edge_rows, nedges, key)
+    wsb = 0
+    if need or workspace is not None:
+        workspace, wsb, _ = _workspace(workspace, lambda: need)
+    opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
+    _check(lib.labsort_bucket_counts_device(opt(d_edges), edge_rows, nedges, opt(d_values), rows, nv, 1 if right else 0,
+                                            KEY[key], opt(d_counts_out), opt(workspace), wsb, _stream(stream)),
+           "bucket_counts_device")
+
+
+def bincount_row_bins() -> int:
+    """The most bins whose counters bincount_device keeps in LDS; past it every value is a global atomic."""
+    return int(lib.labsort_bincount_row_bins())
+
+
+def bincount_device(d_values, rows: int, nv: int, nbins: int, d_counts_out, key: str = "i32", stream=None) -> None:
+    """d_counts_out[r][b], b < nbins = the number of values of row r equal to b; d_counts_out[r][nbins]
+    = the number of its values outside [0, nbins).  d_values: rows x nv keys, key u32, i32, u64 or i64;
+    d_counts_out: rows x (nbins + 1) int32 / uint32 words, which the call zeroes itself.  No workspace,
+    no synchronisation, nothing read back."""
+    opt = lambda t: None if t is None else _ptr(t)  # noqa: E731
+    _check(lib.labsort_bincount_device(opt(d_values), rows, nv, nbins, KEY[key], opt(d_counts_out), _stream(stream)),
+           "bincount_device")
+
+
+def bucket_counts(input, boundaries, right: bool = False, workspace=None, stream=None):  # noqa: A002
+    """The histogram of `input` over explicit edges: torch.bincount(ls.bucketize(input, boundaries,
+    right), minlength=nedges + 1) per row, without the ranks ever being written.  input is 1-D or 2-D
+    (rows x nv); boundaries is 1-D (nedges, shared by every row) or rows x nedges, ascending; both
+    contiguous CUDA tensors of one dtype out of those searchsorted() takes.  Returns an int32 tensor of
+    shape (nedges + 1,) or (rows, nedges + 1): count b is that of the values in (edge b-1, edge b]
+    (right: [edge b-1, edge b)), count 0 lies below the first edge and count nedges past the last one, a
+    NaN is one value past every number and -0.0 < +0.0.  torch.histogram differs: it counts in
+    [edge b, edge b+1) with the last bin closed, drops what lies outside the edges and has no GPU form.
+    Errors as searchsorted(): TypeError for a dtype that is not taken or differs between the two, a
+    non-contiguous or a CPU tensor; ValueError for shapes that do not match; all before the device is
+    touched."""
+    import torch
+    what = "bucket_counts"
+    key = _search_tensor(what, "boundaries", boundaries)
+    if _search_tensor(what, "input", input) != key:
+        raise TypeError(f"{what}: boundaries is {boundaries.dtype}, input {input.dtype}: one dtype expected")
+    named = [("boundaries", boundaries), ("input", input)]
+    for name, t in named:
+        if not t.is_contiguous():
+            raise TypeError(f"{what}: {name}: a contiguous tensor expected")
+    for name, t in named:
+        if not t.is_cuda:
+            raise TypeError(f"{what}: {name}: a CUDA tensor expected")
+    if input.dim() not in (1, 2) or boundaries.dim() not in (1, 2):
+        raise ValueError(f"{what}: a 1-D or 2-D input and 1-D or 2-D boundaries expected")
+    rows, nv = (1, input.shape[0]) if input.dim() == 1 else input.shape
+    if boundaries.dim() == 2 and (input.dim() != 2 or boundaries.shape[0] != rows):
+        raise ValueError(f"{what}: boundaries of shape {tuple(boundaries.shape)} do not match the rows of the "
+                         f"input's {tuple(input.shape)}")
+    edge_rows, nedges = (rows if boundaries.dim() == 2 else 1), boundaries.shape[-1]
+    out = torch.empty((nedges + 1,) if input.dim() == 1 else (rows, nedges + 1), dtype=torch.int32, device=input.device)
+    if rows:  # (an empty tensor has no address to pass)
+        bucket_counts_device(boundaries if nedges else None, edge_rows, nedges, input if nv else None, rows, nv, out,
+                             right=right, key=key, workspace=workspace, stream=stream)
+    return out
+
+
+def bincount(input, nbins: int, stream=None):  # noqa: A002
+    """Counts of the integers 0 .. nbins - 1 per row: input is a contiguous 1-D or 2-D CUDA tensor of
+    int32, int64 or torch.uint32 / torch.uint64; the result is an int32 tensor of shape (nbins + 1,) or
+    (rows, nbins + 1) whose last count is that of the values outside [0, nbins).  torch.bincount differs:
+    its length is max(input) + 1 (at least minlength), which it reads back from the device, a negative
+    value is an error there, and it takes one row only; here the length is the caller's, so the call
+    neither synchronises nor depends on the data, and what does not fit is counted instead of refused."""
+    import torch
+    keys = {torch.int32: "i32", torch.int64: "i64"}
+    for tname, key in (("uint32", "u32"), ("uint64", "u64")):
+        if hasattr(torch, tname):
+            keys[getattr(torch, tname)] = key
+    if not isinstance(input, torch.Tensor) or input.dtype not in keys:
+        raise TypeError(f"bincount: input: int32, int64, uint32 or uint64 tensor expected, got {getattr(input, 'dtype', type(input))}")
+    if not input.is_contiguous():
+        raise TypeError("bincount: input: a contiguous tensor expected")
+    if not input.is_cuda:
+        raise TypeError("bincount: input: a CUDA tensor expected")
+    if input.dim() not in (1, 2):
+        raise ValueError("bincount: a 1-D or 2-D input expected")
+    nbins = int(nbins)
+    if nbins < 0:
+        raise ValueError(f"bincount: nbins >= 0 expected, got {nbins}")
+    rows, nv = (1, input.shape[0]) if input.dim() == 1 else input.shape
+    out = torch.empty((nbins + 1,) if input.dim() == 1 else (rows, nbins + 1), dtype=torch.int32, device=input.device)
+    if rows:
+        bincount_device(input if nv else None, rows, nv, nbins, out, key=keys[input.dtype], stream=stream)
+    return out
 
 
 def key_order_bits(word: int, key: str = "u32") -> int:

@@ -26,6 +26,21 @@ __host__ __device__ inline uint32_t ss_stride(uint32_t cols) { return (cols + SS
 __host__ __device__ inline uint32_t ss_strides(uint32_t cols) { return (cols + ss_stride(cols) - 1) / ss_stride(cols); }
 static_assert(SS_SAMPLES % SS_SAMPLE_BLOCK == 0 && SS_SAMPLES * 8 <= SS_LDS_BYTES, "the table fits the LDS array");
 
+// ---- counting (labsort_bucket_counts_device, labsort_bincount_device): the ranks go into counters.
+// The LDS path keeps the edges' images and nedges + 1 32-bit counters side by side in BC_LDS_BYTES,
+// so that two workgroups fit a CU's 160 KB: bc_row_edges(sizeof(key)) edges at the most, a multiple
+// of 64 (10176 4-byte, 6784 8-byte, 13632 2-byte), never below SS_SAMPLES.  Bincount has counters
+// only: BIN_ROW_BINS + 1 of them.
+constexpr int BC_LDS_BYTES = 80 * 1024;
+__host__ __device__ constexpr uint32_t bc_row_edges(size_t esz) { return (uint32_t)((BC_LDS_BYTES - 4) / (esz + 4) / 64 * 64); }
+constexpr int BIN_ROW_BINS = 16384;
+static_assert(bc_row_edges(8) >= SS_SAMPLES && bc_row_edges(2) * 6 + 4 <= BC_LDS_BYTES, "the counting LDS path's limits");
+// LABSORT_BC_COMBINE=0 (an A/B build): one atomic per value instead of one per run of equal
+// neighbouring ranks of a thread
+#ifndef LABSORT_BC_COMBINE
+#define LABSORT_BC_COMBINE 1
+#endif
+
 // ---- the order image of a key word K: UqImage<K> (unique.h) for 4- and 8-byte words; for the 2-byte
 // words of BF16 / F16 ord16 (common.h), what labsort_key_order_bits computes for them.
 struct SsImage16 {

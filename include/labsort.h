@@ -611,6 +611,54 @@ int labsort_kth_device(const void *d_keys, size_t rows, size_t cols, size_t k, c
                        size_t workspace_bytes, void *stream);
 int labsort_kth_workspace_status(const void *d_workspace, void *stream);
 
+/* ---- top-k filtering per row: every row with all but its k best keys replaced by a fill value,
+ * and / or the mask of the keys kept (the logits filter of a sampler, with a k per request; no
+ * lab.cu counterpart) ----
+ * d_keys is a dense rows x cols matrix; key_type: U32, I32, F32, BF16, F16 as for labsort_kth_device
+ * (the 64-bit types are LABSORT_ERR_ARG).  With u as defined at labsort_topk_device (the order image,
+ * complemented when `largest`) and k_r the k of row r, element i of row r is kept iff (u(key_i), i)
+ * is among the first k_r entries of the stable ascending sort of the row's (u, position) pairs: the
+ * positions kept are the first k_r columns of labsort_sort_rows_device(descending = largest)'s index
+ * output, as a set, so exactly k_r elements of the row are kept.  With (T, P) what labsort_kth_device
+ * returns for the row: kept iff u_i < u(T), or u_i == u(T) and i <= P.  NaNs are equal and largest;
+ * -0.0 < +0.0.
+ * d_keys_out: rows x cols elements of the key type, or NULL.  A kept key is written as the other
+ * entries write keys (bit for bit, a NaN as 0x7FFFFFFF / 0x7FFF); every other element becomes
+ * fill_bits (16-bit types: its low 16 bits; bits set above them are LABSORT_ERR_ARG).
+ * d_keys_out == d_keys filters in place; any other overlap with the input is LABSORT_ERR_ARG.
+ * d_mask_out: rows x cols bytes, 1 for kept and 0 otherwise (torch.bool's layout), any alignment, or
+ * NULL.  At least one of the two outputs must be given.
+ * k, d_k, the clamping of a d_k[r] outside [1, cols], the header word and
+ * labsort_topk_mask_workspace_status: exactly as for labsort_kth_device (a clamped row is filtered
+ * with the clamped k, the status call returns LABSORT_ERR_ARG, the other rows are valid and nothing is
+ * written out of bounds).
+ * rows == 0 or cols == 0 launches nothing (LABSORT_OK before anything else is looked at).
+ * LABSORT_ERR_ARG before any launch: NULL d_keys, both outputs NULL, a bad key type, d_k == NULL with
+ * k == 0 or k > cols, rows > (2^31 - 1) / cols, an odd d_keys / d_keys_out address with a 16-bit type,
+ * high fill_bits with a 16-bit type, any overlap (by the real element sizes) between the input, the
+ * keys output, the mask output and d_k other than d_keys_out == d_keys, a missing or short workspace.
+ * cols <= labsort_kth_row_keys(): one launch (after the header's clearing), one workgroup per row:
+ * the select of labsort_kth_device with the row in registers, one ordered scan that ranks the keys
+ * equal to the threshold in position order (skipped when all of them are kept), then every thread
+ * stores the groups it holds.  Longer rows: labsort_kth_device's launches with positions, their
+ * outputs in the workspace, then one streaming kernel over (row, chunk) that tests every element
+ * against its row's (T, P).  A group of 16 bytes that lies wholly inside its row is one 16-byte
+ * store where the output's address allows it; the heads and tails of rows, which share their
+ * 16 bytes with a neighbour row, are stored element by element (no store covers an element of
+ * another row, no read-modify-write).  The mask's alignment is tested on its own.  No kernel waits
+ * on another workgroup.
+ * Asynchronous on `stream`, no allocation, nothing read back; the launch sequence depends on the
+ * host arguments only (a captured call replays on new keys and new d_k); the call clears what it
+ * relies on in the workspace.  labsort_topk_mask_workspace_bytes never shrinks as rows or cols grow:
+ * 256 bytes for cols <= labsort_kth_row_keys(); above, labsort_kth_workspace_bytes' layout and two
+ * words per row (the k-th pair's position and key), each region 256-byte aligned.
+ * Timing hooks: the kernels count under LABSORT_K_TOPK. */
+size_t labsort_topk_mask_workspace_bytes(size_t rows, size_t cols);
+int labsort_topk_mask_device(const void *d_keys, size_t rows, size_t cols, size_t k, const uint32_t *d_k,
+                             int largest, int key_type, uint32_t fill_bits, void *d_keys_out,
+                             uint8_t *d_mask_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int labsort_topk_mask_workspace_status(const void *d_workspace, void *stream);
+
 /* ---- unique: the distinct keys of an array with their counts, the position of each one's first
  * occurrence and every element's index into them (torch.unique(return_inverse, return_counts) on
  * index tensors, vocabulary and id compaction, edge deduplication on packed (src << 32) | dst keys,

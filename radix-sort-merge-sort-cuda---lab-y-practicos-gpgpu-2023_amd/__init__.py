@@ -67,6 +67,7 @@ C_SYMBOLS = [
     "labsort_sort64_workspace_status", "labsort_sort64_passes",
     "labsort_key_order_bits64", "labsort_key_from_order_bits64",
     "labsort_kth_row_keys", "labsort_kth_workspace_bytes", "labsort_kth_device", "labsort_kth_workspace_status",
+    "labsort_topk_mask_workspace_bytes", "labsort_topk_mask_device", "labsort_topk_mask_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
     "labsort_unique_chunk_keys", "labsort_unique_workspace_bytes", "labsort_unique_device",
     "labsort_unique_workspace_status",
@@ -240,6 +241,11 @@ def _load() -> ctypes.CDLL:
         L.labsort_kth_workspace_bytes.argtypes = [sz, sz]
         L.labsort_kth_device.argtypes = [p, sz, sz, sz, p, i, i, p, p, p, sz, p]
         L.labsort_kth_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_topk_mask_device"):  # (as labsort_radix_path above)
+        L.labsort_topk_mask_workspace_bytes.restype = sz
+        L.labsort_topk_mask_workspace_bytes.argtypes = [sz, sz]
+        L.labsort_topk_mask_device.argtypes = [p, sz, sz, sz, p, i, i, ctypes.c_uint32, p, p, p, sz, p]
+        L.labsort_topk_mask_workspace_status.argtypes = [p, p]
     if hasattr(L, "labsort_unique_device"):  # (as labsort_radix_path above)
         L.labsort_unique_chunk_keys.restype = sz
         L.labsort_unique_chunk_keys.argtypes = []
@@ -997,6 +1003,96 @@ def kthvalue(x, k, largest: bool = False, workspace=None, stream=None):
     indices = torch.empty((rows,), dtype=torch.int32, device=x.device)
     kth_device(x, rows, cols, k, values, indices, largest=largest, key=key, workspace=workspace, stream=stream)
     return values, indices
+
+
+def topk_mask_workspace_bytes(rows: int, cols: int) -> int:
+    return int(lib.labsort_topk_mask_workspace_bytes(rows, cols))
+
+
+def topk_mask_device(d_keys, rows: int, cols: int, k, d_keys_out=None, d_mask_out=None, largest: bool = False,
+                     fill_bits: int = 0, key: str = "u32", workspace=None, stream=None) -> None:
+    """Top-k filtering of every row of the dense rows x cols matrix d_keys: element i of row r is kept
+    iff it is among the row's k smallest (largest) keys, equal keys in order of position, so that
+    exactly k elements of the row are kept (the first k columns of sort_rows_device(descending=largest)'s
+    positions, as a set).  d_keys_out (rows x cols elements, or None): the kept keys where they were,
+    `fill_bits` (a word of the key type) everywhere else; d_keys_out may be d_keys itself (in place).
+    d_mask_out (rows x cols bytes, torch.bool's layout, or None): 1 where kept.  At least one of the two.
+    k as for kth_device: an int, or an int32 CUDA tensor of `rows` elements (a value outside [1, cols] is
+    clamped and reported by topk_mask_workspace_status).  key as topk_device.  Workspace and status follow
+    kth_device: with a caller-owned `workspace` (>= topk_mask_workspace_bytes(rows, cols)) the call stays
+    asynchronous; without one it allocates, synchronises and checks."""
+    workspace, wsb, own = _workspace(workspace, lambda: topk_mask_workspace_bytes(rows, cols))
+    d_k = _ptr(k) if _is_k_tensor(k) else None
+    _check(lib.labsort_topk_mask_device(_ptr(d_keys), rows, cols, 0 if d_k is not None else int(k), d_k,
+                                        1 if largest else 0, KEY[key], int(fill_bits) & 0xFFFFFFFF,
+                                        None if d_keys_out is None else _ptr(d_keys_out),
+                                        None if d_mask_out is None else _ptr(d_mask_out),
+                                        _ptr(workspace), wsb, _stream(stream)), "topk_mask_device")
+    if own:
+        topk_mask_workspace_status(workspace, stream)
+
+
+def topk_mask_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_ARG if a row's k of the last topk_mask_device
+    call on `workspace` lay outside [1, cols] (that row is filtered with the clamped k)."""
+    _check(lib.labsort_topk_mask_workspace_status(_ptr(workspace), _stream(stream)), "topk_mask (status)")
+
+
+def _topk_filter_args(what: str, x, k):
+    """(rows, cols, key) for topk_filter() and topk_mask(), or kthvalue()'s TypeErrors."""
+    import torch
+    rows, cols, key = _dense_rows(what, x)
+    if isinstance(k, torch.Tensor):
+        if k.dtype != torch.int32 or not k.is_cuda or not k.is_contiguous() or k.dim() != 1 or k.shape[0] != rows:
+            raise TypeError(f"{what}: k must be an int or a contiguous int32 CUDA tensor of {rows} elements")
+    elif isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"{what}: k must be an int or an int32 CUDA tensor, got {type(k)}")
+    return rows, cols, key
+
+
+def _fill_bits(dtype, fill) -> int:
+    """The word of one element of `dtype` that holds `fill`."""
+    import torch
+    t = torch.tensor([fill], dtype=dtype)
+    if dtype in (torch.bfloat16, torch.float16):
+        return int(t.view(torch.int16).item()) & 0xFFFF
+    return int(t.view(torch.int32).item()) & 0xFFFFFFFF
+
+
+def topk_filter(x, k, largest: bool = True, fill=None, out=None, workspace=None, stream=None):
+    """x with everything outside each row's top k replaced by `fill`: topk_mask_device with the keys
+    output (what a sampler does to its logits before the softmax).  x: what kthvalue takes; k: an int, or
+    a contiguous int32 CUDA tensor of `rows` elements (one k per row).  Exactly k elements of every row
+    are kept, equal keys in order of position; a kept NaN comes back as the canonical NaN.  fill: by
+    default the worst value for the direction (-inf for largest, +inf otherwise; int32: the dtype's
+    min / max).  out: None (allocated), x itself (in place) or another contiguous tensor of x's shape
+    and dtype; it is returned.  TypeError before the device is touched for what kthvalue rejects and for
+    a wrong `out`.  Workspace and status as topk_mask_device."""
+    import torch
+    rows, cols, key = _topk_filter_args("topk_filter", x, k)
+    if out is None:
+        out = torch.empty_like(x)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous()
+          or out.device != x.device):
+        raise TypeError("topk_filter: out must be None, x itself or a contiguous tensor of x's shape, dtype and device")
+    if fill is None:
+        if x.dtype == torch.int32:
+            fill = torch.iinfo(torch.int32).min if largest else torch.iinfo(torch.int32).max
+        else:
+            fill = float("-inf") if largest else float("inf")
+    topk_mask_device(x, rows, cols, k, d_keys_out=out, largest=largest, fill_bits=_fill_bits(x.dtype, fill), key=key,
+                     workspace=workspace, stream=stream)
+    return out
+
+
+def topk_mask(x, k, largest: bool = True, workspace=None, stream=None):
+    """The torch.bool tensor of x's shape that is True at each row's top k elements (topk_filter's
+    rule: exactly k per row, equal keys in order of position).  Arguments as topk_filter."""
+    import torch
+    rows, cols, key = _topk_filter_args("topk_mask", x, k)
+    mask = torch.empty(x.shape, dtype=torch.bool, device=x.device)
+    topk_mask_device(x, rows, cols, k, d_mask_out=mask, largest=largest, key=key, workspace=workspace, stream=stream)
+    return mask
 
 
 def unique_chunk_keys() -> int:

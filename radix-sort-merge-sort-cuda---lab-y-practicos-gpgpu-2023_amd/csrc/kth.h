@@ -19,5 +19,10 @@ constexpr int KTH_SMALL_BLOCK = 256;
 constexpr int KTH_SMALL_SLOTS = 8;
 constexpr int KTH_SMALL_ROW_KEYS = LABSORT_KTH_SMALL ? KTH_SMALL_BLOCK * KTH_KPT : 0;
 constexpr int KTH_HDR_BYTES = TK_HDR_BYTES;  // word 0: a d_k[r] outside [1, cols] was clamped
+// The one-launch top-k filter skips its ordered scan of the threshold's ties when all of them are
+// kept (DESIGN.md §3.22 has the A/B; LABSORT_TKM_SKIP_SCAN=0 builds with the scan always run).
+#ifndef LABSORT_TKM_SKIP_SCAN
+#define LABSORT_TKM_SKIP_SCAN 1
+#endif
 
 }  // namespace labsort

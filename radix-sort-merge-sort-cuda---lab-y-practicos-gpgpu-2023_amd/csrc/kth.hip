@@ -25,6 +25,13 @@
 //   k_kth_locate  (with positions) one workgroup per row reads that one chunk in position order
 //               and writes the key and the position.
 // Every dependency between workgroups is a kernel boundary: no kernel waits on another workgroup.
+//
+// Top-k filtering (labsort_topk_mask_device) applies the threshold: the row written back with the
+// first k of its (u, position) pairs kept and the fill elsewhere, and / or their mask.
+//   k_tkm_short  rows of up to KTH_ROW_KEYS keys, one launch: k_kth_short's select, the threshold's
+//                ties ranked in position order, then every thread stores the groups it holds.
+//   k_tkm_apply  longer rows, after the launches above with positions: one workgroup per (row,
+//                chunk) tests every key against the row's k-th pair and stores.
 #include "kth.h"
 
 #include <type_traits>
@@ -393,6 +400,208 @@ hipError_t launch_kth_locate(const KthArgs &a, size_t rows, int kt, hipStream_t 
     return hipGetLastError();
 }
 
+// ---- top-k filtering (labsort_topk_mask_device): the row written back with everything outside its
+// first k (u, position) pairs replaced by the fill, and / or the mask of the pairs kept ----
+struct TkmArgs {
+    void *keys_out;       // rows x cols elements of the key type (may be the input itself), or nullptr
+    uint8_t *mask_out;    // rows x cols bytes, or nullptr
+    const uint32_t *pos;  // long rows: [rows], the position of each row's k-th pair (k_kth_locate's output)
+    uint32_t fill;        // what an element outside the top k becomes
+};
+
+// The key of an image, as a word of the key type (kth_write_key's transform)
+template <int KT>
+__device__ __forceinline__ uint32_t kth_unord(uint32_t u, uint32_t xr) {
+    const uint32_t w = u ^ xr;
+    if constexpr (kth_is16(KT)) return unord16(w >> 16);
+    else if constexpr (KT == KTH_F32) return f32_unord(w);
+    else return w;
+}
+
+// Stores one group of a row: elements i0 .. i0 + E - 1 (those of vm exist, rowoff = row * cols), w[j]
+// the word of element j (its key or the fill), bit j of km set where it is kept.  A group that lies
+// wholly inside the row is one 16-byte store of keys and one E-byte store of mask bytes where the
+// address allows it; everything else goes element by element, so that no store covers an element
+// of another row.  The keys' and the mask's alignment are tested each on its own.
+template <int KT>
+__device__ __forceinline__ void tkm_store(const TkmArgs &m, size_t rowoff, int64_t i0, uint32_t vm,
+                                          const uint32_t (&w)[KTH_E<KT>], uint32_t km) {
+    constexpr int E = KTH_E<KT>;
+    constexpr uint32_t FULL = (1u << E) - 1u;
+    using elem_t = kth_elem_t<KT>;
+    if (m.keys_out) {
+        const uintptr_t at = (uintptr_t)m.keys_out + (uintptr_t)(((int64_t)rowoff + i0) * (int64_t)sizeof(elem_t));
+        if (vm == FULL && (at & 15u) == 0u) {
+            uint4 v;
+            if constexpr (E == 4) v = make_uint4(w[0], w[1], w[2], w[3]);
+            else v = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
+            *reinterpret_cast<uint4 *>(at) = v;
+        } else {
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if ((vm >> j) & 1u) reinterpret_cast<elem_t *>(at)[j] = (elem_t)w[j];
+        }
+    }
+    if (m.mask_out) {
+        const uintptr_t at = (uintptr_t)m.mask_out + (uintptr_t)((int64_t)rowoff + i0);
+        // bits 0..3 of x as four bytes of 0 / 1
+        auto spread = [](uint32_t x) { return (x & 1u) | ((x & 2u) << 7) | ((x & 4u) << 14) | ((x & 8u) << 21); };
+        if (vm == FULL && (at & (uintptr_t)(E - 1)) == 0u) {
+            if constexpr (E == 4) *reinterpret_cast<uint32_t *>(at) = spread(km);
+            else *reinterpret_cast<uint2 *>(at) = make_uint2(spread(km), spread(km >> 4));
+        } else {
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if ((vm >> j) & 1u) reinterpret_cast<uint8_t *>(at)[j] = (uint8_t)((km >> j) & 1u);
+        }
+    }
+}
+
+// Rows of up to BLOCK * KTH_KPT keys: k_kth_short's select (a copy: shared, the select kernels'
+// registers would be the filter's), then every thread writes back the groups it holds.
+template <int KT, int BLOCK, int SLOTS>
+__global__ __launch_bounds__(BLOCK) void k_tkm_short(KthArgs a, TkmArgs m) {
+    constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
+    constexpr int TG = T + 1;  // a row that starts inside a group has one group more
+    constexpr int NLEV = kth_levels(KT);
+    __shared__ uint32_t h[256 * SLOTS];
+    __shared__ __attribute__((aligned(16))) uint32_t hrow[256];
+    __shared__ uint32_t wsum[BLOCK / WAVE], tot;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t mis = group_mis(base, 0u), nq = group_count<E>(0u, a.cols, mis);  // <= T * BLOCK + 1
+    uint32_t u[TG][E], vm[TG];
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        const uint32_t q = (uint32_t)t * BLOCK + tid;
+        int64_t i0;
+        vm[t] = 0u;
+        if (q < nq) vm[t] = kth_load<KT>(base, 0u, a.cols, mis, q, a.xr, u[t], i0);
+        else
+#pragma unroll
+            for (int j = 0; j < E; ++j) u[t][j] = 0u;
+    }
+    uint32_t prefix = 0u, krem = kth_k(a, row, tid == 0u), ties = 0u;
+    for (int level = 0; level < NLEV; ++level) {
+        const uint32_t shift = 24u - 8u * (uint32_t)level;
+        const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+        slot_hist_clear<SLOTS, BLOCK>(h, tid);
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u)
+                    slot_hist_add<SLOTS>(h, (u[t][j] >> shift) & 255u, tid);
+        __syncthreads();
+        if (tid < 256u) hrow[tid] = slot_hist_fold<SLOTS>(h, tid);
+        __syncthreads();
+        const KthPick p = kth_pick(hrow, krem, lane);  // (every wave: the same answer)
+        prefix |= p.d << shift;
+        krem -= p.below;
+        ties = hrow[p.d];  // after the last level: the keys equal to the threshold (hrow stays until the next level's barriers)
+    }
+    // km[t]: the elements of group (t, tid) that are kept: the keys below the threshold and the first
+    // krem of its ties in position order.  ties == krem (uniform): all of them, no scan.
+    uint32_t km[TG];
+    const bool all_ties = LABSORT_TKM_SKIP_SCAN && ties == krem;
+    uint32_t carry = 0u;
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        uint32_t lt = 0u, em = 0u;
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const bool v = (vm[t] >> j) & 1u;
+            lt |= (v && u[t][j] < prefix ? 1u : 0u) << j;
+            em |= (v && u[t][j] == prefix ? 1u : 0u) << j;
+        }
+        km[t] = lt;
+        if (all_ties) km[t] |= em;
+        else if (carry < krem) {  // (uniform; past it no tie is kept)
+            const uint32_t c = (uint32_t)__popc(em);
+            const uint32_t before = kth_ordered_step<BLOCK>(c, carry, wsum, &tot);
+            const uint32_t room = before < krem ? krem - before : 0u;
+            uint32_t seen = 0u;
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if ((em >> j) & 1u) {
+                    if (seen < room) km[t] |= 1u << j;
+                    ++seen;
+                }
+        }
+    }
+    const size_t rowoff = (size_t)row * a.cols;
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        const uint32_t q = (uint32_t)t * BLOCK + tid;
+        if (q >= nq) continue;
+        uint32_t w[E];
+#pragma unroll
+        for (int j = 0; j < E; ++j) w[j] = (km[t] >> j) & 1u ? kth_unord<KT>(u[t][j], a.xr) : m.fill;
+        tkm_store<KT>(m, rowoff, (int64_t)E * q - (int64_t)mis, vm[t], w, km[t]);
+    }
+}
+
+// Longer rows, after the select with positions: one workgroup per (row, chunk) streams its chunk
+// through the test against the row's k-th pair (uT, P).
+template <int KT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m) {
+    constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = blockIdx.x / a.nch, c = blockIdx.x - row * a.nch;
+    const uint32_t uT = a.st[(size_t)row * (TK_LEVELS + 1) + kth_levels(KT)].prefix, P = m.pos[row];
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const size_t rowoff = (size_t)row * a.cols;
+    const uint32_t beg = c * TK_CHUNK, end = a.cols - beg > (uint32_t)TK_CHUNK ? beg + TK_CHUNK : a.cols;
+    const uint32_t mis = group_mis(base, beg), nq = group_count<E>(beg, end, mis);
+    for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)T * KTH_BLOCK) {
+        uint32_t u[T][E], vm[T];
+        int64_t i0[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint32_t q = q0 + (uint32_t)t * KTH_BLOCK + tid;
+            vm[t] = 0u;
+            i0[t] = 0;
+            if (q < nq) vm[t] = kth_load<KT>(base, beg, end, mis, q, a.xr, u[t], i0[t]);
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            if (!vm[t]) continue;
+            uint32_t w[E], km = 0u;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const bool keep = ((vm[t] >> j) & 1u) && (u[t][j] < uT || (u[t][j] == uT && i0[t] + j <= (int64_t)P));
+                km |= (keep ? 1u : 0u) << j;
+                w[j] = keep ? kth_unord<KT>(u[t][j], a.xr) : m.fill;
+            }
+            tkm_store<KT>(m, rowoff, i0[t], vm[t], w, km);
+        }
+    }
+}
+
+template <int BLOCK, int SLOTS>
+hipError_t launch_tkm_short_as(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
+    const unsigned grid = (unsigned)rows;
+    if (kt == KTH_BF16) k_tkm_short<KTH_BF16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
+    else if (kt == KTH_F16) k_tkm_short<KTH_F16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
+    else if (kt == KTH_F32) k_tkm_short<KTH_F32, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
+    else k_tkm_short<KTH_INT, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
+    return hipGetLastError();
+}
+hipError_t launch_tkm_short(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
+    if (a.cols <= (uint32_t)KTH_SMALL_ROW_KEYS) return launch_tkm_short_as<KTH_SMALL_BLOCK, KTH_SMALL_SLOTS>(a, m, rows, kt, s);
+    return launch_tkm_short_as<KTH_BLOCK, TK_SLOTS>(a, m, rows, kt, s);
+}
+
+hipError_t launch_tkm_apply(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
+    const unsigned grid = (unsigned)(rows * a.nch);
+    if (kt == KTH_BF16) k_tkm_apply<KTH_BF16><<<grid, KTH_BLOCK, 0, s>>>(a, m);
+    else if (kt == KTH_F16) k_tkm_apply<KTH_F16><<<grid, KTH_BLOCK, 0, s>>>(a, m);
+    else if (kt == KTH_F32) k_tkm_apply<KTH_F32><<<grid, KTH_BLOCK, 0, s>>>(a, m);
+    else k_tkm_apply<KTH_INT><<<grid, KTH_BLOCK, 0, s>>>(a, m);
+    return hipGetLastError();
+}
+
 // header | hist | per-row states | per-chunk counts.  Header and histograms are the only words a
 // call relies on being clear.  A short row needs the header alone.
 struct KthLayout {
@@ -409,6 +618,25 @@ KthLayout kth_layout(size_t rows, size_t cols) {
     L.zero_bytes = c.o;
     L.off_st = c.take(rows * (TK_LEVELS + 1) * sizeof(KthState));
     L.off_cnt = c.take(rows * L.nch * 256 * sizeof(uint32_t));
+    L.total = c.o;
+    return L;
+}
+
+// The filter's workspace: kth's, then for long rows the words its select writes per row: the
+// position of the k-th pair and the key (which the apply pass reads as u from the states instead).
+struct TkmLayout {
+    KthLayout kth;
+    size_t off_pos, off_key, total;
+};
+TkmLayout tkm_layout(size_t rows, size_t cols) {
+    TkmLayout L{};
+    L.kth = kth_layout(rows, cols);
+    L.total = L.kth.total;
+    if (!L.kth.nch) return L;
+    Carver c;
+    c.o = L.kth.total;
+    L.off_pos = c.take(rows * sizeof(uint32_t));
+    L.off_key = c.take(rows * sizeof(uint32_t));
     L.total = c.o;
     return L;
 }
@@ -481,5 +709,67 @@ int labsort_kth_workspace_status(const void *d_ws, void *stream) {
     if (const int st = read_ws_words(d_ws, &w, 1, as_stream(stream))) return st;
     return w ? LABSORT_ERR_ARG : LABSORT_OK;
 }
+
+size_t labsort_topk_mask_workspace_bytes(size_t rows, size_t cols) { return tkm_layout(rows, cols).total; }
+
+int labsort_topk_mask_device(const void *d_keys, size_t rows, size_t cols, size_t k, const uint32_t *d_k, int largest,
+                             int key_type, uint32_t fill_bits, void *d_keys_out, uint8_t *d_mask_out, void *d_ws,
+                             size_t ws_bytes, void *stream) {
+    if (rows == 0 || cols == 0) return LABSORT_OK;
+    if (!d_keys || (!d_keys_out && !d_mask_out)) return LABSORT_ERR_ARG;
+    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
+    if (!d_k && (k == 0 || k > cols)) return LABSORT_ERR_ARG;
+    if (rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    const bool k16 = key_type_is16(key_type);
+    const size_t esz = k16 ? 2 : 4;  // bytes per key
+    if (k16 && ((((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u) || (fill_bits >> 16))) return LABSORT_ERR_ARG;
+    // the one alias: the keys written over the input, element for element
+    const size_t key_bytes = rows * cols * esz, mask_bytes = rows * cols, w_bytes = rows * 4;
+    if (d_keys_out && d_keys_out != d_keys && ranges_overlap(d_keys, key_bytes, d_keys_out, key_bytes)) return LABSORT_ERR_ARG;
+    if (d_mask_out && ranges_overlap(d_keys, key_bytes, d_mask_out, mask_bytes)) return LABSORT_ERR_ARG;
+    if (d_mask_out && d_keys_out && ranges_overlap(d_keys_out, key_bytes, d_mask_out, mask_bytes)) return LABSORT_ERR_ARG;
+    if (d_k && ranges_overlap(d_k, w_bytes, d_keys, key_bytes)) return LABSORT_ERR_ARG;
+    if (d_k && d_keys_out && ranges_overlap(d_k, w_bytes, d_keys_out, key_bytes)) return LABSORT_ERR_ARG;
+    if (d_k && d_mask_out && ranges_overlap(d_k, w_bytes, d_mask_out, mask_bytes)) return LABSORT_ERR_ARG;
+    const TkmLayout L = tkm_layout(rows, cols);
+    if (!d_ws || ws_bytes < L.total) return LABSORT_ERR_ARG;
+    const int kt = key_type == LABSORT_KEY_F32 ? KTH_F32 : key_type == LABSORT_KEY_BF16 ? KTH_BF16 : key_type == LABSORT_KEY_F16 ? KTH_F16 : KTH_INT;
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    KthArgs a{};
+    a.keys = d_keys;
+    a.d_k = d_k;
+    a.hdr = reinterpret_cast<uint32_t *>(ws);
+    a.cols = (uint32_t)cols;
+    a.k = (uint32_t)(d_k ? 1 : k);
+    a.nch = (uint32_t)L.kth.nch;
+    a.xr = k16 ? (largest ? 0xFFFF0000u : 0u) : flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);  // (as labsort_kth_device)
+    TkmArgs m{};
+    m.keys_out = d_keys_out;
+    m.mask_out = d_mask_out;
+    m.fill = fill_bits;
+    HIP_TRY(launch_zero(ws, L.kth.zero_bytes, s));
+    TimingScope ts(LABSORT_K_TOPK, s);
+    if (cols <= (size_t)KTH_ROW_KEYS) {
+        HIP_TRY(launch_tkm_short(a, m, rows, kt, s));
+        return LABSORT_OK;
+    }
+    // the select with positions, its outputs in the workspace, then the streaming pass
+    a.hist = reinterpret_cast<uint32_t *>(ws + L.kth.off_hist);
+    a.st = reinterpret_cast<KthState *>(ws + L.kth.off_st);
+    a.cnt = reinterpret_cast<uint32_t *>(ws + L.kth.off_cnt);
+    a.keys_out = ws + L.off_key;
+    a.idx_out = reinterpret_cast<uint32_t *>(ws + L.off_pos);
+    m.pos = a.idx_out;
+    for (int level = 0; level < kth_levels(kt); ++level) {
+        HIP_TRY(launch_kth_hist(a, rows, level, kt, s));
+        HIP_TRY(launch_kth_pick(a, rows, level, kt, s));
+    }
+    HIP_TRY(launch_kth_locate(a, rows, kt, s));
+    HIP_TRY(launch_tkm_apply(a, m, rows, kt, s));
+    return LABSORT_OK;
+}
+
+int labsort_topk_mask_workspace_status(const void *d_ws, void *stream) { return labsort_kth_workspace_status(d_ws, stream); }
 
 }  // extern "C"

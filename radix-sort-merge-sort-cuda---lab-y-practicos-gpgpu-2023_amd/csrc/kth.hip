@@ -28,10 +28,14 @@
 //
 // Top-k filtering (labsort_topk_mask_device) applies the threshold: the row written back with the
 // first k of its (u, position) pairs kept and the fill elsewhere, and / or their mask.
-//   k_tkm_short  rows of up to KTH_ROW_KEYS keys, one launch: k_kth_short's select, the threshold's
-//                ties ranked in position order, then every thread stores the groups it holds.
+//   k_kth_short<.., FILTER = true>  rows of up to KTH_ROW_KEYS keys, one launch: the same kernel
+//                template, so the load and the level loop stand once; after the select the
+//                threshold's ties are ranked in position order and every thread stores the groups
+//                it holds.  There is no kernel of the filter's own name: a profiler lists the
+//                select as k_kth_short<KT, BLOCK, SLOTS, false> and the filter as <.., true>.
 //   k_tkm_apply  longer rows, after the launches above with positions: one workgroup per (row,
 //                chunk) tests every key against the row's k-th pair and stores.
+// Both instantiations compile to the text the two separate kernels had.
 #include "kth.h"
 
 #include <type_traits>
@@ -94,6 +98,19 @@ template <int KT>
 __device__ __forceinline__ uint32_t kth_load(const kth_elem_t<KT> *base, uint32_t beg, uint32_t end, uint32_t mis, uint32_t q,
                                              uint32_t xr, uint32_t (&u)[KTH_E<KT>], int64_t &i0) {
     return load_group(base, beg, end, mis, q, u, i0, [xr](uint32_t x) { return kth_u<KT>(x, xr); });
+}
+// Chunk c of a long row: its keys [beg, end) and their groups (devutil.h, group_mis / group_count)
+struct KthChunk {
+    uint32_t beg, end, mis, nq;
+};
+template <int KT>
+__device__ __forceinline__ KthChunk kth_chunk(const kth_elem_t<KT> *base, uint32_t cols, uint32_t c) {
+    KthChunk ch;
+    ch.beg = c * TK_CHUNK;
+    ch.end = cols - ch.beg > (uint32_t)TK_CHUNK ? ch.beg + TK_CHUNK : cols;
+    ch.mis = group_mis(base, ch.beg);
+    ch.nq = group_count<KTH_E<KT>>(ch.beg, ch.end, ch.mis);
+    return ch;
 }
 
 // The row's k, clamped into [1, cols]; a k outside is reported in the header by the thread told to
@@ -162,10 +179,69 @@ __device__ __forceinline__ uint32_t kth_ordered_step(uint32_t c, uint32_t &carry
     return before;
 }
 
+// ---- top-k filtering (labsort_topk_mask_device): the row written back with everything outside its
+// first k (u, position) pairs replaced by the fill, and / or the mask of the pairs kept ----
+struct TkmArgs {
+    void *keys_out;       // rows x cols elements of the key type (may be the input itself), or nullptr
+    uint8_t *mask_out;    // rows x cols bytes, or nullptr
+    const uint32_t *pos;  // long rows: [rows], the position of each row's k-th pair (k_kth_locate's output)
+    uint32_t fill;        // what an element outside the top k becomes
+};
+
+// The key of an image, as a word of the key type (kth_write_key's transform)
+template <int KT>
+__device__ __forceinline__ uint32_t kth_unord(uint32_t u, uint32_t xr) {
+    const uint32_t w = u ^ xr;
+    if constexpr (kth_is16(KT)) return unord16(w >> 16);
+    else if constexpr (KT == KTH_F32) return f32_unord(w);
+    else return w;
+}
+
+// Stores one group of a row: elements i0 .. i0 + E - 1 (those of vm exist, rowoff = row * cols), w[j]
+// the word of element j (its key or the fill), bit j of km set where it is kept.  A group that lies
+// wholly inside the row is one 16-byte store of keys and one E-byte store of mask bytes where the
+// address allows it; everything else goes element by element, so that no store covers an element
+// of another row.  The keys' and the mask's alignment are tested each on its own.
+template <int KT>
+__device__ __forceinline__ void tkm_store(const TkmArgs &m, size_t rowoff, int64_t i0, uint32_t vm,
+                                          const uint32_t (&w)[KTH_E<KT>], uint32_t km) {
+    constexpr int E = KTH_E<KT>;
+    constexpr uint32_t FULL = (1u << E) - 1u;
+    using elem_t = kth_elem_t<KT>;
+    if (m.keys_out) {
+        const uintptr_t at = (uintptr_t)m.keys_out + (uintptr_t)(((int64_t)rowoff + i0) * (int64_t)sizeof(elem_t));
+        if (vm == FULL && (at & 15u) == 0u) {
+            uint4 v;
+            if constexpr (E == 4) v = make_uint4(w[0], w[1], w[2], w[3]);
+            else v = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
+            *reinterpret_cast<uint4 *>(at) = v;
+        } else {
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if ((vm >> j) & 1u) reinterpret_cast<elem_t *>(at)[j] = (elem_t)w[j];
+        }
+    }
+    if (m.mask_out) {
+        const uintptr_t at = (uintptr_t)m.mask_out + (uintptr_t)((int64_t)rowoff + i0);
+        // bits 0..3 of x as four bytes of 0 / 1
+        auto spread = [](uint32_t x) { return (x & 1u) | ((x & 2u) << 7) | ((x & 4u) << 14) | ((x & 8u) << 21); };
+        if (vm == FULL && (at & (uintptr_t)(E - 1)) == 0u) {
+            if constexpr (E == 4) *reinterpret_cast<uint32_t *>(at) = spread(km);
+            else *reinterpret_cast<uint2 *>(at) = make_uint2(spread(km), spread(km >> 4));
+        } else {
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if ((vm >> j) & 1u) reinterpret_cast<uint8_t *>(at)[j] = (uint8_t)((km >> j) & 1u);
+        }
+    }
+}
+
 // ---- rows of up to BLOCK * KTH_KPT keys: one workgroup of BLOCK threads, the row in registers;
-// SLOTS counter replicas per digit ----
-template <int KT, int BLOCK, int SLOTS>
-__global__ __launch_bounds__(BLOCK) void k_kth_short(KthArgs a) {
+// SLOTS counter replicas per digit.  FILTER = false: the select, which writes the k-th key and its
+// position (m is not read).  FILTER = true: the top-k filter, which after the same select writes
+// back the groups every thread holds (a.keys_out and a.idx_out are not read) ----
+template <int KT, int BLOCK, int SLOTS, bool FILTER>
+__global__ __launch_bounds__(BLOCK) void k_kth_short(KthArgs a, TkmArgs m) {
     constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
     constexpr int TG = T + 1;  // a row that starts inside a group has one group more
     constexpr int NLEV = kth_levels(KT);
@@ -186,7 +262,7 @@ __global__ __launch_bounds__(BLOCK) void k_kth_short(KthArgs a) {
 #pragma unroll
             for (int j = 0; j < E; ++j) u[t][j] = 0u;
     }
-    uint32_t prefix = 0u, krem = kth_k(a, row, tid == 0u);
+    uint32_t prefix = 0u, krem = kth_k(a, row, tid == 0u), ties = 0u;
     for (int level = 0; level < NLEV; ++level) {
         const uint32_t shift = 24u - 8u * (uint32_t)level;
         const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
@@ -204,6 +280,50 @@ __global__ __launch_bounds__(BLOCK) void k_kth_short(KthArgs a) {
         const KthPick p = kth_pick(hrow, krem, lane);  // (every wave: the same answer)
         prefix |= p.d << shift;
         krem -= p.below;
+        // after the last level: the keys equal to the threshold (hrow stays until the next level's barriers)
+        if constexpr (FILTER) ties = hrow[p.d];
+    }
+    if constexpr (FILTER) {
+        // km[t]: the elements of group (t, tid) that are kept: the keys below the threshold and the first
+        // krem of its ties in position order.  ties == krem (uniform): all of them, no scan.
+        uint32_t km[TG];
+        const bool all_ties = LABSORT_TKM_SKIP_SCAN && ties == krem;
+        uint32_t carry = 0u;
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+            uint32_t lt = 0u, em = 0u;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const bool v = (vm[t] >> j) & 1u;
+                lt |= (v && u[t][j] < prefix ? 1u : 0u) << j;
+                em |= (v && u[t][j] == prefix ? 1u : 0u) << j;
+            }
+            km[t] = lt;
+            if (all_ties) km[t] |= em;
+            else if (carry < krem) {  // (uniform; past it no tie is kept)
+                const uint32_t c = (uint32_t)__popc(em);
+                const uint32_t before = kth_ordered_step<BLOCK>(c, carry, wsum, &tot);
+                const uint32_t room = before < krem ? krem - before : 0u;
+                uint32_t seen = 0u;
+#pragma unroll
+                for (int j = 0; j < E; ++j)
+                    if ((em >> j) & 1u) {
+                        if (seen < room) km[t] |= 1u << j;
+                        ++seen;
+                    }
+            }
+        }
+        const size_t rowoff = (size_t)row * a.cols;
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+            const uint32_t q = (uint32_t)t * BLOCK + tid;
+            if (q >= nq) continue;
+            uint32_t w[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) w[j] = (km[t] >> j) & 1u ? kth_unord<KT>(u[t][j], a.xr) : m.fill;
+            tkm_store<KT>(m, rowoff, (int64_t)E * q - (int64_t)mis, vm[t], w, km[t]);
+        }
+        return;
     }
     if (a.idx_out) {
         // groups in position order: (t, tid); krem: the rank of the k-th key among the keys equal to prefix
@@ -254,16 +374,15 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_kth_hist(KthArgs a, int level, ui
         }
         slot_hist_clear<TK_SLOTS, KTH_BLOCK>(h, tid);
         __syncthreads();
-        const uint32_t beg = c * TK_CHUNK, end = a.cols - beg > (uint32_t)TK_CHUNK ? beg + TK_CHUNK : a.cols;
-        const uint32_t mis = group_mis(base, beg), nq = group_count<E>(beg, end, mis);
-        for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)T * KTH_BLOCK) {
+        const KthChunk ch = kth_chunk<KT>(base, a.cols, c);
+        for (uint32_t q0 = 0; q0 < ch.nq; q0 += (uint32_t)T * KTH_BLOCK) {
             uint32_t u[T][E], vm[T];
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 const uint32_t q = q0 + (uint32_t)t * KTH_BLOCK + tid;
                 int64_t i0;
                 vm[t] = 0u;
-                if (q < nq) vm[t] = kth_load<KT>(base, beg, end, mis, q, xr, u[t], i0);
+                if (q < ch.nq) vm[t] = kth_load<KT>(base, ch.beg, ch.end, ch.mis, q, xr, u[t], i0);
                 else
 #pragma unroll
                     for (int j = 0; j < E; ++j) u[t][j] = 0u;
@@ -341,14 +460,13 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_kth_locate(KthArgs a) {
     const KthState st = a.st[(size_t)row * (TK_LEVELS + 1) + kth_levels(KT)];
     const uint32_t c = st.cstar < a.nch ? st.cstar : a.nch - 1u;
     const kth_elem_t<KT> *base = kth_row<KT>(a, row);
-    const uint32_t beg = c * TK_CHUNK, end = a.cols - beg > (uint32_t)TK_CHUNK ? beg + TK_CHUNK : a.cols;
-    const uint32_t mis = group_mis(base, beg), nq = group_count<E>(beg, end, mis);
+    const KthChunk ch = kth_chunk<KT>(base, a.cols, c);
     uint32_t carry = 0u;
-    for (uint32_t q0 = 0; q0 < nq && carry < st.krem; q0 += KTH_BLOCK) {  // (uniform)
+    for (uint32_t q0 = 0; q0 < ch.nq && carry < st.krem; q0 += KTH_BLOCK) {  // (uniform)
         const uint32_t q = q0 + tid;
         uint32_t u[E], vm = 0u;
         int64_t i0 = 0;
-        if (q < nq) vm = kth_load<KT>(base, beg, end, mis, q, a.xr, u, i0);
+        if (q < ch.nq) vm = kth_load<KT>(base, ch.beg, ch.end, ch.mis, q, a.xr, u, i0);
         uint32_t em = 0u;
 #pragma unroll
         for (int j = 0; j < E; ++j) em |= (((vm >> j) & 1u) && u[j] == st.prefix ? 1u : 0u) << j;
@@ -360,190 +478,8 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_kth_locate(KthArgs a) {
     if (tid == 0u) kth_write_key(a.keys_out, row, st.prefix, a.xr, KT);
 }
 
-// kt: KthKey, the instantiation that runs
-template <int BLOCK, int SLOTS>
-hipError_t launch_kth_short_as(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
-    const unsigned grid = (unsigned)rows;
-    if (kt == KTH_BF16) k_kth_short<KTH_BF16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
-    else if (kt == KTH_F16) k_kth_short<KTH_F16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
-    else if (kt == KTH_F32) k_kth_short<KTH_F32, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
-    else k_kth_short<KTH_INT, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a);
-    return hipGetLastError();
-}
-hipError_t launch_kth_short(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
-    if (a.cols <= (uint32_t)KTH_SMALL_ROW_KEYS) return launch_kth_short_as<KTH_SMALL_BLOCK, KTH_SMALL_SLOTS>(a, rows, kt, s);
-    return launch_kth_short_as<KTH_BLOCK, TK_SLOTS>(a, rows, kt, s);
-}
-
-hipError_t launch_kth_hist(const KthArgs &a, size_t rows, int level, int kt, hipStream_t s) {
-    const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
-    const uint32_t nx = (a.nch + g - 1u) / g;
-    const unsigned grid = (unsigned)(rows * nx);
-    if (kt == KTH_BF16) k_kth_hist<KTH_BF16><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
-    else if (kt == KTH_F16) k_kth_hist<KTH_F16><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
-    else if (kt == KTH_F32) k_kth_hist<KTH_F32><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
-    else k_kth_hist<KTH_INT><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g);
-    return hipGetLastError();
-}
-
-hipError_t launch_kth_pick(const KthArgs &a, size_t rows, int level, int kt, hipStream_t s) {
-    k_kth_pick<<<(unsigned)rows, KTH_BLOCK, 0, s>>>(a, level, level == kth_levels(kt) - 1, kt);
-    return hipGetLastError();
-}
-
-hipError_t launch_kth_locate(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
-    const unsigned grid = (unsigned)rows;
-    if (kt == KTH_BF16) k_kth_locate<KTH_BF16><<<grid, KTH_BLOCK, 0, s>>>(a);
-    else if (kt == KTH_F16) k_kth_locate<KTH_F16><<<grid, KTH_BLOCK, 0, s>>>(a);
-    else if (kt == KTH_F32) k_kth_locate<KTH_F32><<<grid, KTH_BLOCK, 0, s>>>(a);
-    else k_kth_locate<KTH_INT><<<grid, KTH_BLOCK, 0, s>>>(a);
-    return hipGetLastError();
-}
-
-// ---- top-k filtering (labsort_topk_mask_device): the row written back with everything outside its
-// first k (u, position) pairs replaced by the fill, and / or the mask of the pairs kept ----
-struct TkmArgs {
-    void *keys_out;       // rows x cols elements of the key type (may be the input itself), or nullptr
-    uint8_t *mask_out;    // rows x cols bytes, or nullptr
-    const uint32_t *pos;  // long rows: [rows], the position of each row's k-th pair (k_kth_locate's output)
-    uint32_t fill;        // what an element outside the top k becomes
-};
-
-// The key of an image, as a word of the key type (kth_write_key's transform)
-template <int KT>
-__device__ __forceinline__ uint32_t kth_unord(uint32_t u, uint32_t xr) {
-    const uint32_t w = u ^ xr;
-    if constexpr (kth_is16(KT)) return unord16(w >> 16);
-    else if constexpr (KT == KTH_F32) return f32_unord(w);
-    else return w;
-}
-
-// Stores one group of a row: elements i0 .. i0 + E - 1 (those of vm exist, rowoff = row * cols), w[j]
-// the word of element j (its key or the fill), bit j of km set where it is kept.  A group that lies
-// wholly inside the row is one 16-byte store of keys and one E-byte store of mask bytes where the
-// address allows it; everything else goes element by element, so that no store covers an element
-// of another row.  The keys' and the mask's alignment are tested each on its own.
-template <int KT>
-__device__ __forceinline__ void tkm_store(const TkmArgs &m, size_t rowoff, int64_t i0, uint32_t vm,
-                                          const uint32_t (&w)[KTH_E<KT>], uint32_t km) {
-    constexpr int E = KTH_E<KT>;
-    constexpr uint32_t FULL = (1u << E) - 1u;
-    using elem_t = kth_elem_t<KT>;
-    if (m.keys_out) {
-        const uintptr_t at = (uintptr_t)m.keys_out + (uintptr_t)(((int64_t)rowoff + i0) * (int64_t)sizeof(elem_t));
-        if (vm == FULL && (at & 15u) == 0u) {
-            uint4 v;
-            if constexpr (E == 4) v = make_uint4(w[0], w[1], w[2], w[3]);
-            else v = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
-            *reinterpret_cast<uint4 *>(at) = v;
-        } else {
-#pragma unroll
-            for (int j = 0; j < E; ++j)
-                if ((vm >> j) & 1u) reinterpret_cast<elem_t *>(at)[j] = (elem_t)w[j];
-        }
-    }
-    if (m.mask_out) {
-        const uintptr_t at = (uintptr_t)m.mask_out + (uintptr_t)((int64_t)rowoff + i0);
-        // bits 0..3 of x as four bytes of 0 / 1
-        auto spread = [](uint32_t x) { return (x & 1u) | ((x & 2u) << 7) | ((x & 4u) << 14) | ((x & 8u) << 21); };
-        if (vm == FULL && (at & (uintptr_t)(E - 1)) == 0u) {
-            if constexpr (E == 4) *reinterpret_cast<uint32_t *>(at) = spread(km);
-            else *reinterpret_cast<uint2 *>(at) = make_uint2(spread(km), spread(km >> 4));
-        } else {
-#pragma unroll
-            for (int j = 0; j < E; ++j)
-                if ((vm >> j) & 1u) reinterpret_cast<uint8_t *>(at)[j] = (uint8_t)((km >> j) & 1u);
-        }
-    }
-}
-
-// Rows of up to BLOCK * KTH_KPT keys: k_kth_short's select (a copy: shared, the select kernels'
-// registers would be the filter's), then every thread writes back the groups it holds.
-template <int KT, int BLOCK, int SLOTS>
-__global__ __launch_bounds__(BLOCK) void k_tkm_short(KthArgs a, TkmArgs m) {
-    constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
-    constexpr int TG = T + 1;  // a row that starts inside a group has one group more
-    constexpr int NLEV = kth_levels(KT);
-    __shared__ uint32_t h[256 * SLOTS];
-    __shared__ __attribute__((aligned(16))) uint32_t hrow[256];
-    __shared__ uint32_t wsum[BLOCK / WAVE], tot;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
-    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
-    const uint32_t mis = group_mis(base, 0u), nq = group_count<E>(0u, a.cols, mis);  // <= T * BLOCK + 1
-    uint32_t u[TG][E], vm[TG];
-#pragma unroll
-    for (int t = 0; t < TG; ++t) {
-        const uint32_t q = (uint32_t)t * BLOCK + tid;
-        int64_t i0;
-        vm[t] = 0u;
-        if (q < nq) vm[t] = kth_load<KT>(base, 0u, a.cols, mis, q, a.xr, u[t], i0);
-        else
-#pragma unroll
-            for (int j = 0; j < E; ++j) u[t][j] = 0u;
-    }
-    uint32_t prefix = 0u, krem = kth_k(a, row, tid == 0u), ties = 0u;
-    for (int level = 0; level < NLEV; ++level) {
-        const uint32_t shift = 24u - 8u * (uint32_t)level;
-        const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
-        slot_hist_clear<SLOTS, BLOCK>(h, tid);
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TG; ++t)
-#pragma unroll
-            for (int j = 0; j < E; ++j)
-                if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u)
-                    slot_hist_add<SLOTS>(h, (u[t][j] >> shift) & 255u, tid);
-        __syncthreads();
-        if (tid < 256u) hrow[tid] = slot_hist_fold<SLOTS>(h, tid);
-        __syncthreads();
-        const KthPick p = kth_pick(hrow, krem, lane);  // (every wave: the same answer)
-        prefix |= p.d << shift;
-        krem -= p.below;
-        ties = hrow[p.d];  // after the last level: the keys equal to the threshold (hrow stays until the next level's barriers)
-    }
-    // km[t]: the elements of group (t, tid) that are kept: the keys below the threshold and the first
-    // krem of its ties in position order.  ties == krem (uniform): all of them, no scan.
-    uint32_t km[TG];
-    const bool all_ties = LABSORT_TKM_SKIP_SCAN && ties == krem;
-    uint32_t carry = 0u;
-#pragma unroll
-    for (int t = 0; t < TG; ++t) {
-        uint32_t lt = 0u, em = 0u;
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            const bool v = (vm[t] >> j) & 1u;
-            lt |= (v && u[t][j] < prefix ? 1u : 0u) << j;
-            em |= (v && u[t][j] == prefix ? 1u : 0u) << j;
-        }
-        km[t] = lt;
-        if (all_ties) km[t] |= em;
-        else if (carry < krem) {  // (uniform; past it no tie is kept)
-            const uint32_t c = (uint32_t)__popc(em);
-            const uint32_t before = kth_ordered_step<BLOCK>(c, carry, wsum, &tot);
-            const uint32_t room = before < krem ? krem - before : 0u;
-            uint32_t seen = 0u;
-#pragma unroll
-            for (int j = 0; j < E; ++j)
-                if ((em >> j) & 1u) {
-                    if (seen < room) km[t] |= 1u << j;
-                    ++seen;
-                }
-        }
-    }
-    const size_t rowoff = (size_t)row * a.cols;
-#pragma unroll
-    for (int t = 0; t < TG; ++t) {
-        const uint32_t q = (uint32_t)t * BLOCK + tid;
-        if (q >= nq) continue;
-        uint32_t w[E];
-#pragma unroll
-        for (int j = 0; j < E; ++j) w[j] = (km[t] >> j) & 1u ? kth_unord<KT>(u[t][j], a.xr) : m.fill;
-        tkm_store<KT>(m, rowoff, (int64_t)E * q - (int64_t)mis, vm[t], w, km[t]);
-    }
-}
-
-// Longer rows, after the select with positions: one workgroup per (row, chunk) streams its chunk
-// through the test against the row's k-th pair (uT, P).
+// The filter's longer rows, after the select with positions: one workgroup per (row, chunk) streams
+// its chunk through the test against the row's k-th pair (uT, P).
 template <int KT>
 __global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m) {
     constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
@@ -552,9 +488,8 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m) {
     const uint32_t uT = a.st[(size_t)row * (TK_LEVELS + 1) + kth_levels(KT)].prefix, P = m.pos[row];
     const kth_elem_t<KT> *base = kth_row<KT>(a, row);
     const size_t rowoff = (size_t)row * a.cols;
-    const uint32_t beg = c * TK_CHUNK, end = a.cols - beg > (uint32_t)TK_CHUNK ? beg + TK_CHUNK : a.cols;
-    const uint32_t mis = group_mis(base, beg), nq = group_count<E>(beg, end, mis);
-    for (uint32_t q0 = 0; q0 < nq; q0 += (uint32_t)T * KTH_BLOCK) {
+    const KthChunk ch = kth_chunk<KT>(base, a.cols, c);
+    for (uint32_t q0 = 0; q0 < ch.nq; q0 += (uint32_t)T * KTH_BLOCK) {
         uint32_t u[T][E], vm[T];
         int64_t i0[T];
 #pragma unroll
@@ -562,7 +497,7 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m) {
             const uint32_t q = q0 + (uint32_t)t * KTH_BLOCK + tid;
             vm[t] = 0u;
             i0[t] = 0;
-            if (q < nq) vm[t] = kth_load<KT>(base, beg, end, mis, q, a.xr, u[t], i0[t]);
+            if (q < ch.nq) vm[t] = kth_load<KT>(base, ch.beg, ch.end, ch.mis, q, a.xr, u[t], i0[t]);
         }
 #pragma unroll
         for (int t = 0; t < T; ++t) {
@@ -579,27 +514,60 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m) {
     }
 }
 
-template <int BLOCK, int SLOTS>
-hipError_t launch_tkm_short_as(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
+// ---- launches.  kt: KthKey, the instantiation that runs: f gets it as a constant ----
+template <class F>
+void kth_dispatch(int kt, F f) {
+    if (kt == KTH_BF16) f(std::integral_constant<int, KTH_BF16>{});
+    else if (kt == KTH_F16) f(std::integral_constant<int, KTH_F16>{});
+    else if (kt == KTH_F32) f(std::integral_constant<int, KTH_F32>{});
+    else f(std::integral_constant<int, KTH_INT>{});
+}
+
+// FILTER = false: the select (m: TkmArgs{}).  FILTER = true: the top-k filter.
+template <bool FILTER>
+hipError_t launch_kth_short(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
     const unsigned grid = (unsigned)rows;
-    if (kt == KTH_BF16) k_tkm_short<KTH_BF16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
-    else if (kt == KTH_F16) k_tkm_short<KTH_F16, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
-    else if (kt == KTH_F32) k_tkm_short<KTH_F32, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
-    else k_tkm_short<KTH_INT, BLOCK, SLOTS><<<grid, BLOCK, 0, s>>>(a, m);
+    kth_dispatch(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        if (a.cols <= (uint32_t)KTH_SMALL_ROW_KEYS)
+            k_kth_short<KT, KTH_SMALL_BLOCK, KTH_SMALL_SLOTS, FILTER><<<grid, KTH_SMALL_BLOCK, 0, s>>>(a, m);
+        else k_kth_short<KT, KTH_BLOCK, TK_SLOTS, FILTER><<<grid, KTH_BLOCK, 0, s>>>(a, m);
+    });
     return hipGetLastError();
 }
-hipError_t launch_tkm_short(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
-    if (a.cols <= (uint32_t)KTH_SMALL_ROW_KEYS) return launch_tkm_short_as<KTH_SMALL_BLOCK, KTH_SMALL_SLOTS>(a, m, rows, kt, s);
-    return launch_tkm_short_as<KTH_BLOCK, TK_SLOTS>(a, m, rows, kt, s);
+
+hipError_t launch_kth_hist(const KthArgs &a, size_t rows, int level, int kt, hipStream_t s) {
+    const uint32_t g = (a.nch + TK_MAX_HIST_WG - 1u) / TK_MAX_HIST_WG;  // chunks per workgroup
+    const uint32_t nx = (a.nch + g - 1u) / g;
+    const unsigned grid = (unsigned)(rows * nx);
+    kth_dispatch(kt, [&](auto K) { k_kth_hist<decltype(K)::value><<<grid, KTH_BLOCK, 0, s>>>(a, level, nx, g); });
+    return hipGetLastError();
+}
+
+hipError_t launch_kth_pick(const KthArgs &a, size_t rows, int level, int kt, hipStream_t s) {
+    k_kth_pick<<<(unsigned)rows, KTH_BLOCK, 0, s>>>(a, level, level == kth_levels(kt) - 1, kt);
+    return hipGetLastError();
+}
+
+hipError_t launch_kth_locate(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
+    kth_dispatch(kt, [&](auto K) { k_kth_locate<decltype(K)::value><<<(unsigned)rows, KTH_BLOCK, 0, s>>>(a); });
+    return hipGetLastError();
 }
 
 hipError_t launch_tkm_apply(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
     const unsigned grid = (unsigned)(rows * a.nch);
-    if (kt == KTH_BF16) k_tkm_apply<KTH_BF16><<<grid, KTH_BLOCK, 0, s>>>(a, m);
-    else if (kt == KTH_F16) k_tkm_apply<KTH_F16><<<grid, KTH_BLOCK, 0, s>>>(a, m);
-    else if (kt == KTH_F32) k_tkm_apply<KTH_F32><<<grid, KTH_BLOCK, 0, s>>>(a, m);
-    else k_tkm_apply<KTH_INT><<<grid, KTH_BLOCK, 0, s>>>(a, m);
+    kth_dispatch(kt, [&](auto K) { k_tkm_apply<decltype(K)::value><<<grid, KTH_BLOCK, 0, s>>>(a, m); });
     return hipGetLastError();
+}
+
+// Longer rows: a histogram and a pick per level, then the position where the call has one
+int run_kth_long(const KthArgs &a, size_t rows, int kt, hipStream_t s) {
+    for (int level = 0; level < kth_levels(kt); ++level) {
+        HIP_TRY(launch_kth_hist(a, rows, level, kt, s));
+        HIP_TRY(launch_kth_pick(a, rows, level, kt, s));
+    }
+    if (a.idx_out) HIP_TRY(launch_kth_locate(a, rows, kt, s));
+    return LABSORT_OK;
 }
 
 // header | hist | per-row states | per-chunk counts.  Header and histograms are the only words a
@@ -641,6 +609,42 @@ TkmLayout tkm_layout(size_t rows, size_t cols) {
     return L;
 }
 
+// What both entry points refuse alike, rows and cols != 0: the key type, a host k outside
+// [1, cols], more than 2^31 - 1 elements, a 16-bit key pointer at an odd address (keys_out may be
+// nullptr).  Outputs and aliases are each entry's own.
+bool kth_call_ok(const void *d_keys, const void *d_keys_out, size_t rows, size_t cols, size_t k, const uint32_t *d_k, int key_type) {
+    if (!d_keys || !topk_key_type_ok(key_type)) return false;
+    if (!d_k && (k == 0 || k > cols)) return false;
+    if (rows > (size_t)0x7FFFFFFFu / cols) return false;
+    return !(key_type_is16(key_type) && (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u));
+}
+
+// A checked call's key type as KthKey and what its kernels read, but for the outputs: the input,
+// k, the order and, for long rows (L.nch != 0), the workspace's tables
+struct KthCall {
+    int kt;
+    KthArgs a;
+};
+KthCall kth_call(const void *d_keys, size_t cols, size_t k, const uint32_t *d_k, int largest, int key_type, void *d_ws, const KthLayout &L) {
+    char *ws = static_cast<char *>(d_ws);
+    KthCall c{};
+    c.kt = key_type == LABSORT_KEY_F32 ? KTH_F32 : key_type == LABSORT_KEY_BF16 ? KTH_BF16 : key_type == LABSORT_KEY_F16 ? KTH_F16 : KTH_INT;
+    c.a.keys = d_keys;
+    c.a.d_k = d_k;
+    c.a.hdr = reinterpret_cast<uint32_t *>(ws);
+    c.a.cols = (uint32_t)cols;
+    c.a.k = (uint32_t)(d_k ? 1 : k);
+    c.a.nch = (uint32_t)L.nch;
+    // 16-bit keys: u = (ord16(key) << 16) ^ xr, its low half clear
+    c.a.xr = kth_is16(c.kt) ? (largest ? 0xFFFF0000u : 0u) : flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
+    if (L.nch) {
+        c.a.hist = reinterpret_cast<uint32_t *>(ws + L.off_hist);
+        c.a.st = reinterpret_cast<KthState *>(ws + L.off_st);
+        c.a.cnt = reinterpret_cast<uint32_t *>(ws + L.off_cnt);
+    }
+    return c;
+}
+
 }  // namespace
 
 }  // namespace labsort
@@ -657,13 +661,8 @@ int labsort_kth_device(const void *d_keys, size_t rows, size_t cols, size_t k, c
                        void *d_keys_out, uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
     static_assert(KTH_HDR_BYTES == 256, "labsort.h states the header's size");
     if (rows == 0 || cols == 0) return LABSORT_OK;
-    if (!d_keys || !d_keys_out) return LABSORT_ERR_ARG;
-    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
-    if (!d_k && (k == 0 || k > cols)) return LABSORT_ERR_ARG;
-    if (rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
-    const bool k16 = key_type_is16(key_type);
-    const size_t esz = k16 ? 2 : 4;  // bytes per key
-    if (k16 && (((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u)) return LABSORT_ERR_ARG;
+    if (!d_keys_out || !kth_call_ok(d_keys, d_keys_out, rows, cols, k, d_k, key_type)) return LABSORT_ERR_ARG;
+    const size_t esz = key_type_is16(key_type) ? 2 : 4;  // bytes per key
     if (d_idx_out == d_keys_out) return LABSORT_ERR_ARG;
     const size_t in_bytes = rows * cols * esz, ko_bytes = rows * esz, w_bytes = rows * 4;
     if (ranges_overlap(d_keys, in_bytes, d_keys_out, ko_bytes)) return LABSORT_ERR_ARG;
@@ -673,34 +672,14 @@ int labsort_kth_device(const void *d_keys, size_t rows, size_t cols, size_t k, c
     if (d_k && d_idx_out && ranges_overlap(d_k, w_bytes, d_idx_out, w_bytes)) return LABSORT_ERR_ARG;
     const KthLayout L = kth_layout(rows, cols);
     if (!d_ws || ws_bytes < L.total) return LABSORT_ERR_ARG;
-    const int kt = key_type == LABSORT_KEY_F32 ? KTH_F32 : key_type == LABSORT_KEY_BF16 ? KTH_BF16 : key_type == LABSORT_KEY_F16 ? KTH_F16 : KTH_INT;
     hipStream_t s = as_stream(stream);
-    char *ws = static_cast<char *>(d_ws);
-    KthArgs a{};
-    a.keys = d_keys;
-    a.d_k = d_k;
-    a.hdr = reinterpret_cast<uint32_t *>(ws);
-    a.keys_out = d_keys_out;
-    a.idx_out = d_idx_out;
-    a.cols = (uint32_t)cols;
-    a.k = (uint32_t)(d_k ? 1 : k);
-    a.nch = (uint32_t)L.nch;
-    // 16-bit keys: u = (ord16(key) << 16) ^ xr, its low half clear
-    a.xr = k16 ? (largest ? 0xFFFF0000u : 0u) : flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);
-    HIP_TRY(launch_zero(ws, L.zero_bytes, s));  // (a kernel: graph-replayable)
+    KthCall c = kth_call(d_keys, cols, k, d_k, largest, key_type, d_ws, L);
+    c.a.keys_out = d_keys_out;
+    c.a.idx_out = d_idx_out;
+    HIP_TRY(launch_zero(d_ws, L.zero_bytes, s));  // (a kernel: graph-replayable)
     TimingScope ts(LABSORT_K_TOPK, s);
-    if (cols <= (size_t)KTH_ROW_KEYS) {
-        HIP_TRY(launch_kth_short(a, rows, kt, s));
-        return LABSORT_OK;
-    }
-    a.hist = reinterpret_cast<uint32_t *>(ws + L.off_hist);
-    a.st = reinterpret_cast<KthState *>(ws + L.off_st);
-    a.cnt = reinterpret_cast<uint32_t *>(ws + L.off_cnt);
-    for (int level = 0; level < kth_levels(kt); ++level) {
-        HIP_TRY(launch_kth_hist(a, rows, level, kt, s));
-        HIP_TRY(launch_kth_pick(a, rows, level, kt, s));
-    }
-    if (d_idx_out) HIP_TRY(launch_kth_locate(a, rows, kt, s));
+    if (cols > (size_t)KTH_ROW_KEYS) return run_kth_long(c.a, rows, c.kt, s);
+    HIP_TRY(launch_kth_short<false>(c.a, TkmArgs{}, rows, c.kt, s));
     return LABSORT_OK;
 }
 
@@ -716,13 +695,11 @@ int labsort_topk_mask_device(const void *d_keys, size_t rows, size_t cols, size_
                              int key_type, uint32_t fill_bits, void *d_keys_out, uint8_t *d_mask_out, void *d_ws,
                              size_t ws_bytes, void *stream) {
     if (rows == 0 || cols == 0) return LABSORT_OK;
-    if (!d_keys || (!d_keys_out && !d_mask_out)) return LABSORT_ERR_ARG;
-    if (!topk_key_type_ok(key_type)) return LABSORT_ERR_ARG;
-    if (!d_k && (k == 0 || k > cols)) return LABSORT_ERR_ARG;
-    if (rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    if (!d_keys_out && !d_mask_out) return LABSORT_ERR_ARG;
+    if (!kth_call_ok(d_keys, d_keys_out, rows, cols, k, d_k, key_type)) return LABSORT_ERR_ARG;
     const bool k16 = key_type_is16(key_type);
     const size_t esz = k16 ? 2 : 4;  // bytes per key
-    if (k16 && ((((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u) || (fill_bits >> 16))) return LABSORT_ERR_ARG;
+    if (k16 && (fill_bits >> 16)) return LABSORT_ERR_ARG;
     // the one alias: the keys written over the input, element for element
     const size_t key_bytes = rows * cols * esz, mask_bytes = rows * cols, w_bytes = rows * 4;
     if (d_keys_out && d_keys_out != d_keys && ranges_overlap(d_keys, key_bytes, d_keys_out, key_bytes)) return LABSORT_ERR_ARG;
@@ -733,17 +710,9 @@ int labsort_topk_mask_device(const void *d_keys, size_t rows, size_t cols, size_
     if (d_k && d_mask_out && ranges_overlap(d_k, w_bytes, d_mask_out, mask_bytes)) return LABSORT_ERR_ARG;
     const TkmLayout L = tkm_layout(rows, cols);
     if (!d_ws || ws_bytes < L.total) return LABSORT_ERR_ARG;
-    const int kt = key_type == LABSORT_KEY_F32 ? KTH_F32 : key_type == LABSORT_KEY_BF16 ? KTH_BF16 : key_type == LABSORT_KEY_F16 ? KTH_F16 : KTH_INT;
     hipStream_t s = as_stream(stream);
     char *ws = static_cast<char *>(d_ws);
-    KthArgs a{};
-    a.keys = d_keys;
-    a.d_k = d_k;
-    a.hdr = reinterpret_cast<uint32_t *>(ws);
-    a.cols = (uint32_t)cols;
-    a.k = (uint32_t)(d_k ? 1 : k);
-    a.nch = (uint32_t)L.kth.nch;
-    a.xr = k16 ? (largest ? 0xFFFF0000u : 0u) : flip_of(key_type) ^ (largest ? 0xFFFFFFFFu : 0u);  // (as labsort_kth_device)
+    KthCall c = kth_call(d_keys, cols, k, d_k, largest, key_type, d_ws, L.kth);
     TkmArgs m{};
     m.keys_out = d_keys_out;
     m.mask_out = d_mask_out;
@@ -751,22 +720,15 @@ int labsort_topk_mask_device(const void *d_keys, size_t rows, size_t cols, size_
     HIP_TRY(launch_zero(ws, L.kth.zero_bytes, s));
     TimingScope ts(LABSORT_K_TOPK, s);
     if (cols <= (size_t)KTH_ROW_KEYS) {
-        HIP_TRY(launch_tkm_short(a, m, rows, kt, s));
+        HIP_TRY(launch_kth_short<true>(c.a, m, rows, c.kt, s));
         return LABSORT_OK;
     }
     // the select with positions, its outputs in the workspace, then the streaming pass
-    a.hist = reinterpret_cast<uint32_t *>(ws + L.kth.off_hist);
-    a.st = reinterpret_cast<KthState *>(ws + L.kth.off_st);
-    a.cnt = reinterpret_cast<uint32_t *>(ws + L.kth.off_cnt);
-    a.keys_out = ws + L.off_key;
-    a.idx_out = reinterpret_cast<uint32_t *>(ws + L.off_pos);
-    m.pos = a.idx_out;
-    for (int level = 0; level < kth_levels(kt); ++level) {
-        HIP_TRY(launch_kth_hist(a, rows, level, kt, s));
-        HIP_TRY(launch_kth_pick(a, rows, level, kt, s));
-    }
-    HIP_TRY(launch_kth_locate(a, rows, kt, s));
-    HIP_TRY(launch_tkm_apply(a, m, rows, kt, s));
+    c.a.keys_out = ws + L.off_key;
+    c.a.idx_out = reinterpret_cast<uint32_t *>(ws + L.off_pos);
+    m.pos = c.a.idx_out;
+    if (const int st = run_kth_long(c.a, rows, c.kt, s)) return st;
+    HIP_TRY(launch_tkm_apply(c.a, m, rows, c.kt, s));
     return LABSORT_OK;
 }
 

@@ -171,6 +171,37 @@ def test_ties_across_chunks(ls, torch_gpu, kind):
         check(ls, torch_gpu, x[:1], int(ks[3]), largest, kind, keys=False)
 
 
+@pytest.mark.parametrize("kind", ["i32", "f32", "bf16"])
+@pytest.mark.parametrize("cols", [65, 4096, 4097, C])
+def test_select_and_filter_agree(ls, torch_gpu, cols, kind):
+    """Short rows, where kth_device and topk_mask_device run one kernel template: the two calls
+    against each other, no model between them.  Half of the keys take one of four values, so the
+    threshold has many ties.  With (T, P) what the select returns for a row: the mask has k ones,
+    the last kept tie of T sits at P, and no kept key is worse than T."""
+    torch = torch_gpu
+    rows = 3
+    rng = np.random.default_rng(0x7A50 + cols)
+    x = R.random_words((rows, cols), 0x7A51 + cols, kind)
+    four = x[0, :4].copy()
+    tied = rng.random((rows, cols)) < 0.5
+    x[tied] = four[rng.integers(0, 4, size=int(tied.sum()))]
+    d = to_dev(torch, x, kind).cuda()
+    for largest in BOTH:
+        u = R.u_of(x, kind, largest)
+        for k in sorted({1, cols // 2, cols}):
+            ko = torch.empty(rows, dtype=sdtype(torch, kind), device="cuda")
+            io = torch.empty(rows, dtype=torch.int32, device="cuda")
+            ls.kth_device(d, rows, cols, k, ko, io, largest=largest, key=kind)
+            uT = R.u_of(ko.cpu().numpy().view(R.wdtype(kind)).reshape(rows, 1), kind, largest)[:, 0]
+            P = io.cpu().numpy().view(np.uint32)
+            _, gm = run(ls, torch, x, k, largest, kind)
+            for r in range(rows):
+                msg = f"{kind} cols={cols} k={k} largest={largest} row {r}"
+                assert int(gm[r].sum()) == k, msg
+                assert int(np.flatnonzero((u[r] == uT[r]) & (gm[r] != 0))[-1]) == int(P[r]), msg
+                assert int(u[r][gm[r] != 0].max()) <= int(uT[r]), msg
+
+
 @KINDS
 @pytest.mark.parametrize("cols", [1000, 3 * C - 1])
 def test_all_equal_rows(ls, torch_gpu, cols, kind):

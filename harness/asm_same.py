@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""asm_same.py OLD.s NEW.s -- are the kernels of two device-only assembly listings of kth.hip
+"""asm_same.py [--allow-new] OLD.s NEW.s -- are the kernels of two device-only assembly listings of kth.hip
 (hipcc --cuda-device-only -S, the Makefile's flags) the same instruction streams?  Comments,
 directives and block labels are dropped, the function number in a branch target too; what is
 left is compared line by line, kernel by kernel, and one `same` or `DIFFERS` line is printed for
 each.  Names are compared demangled, the old k_tkm_short<KT, B, S> as k_kth_short<KT, B, S, true>
-and the old k_kth_short<KT, B, S> as <KT, B, S, false>.  Exit status 1 unless
-every kernel of either file is in the other and the same."""
+the old k_kth_short<KT, B, S> as <KT, B, S, false> and the old k_tkm_apply<KT> as
+k_tkm_apply<KT, false>.  Exit status 1 unless every kernel of either file is in the
+other and the same; with --allow-new a kernel that only NEW has is listed as `new` and does not count
+(a feature adds kernels and must leave the others alone)."""
 import re
 import subprocess
 import sys
@@ -34,13 +36,20 @@ def kernels(path):
             kernel, targs = "k_kth_short", targs + ", true"
         elif kernel == "k_kth_short" and targs.count(",") == 2:
             targs += ", false"
+        elif kernel == "k_tkm_apply" and "," not in targs:
+            targs += ", false"
         out[f"{kernel}<{targs}>" if targs else kernel] = body[mangled]
     return out
 
 
-old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+allow_new = "--allow-new" in sys.argv[1:]
+paths = [a for a in sys.argv[1:] if a != "--allow-new"]
+old, new = kernels(paths[0]), kernels(paths[1])
 bad = 0
 for k in sorted(set(old) | set(new)):
+    if allow_new and k not in old:
+        print(f"new  {k}  ({len(new[k])} instructions)")
+        continue
     if k not in old or k not in new:
         print(f"ONLY IN {'OLD' if k in old else 'NEW'}  {k}")
     elif old[k] != new[k]:

@@ -659,6 +659,72 @@ int labsort_topk_mask_device(const void *d_keys, size_t rows, size_t cols, size_
                              uint8_t *d_mask_out, void *d_workspace, size_t workspace_bytes, void *stream);
 int labsort_topk_mask_workspace_status(const void *d_workspace, void *stream);
 
+/* ---- top-p (nucleus) filtering per row: every row reduced to the smallest prefix of its most
+ * probable elements whose mass reaches p, with a p per request, and / or the mask of the elements
+ * kept and their number (the step of a sampler after the softmax; no lab.cu counterpart) ----
+ * d_keys is a dense rows x cols matrix of non-negative weights, normally probabilities; key_type:
+ * F32, BF16 or F16 (every other type is LABSORT_ERR_ARG), the 16-bit types with 2-byte elements and
+ * 2-byte alignment.  All sums are integers, so the result is exact, repeatable and the same in any
+ * order of summation:
+ * Weight.  An element x weighs w = min(floor(x 2^40), 2^40); 0 if its sign bit is set (-0.0 and -inf
+ * too) or if it is a NaN; +inf and everything from 1.0 up weigh 2^40.  The weight is taken from the
+ * bit pattern with integer shifts (a 16-bit key as its exact float32 value), on the device and in
+ * labsort_top_p_weight (host; 0 for a key type the entry does not take), so neither a denormal mode
+ * nor contraction can change it.  cols <= 2^23 keeps a row's total below 2^63; a longer row is
+ * LABSORT_ERR_ARG.
+ * Target.  W_r is the sum of row r's weights, P_r = clamp(floor(p_r 2^32), 1, 2^32) for the row's
+ * float32 p_r (from its bits as well), and t_r = max(1, ceil(P_r W_r / 2^32)), the product in 96 bits.
+ * Order.  That of labsort_sort_rows_device(descending = 1): the row's (u, position) pairs ascending,
+ * u the complemented order image: NaNs are equal and first, equal keys come in order of position.
+ * Kept.  k_r is the smallest n such that the weights of the first n entries of that order sum to at
+ * least t_r, and the row keeps exactly those n elements: the outputs are what
+ * labsort_topk_mask_device(largest = 1) gives with d_k[r] = k_r, element for element.  Elements of
+ * weight zero ahead of the threshold (the NaNs) are kept; those behind the last element with a
+ * weight are never kept, not even at p = 1.
+ * A row with W_r == 0 is kept whole (k_r = cols) and sets word 0 of the workspace's 256-byte header:
+ * labsort_top_p_workspace_status (which synchronises `stream`) then returns LABSORT_ERR_ARG; the other
+ * rows' results are valid.  d_p == NULL: every row uses the host p, and a p that is a NaN or outside
+ * (0, 1] is LABSORT_ERR_ARG before any launch.  d_p != NULL: rows float32 words in device memory,
+ * never written, and the host p is ignored; a d_p[r] outside (0, 1] sets the same header word, with
+ * p <= 0 taken as P = 1 and a NaN or p > 1 as P = 2^32.
+ * Outputs: any of the three, at least one.  d_keys_out: rows x cols elements of the key type, the
+ * kept keys where they were and fill_bits elsewhere; d_keys_out == d_keys filters in place.
+ * d_mask_out: rows x cols bytes, 1 for kept.  d_kept_out: rows uint32 words, k_r.  Stores, overlaps,
+ * alignment, fill_bits and the NaN spelling of a kept key are labsort_topk_mask_device's.
+ * rows == 0 or cols == 0 launches nothing (LABSORT_OK before anything else is looked at).
+ * LABSORT_ERR_ARG before any launch: NULL d_keys, all three outputs NULL, a key type other than the
+ * three, a bad host p with d_p == NULL, cols > 2^23, rows > (2^31 - 1) / cols, an odd d_keys /
+ * d_keys_out address or high fill_bits with a 16-bit type, a d_kept_out or d_p that is not 4-byte
+ * aligned, any overlap (by the real element sizes) between the input, the three outputs and d_p
+ * other than d_keys_out == d_keys, a missing or short workspace.
+ * cols <= labsort_kth_row_keys(): one launch (after the header's clearing), one workgroup per row,
+ * the row in registers as u; every digit level sums the weights of the keys that match the digits
+ * chosen so far into a histogram of 64-bit masses in LDS and picks the digit d with
+ * mass(< d) < t <= mass(<= d), t less mass(< d) going to the next level.  The last prefix is the
+ * threshold T, w(T) > 0, and the first ceil(t / w(T)) of its ties in position order are kept, by
+ * the top-k filter's ordered scan and stores; the count is one block sum.
+ * Longer rows: per level one kernel over (row, chunk) sums each chunk's masses (a chunk without
+ * mass in the digit chosen before is skipped) and adds them to the row's, one 64-bit atomic per
+ * workgroup and digit, and one kernel per row picks.  The last pick divides each chunk's mass of the
+ * last digit by w(T), which is its count of T, finds the chunk that holds the last tie kept and
+ * writes the state that labsort_topk_mask_device's last two kernels read: they run as they do there,
+ * the streaming pass also counting what it keeps (one atomic per chunk) when d_kept_out is given.
+ * No kernel waits on another workgroup.
+ * Asynchronous on `stream`, no allocation, nothing read back; the launch sequence depends on the
+ * host arguments only (a captured call replays on new keys and a new d_p); the call clears what it
+ * relies on in the workspace.  labsort_top_p_workspace_bytes takes no key type and never shrinks as
+ * rows or cols grow: 256 bytes for cols <= labsort_kth_row_keys(); above, in this order and each
+ * region 256-byte aligned: the header, rows x 4 x 256 histogram masses (8 bytes each), rows x 5
+ * 16-byte states of the mass select, rows x 5 16-byte states of labsort_kth_device's layout, rows x
+ * chunks x 256 chunk masses (1/8 byte per key), and a position and a key word per row.
+ * Timing hooks: the kernels count under LABSORT_K_TOPK. */
+uint64_t labsort_top_p_weight(uint32_t word, int key_type);
+size_t labsort_top_p_workspace_bytes(size_t rows, size_t cols);
+int labsort_top_p_device(const void *d_keys, size_t rows, size_t cols, float p, const float *d_p, int key_type,
+                         uint32_t fill_bits, void *d_keys_out, uint8_t *d_mask_out, uint32_t *d_kept_out,
+                         void *d_workspace, size_t workspace_bytes, void *stream);
+int labsort_top_p_workspace_status(const void *d_workspace, void *stream);
+
 /* ---- unique: the distinct keys of an array with their counts, the position of each one's first
  * occurrence and every element's index into them (torch.unique(return_inverse, return_counts) on
  * index tensors, vocabulary and id compaction, edge deduplication on packed (src << 32) | dst keys,

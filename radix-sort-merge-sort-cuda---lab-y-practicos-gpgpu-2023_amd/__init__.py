@@ -68,6 +68,7 @@ C_SYMBOLS = [
     "labsort_key_order_bits64", "labsort_key_from_order_bits64",
     "labsort_kth_row_keys", "labsort_kth_workspace_bytes", "labsort_kth_device", "labsort_kth_workspace_status",
     "labsort_topk_mask_workspace_bytes", "labsort_topk_mask_device", "labsort_topk_mask_workspace_status",
+    "labsort_top_p_weight", "labsort_top_p_workspace_bytes", "labsort_top_p_device", "labsort_top_p_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
     "labsort_unique_chunk_keys", "labsort_unique_workspace_bytes", "labsort_unique_device",
     "labsort_unique_workspace_status",
@@ -246,6 +247,13 @@ def _load() -> ctypes.CDLL:
         L.labsort_topk_mask_workspace_bytes.argtypes = [sz, sz]
         L.labsort_topk_mask_device.argtypes = [p, sz, sz, sz, p, i, i, ctypes.c_uint32, p, p, p, sz, p]
         L.labsort_topk_mask_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_top_p_device"):  # (as labsort_radix_path above)
+        L.labsort_top_p_weight.restype = u64
+        L.labsort_top_p_weight.argtypes = [ctypes.c_uint32, i]
+        L.labsort_top_p_workspace_bytes.restype = sz
+        L.labsort_top_p_workspace_bytes.argtypes = [sz, sz]
+        L.labsort_top_p_device.argtypes = [p, sz, sz, ctypes.c_float, p, i, ctypes.c_uint32, p, p, p, p, sz, p]
+        L.labsort_top_p_workspace_status.argtypes = [p, p]
     if hasattr(L, "labsort_unique_device"):  # (as labsort_radix_path above)
         L.labsort_unique_chunk_keys.restype = sz
         L.labsort_unique_chunk_keys.argtypes = []
@@ -1093,6 +1101,96 @@ def topk_mask(x, k, largest: bool = True, workspace=None, stream=None):
     mask = torch.empty(x.shape, dtype=torch.bool, device=x.device)
     topk_mask_device(x, rows, cols, k, d_mask_out=mask, largest=largest, key=key, workspace=workspace, stream=stream)
     return mask
+
+
+def top_p_weight(word: int, key: str = "f32") -> int:
+    """The fixed-point weight of one key word in top_p_device: min(floor(x 2^40), 2^40), 0 for a set sign
+    bit and for a NaN (labsort_top_p_weight; 0 for a key type other than f32, bf16, f16)."""
+    return int(lib.labsort_top_p_weight(int(word) & 0xFFFFFFFF, KEY[key]))
+
+
+def top_p_workspace_bytes(rows: int, cols: int) -> int:
+    return int(lib.labsort_top_p_workspace_bytes(rows, cols))
+
+
+def top_p_device(d_keys, rows: int, cols: int, p, d_keys_out=None, d_mask_out=None, d_kept_out=None,
+                 fill_bits: int = 0, key: str = "f32", workspace=None, stream=None) -> None:
+    """Top-p filtering of every row of the dense rows x cols matrix d_keys of non-negative weights
+    (probabilities): the row keeps the smallest prefix of sort_rows_device(descending=True)'s order
+    whose weights, summed exactly in 2^-40 fixed point, reach p times the row's total (labsort.h has the
+    rule).  d_keys_out (rows x cols elements, or None; may be d_keys itself): the kept keys where they
+    were, `fill_bits` elsewhere.  d_mask_out (rows x cols bytes, or None): 1 where kept.  d_kept_out (rows
+    uint32 words, or None): how many elements each row keeps.  At least one of the three.  p is a float in
+    (0, 1], or a float32 CUDA tensor of `rows` elements, one p per row, which is passed as d_p: a value
+    outside (0, 1] is clamped on the device and reported by top_p_workspace_status as ERR_ARG, as is a row
+    whose weights are all zero (it is kept whole); the other rows stay valid.  key: f32, bf16 or f16.
+    Workspace and status follow topk_mask_device: with a caller-owned `workspace`
+    (>= top_p_workspace_bytes(rows, cols)) the call stays asynchronous; without one it allocates,
+    synchronises and checks."""
+    workspace, wsb, own = _workspace(workspace, lambda: top_p_workspace_bytes(rows, cols))
+    d_p = _ptr(p) if _is_k_tensor(p) else None
+    _check(lib.labsort_top_p_device(_ptr(d_keys), rows, cols, 1.0 if d_p is not None else float(p), d_p, KEY[key],
+                                    int(fill_bits) & 0xFFFFFFFF,
+                                    None if d_keys_out is None else _ptr(d_keys_out),
+                                    None if d_mask_out is None else _ptr(d_mask_out),
+                                    None if d_kept_out is None else _ptr(d_kept_out),
+                                    _ptr(workspace), wsb, _stream(stream)), "top_p_device")
+    if own:
+        top_p_workspace_status(workspace, stream)
+
+
+def top_p_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_ARG if in the last top_p_device call on
+    `workspace` a row's p lay outside (0, 1] (it was clamped) or a row's weights were all zero (the
+    row was kept whole)."""
+    _check(lib.labsort_top_p_workspace_status(_ptr(workspace), _stream(stream)), "top_p (status)")
+
+
+def _top_p_args(what: str, x, p):
+    """(rows, cols, key) for top_p_filter() and top_p_mask(), or their TypeErrors."""
+    import torch
+    if isinstance(x, torch.Tensor) and x.dtype == torch.int32:
+        raise TypeError(f"{what}: float32, bfloat16 or float16 tensor expected, got {x.dtype}")
+    rows, cols, key = _dense_rows(what, x)
+    if isinstance(p, torch.Tensor):
+        if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or p.dim() != 1 or p.shape[0] != rows:
+            raise TypeError(f"{what}: p must be a float or a contiguous float32 CUDA tensor of {rows} elements")
+    elif isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{what}: p must be a float or a float32 CUDA tensor, got {type(p)}")
+    return rows, cols, key
+
+
+def top_p_filter(x, p, fill=0.0, out=None, return_kept: bool = False, workspace=None, stream=None):
+    """x with everything outside each row's top-p set replaced by `fill`: top_p_device with the keys
+    output (what a sampler does to its probabilities after the softmax).  x: a contiguous 1-D (one row)
+    or 2-D CUDA tensor of float32, bfloat16 or float16; p: a float in (0, 1], or a contiguous float32 CUDA
+    tensor of `rows` elements (one p per row).  out: None (allocated), x itself (in place) or another
+    contiguous tensor of x's shape and dtype; it is returned.  return_kept: also return the int32 tensor
+    of `rows` elements that holds how many elements each row keeps.  TypeError before the device is
+    touched for anything else.  The sums are exact integers, so the result does not depend on their
+    order and repeats bit for bit.  Workspace and status as top_p_device."""
+    import torch
+    rows, cols, key = _top_p_args("top_p_filter", x, p)
+    if out is None:
+        out = torch.empty_like(x)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous()
+          or out.device != x.device):
+        raise TypeError("top_p_filter: out must be None, x itself or a contiguous tensor of x's shape, dtype and device")
+    kept = torch.empty((rows,), dtype=torch.int32, device=x.device) if return_kept else None
+    top_p_device(x, rows, cols, p, d_keys_out=out, d_kept_out=kept, fill_bits=_fill_bits(x.dtype, fill), key=key,
+                 workspace=workspace, stream=stream)
+    return (out, kept) if return_kept else out
+
+
+def top_p_mask(x, p, return_kept: bool = False, workspace=None, stream=None):
+    """The torch.bool tensor of x's shape that is True at each row's top-p set (top_p_filter's rule),
+    with return_kept also the int32 count per row.  Arguments as top_p_filter."""
+    import torch
+    rows, cols, key = _top_p_args("top_p_mask", x, p)
+    mask = torch.empty(x.shape, dtype=torch.bool, device=x.device)
+    kept = torch.empty((rows,), dtype=torch.int32, device=x.device) if return_kept else None
+    top_p_device(x, rows, cols, p, d_mask_out=mask, d_kept_out=kept, key=key, workspace=workspace, stream=stream)
+    return (mask, kept) if return_kept else mask
 
 
 def unique_chunk_keys() -> int:

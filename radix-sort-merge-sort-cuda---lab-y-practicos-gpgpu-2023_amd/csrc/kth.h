@@ -24,5 +24,16 @@ constexpr int KTH_HDR_BYTES = TK_HDR_BYTES;  // word 0: a d_k[r] outside [1, col
 #ifndef LABSORT_TKM_SKIP_SCAN
 #define LABSORT_TKM_SKIP_SCAN 1
 #endif
+// Top-p filtering (labsort_top_p_device): the select's histograms hold masses, 64-bit words of
+// 2^-40 fixed point, so a slot costs twice the LDS of a counter: half the replicas of the count
+// kernels at 1024 threads (32 KB, the size of their histogram), the same eight at 256 (16 KB;
+// 16 were 17-30 % slower on rows of 1024 and 4096 keys).
+constexpr int TP_FRAC_BITS = 40;       // a weight is floor(x 2^40), at most 2^40
+constexpr size_t TP_MAX_COLS = 1u << 23;  // so that a row's total stays below 2^63
+constexpr int TP_SLOTS = TK_SLOTS / 2;
+#ifndef LABSORT_TP_SMALL_SLOTS
+#define LABSORT_TP_SMALL_SLOTS 8  // (A/B build knob)
+#endif
+constexpr int TP_SMALL_SLOTS = LABSORT_TP_SMALL_SLOTS;
 
 }  // namespace labsort

@@ -36,6 +36,16 @@
 //   k_tkm_apply  longer rows, after the launches above with positions: one workgroup per (row,
 //                chunk) tests every key against the row's k-th pair and stores.
 // Both instantiations compile to the text the two separate kernels had.
+//
+// Top-p filtering (labsort_top_p_device) is the same select on masses: every key weighs
+// min(floor(x 2^40), 2^40), the level histograms hold 64-bit sums of weights, and the digit picked is
+// the one at which the running mass reaches the row's target.
+//   k_tp_short   rows of up to KTH_ROW_KEYS keys, one launch: the mass select with the row in
+//                registers, then the filter's ordered scan of the threshold's ties and its stores.
+//   k_tp_hist / k_tp_pick  longer rows, per level, in the shape of k_kth_hist / k_kth_pick; the last
+//                pick writes the KthState that k_kth_locate and k_tkm_apply read, and those two run
+//                as they do for the top-k filter (k_tkm_apply<.., COUNT = true> also counts what it
+//                keeps, for the call's kept-count output).
 #include "kth.h"
 
 #include <type_traits>
@@ -479,11 +489,19 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_kth_locate(KthArgs a) {
 }
 
 // The filter's longer rows, after the select with positions: one workgroup per (row, chunk) streams
-// its chunk through the test against the row's k-th pair (uT, P).
-template <int KT>
-__global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m) {
+// its chunk through the test against the row's k-th pair (uT, P).  COUNT (top-p filtering, where
+// the number kept is a result): the elements kept are counted and added to kept[row], which is
+// zero before the launch, once per workgroup; either output of m may then be absent.
+template <int KT, bool COUNT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m, uint32_t *kept) {
     constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
+    __shared__ uint32_t nkept;
     const uint32_t tid = threadIdx.x;
+    uint32_t mine = 0u;
+    if constexpr (COUNT) {
+        if (tid == 0u) nkept = 0u;
+        __syncthreads();
+    }
     const uint32_t row = blockIdx.x / a.nch, c = blockIdx.x - row * a.nch;
     const uint32_t uT = a.st[(size_t)row * (TK_LEVELS + 1) + kth_levels(KT)].prefix, P = m.pos[row];
     const kth_elem_t<KT> *base = kth_row<KT>(a, row);
@@ -510,8 +528,396 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_tkm_apply(KthArgs a, TkmArgs m) {
                 w[j] = keep ? kth_unord<KT>(u[t][j], a.xr) : m.fill;
             }
             tkm_store<KT>(m, rowoff, i0[t], vm[t], w, km);
+            if constexpr (COUNT) mine += (uint32_t)__popc(km);
         }
     }
+    if constexpr (COUNT) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+        if ((tid & 63u) == 0u && mine) atomicAdd(&nkept, mine);
+        __syncthreads();
+        if (tid == 0u && nkept) atomicAdd(&kept[row], nkept);
+    }
+}
+
+// ---- top-p filtering (labsort_top_p_device): the select above with masses for counts.  An
+// element weighs w = min(floor(x 2^40), 2^40), zero for a set sign bit and for a NaN; a row's
+// target is t = max(1, ceil(P W / 2^32)) with W its total and P = clamp(floor(p 2^32), 1, 2^32).
+// Every level sums the weights of the keys that match the prefix by digit and picks the digit at
+// which the running mass reaches what is left of t.  The last prefix is the threshold T, w(T) > 0,
+// and the first ceil(trem / w(T)) of its ties are kept.  Integer sums: any order gives the same. ----
+typedef unsigned long long tp_mass_t;  // (the type atomicAdd takes)
+
+// The weight of a float32 word, of a bfloat16 word and of a float16 word (the float32 rule on the
+// value widened exactly: sig 2^(E - 25) 2^40 with E <= 14 below 1.0), from the bits alone
+__host__ __device__ inline uint64_t tp_weight_f32(uint32_t x) {
+    if (x > 0x7F800000u) return 0u;  // the sign bit, or a NaN
+    if (x >= 0x3F800000u) return 1ull << TP_FRAC_BITS;
+    const uint32_t e = x >> 23, m = x & 0x7FFFFFu;
+    const uint64_t sig = e ? (m | 0x800000u) : m;
+    const int sh = (int)(e ? e : 1u) - (150 - TP_FRAC_BITS);  // x 2^40 = sig 2^sh, sh <= 16
+    if (sh >= 0) return sig << sh;
+    return sh > -24 ? sig >> -sh : 0u;
+}
+__host__ __device__ inline uint64_t tp_weight_f16(uint32_t x) {
+    x &= 0xFFFFu;
+    if (x > 0x7C00u) return 0u;
+    if (x >= 0x3C00u) return 1ull << TP_FRAC_BITS;
+    const uint32_t e = x >> 10, m = x & 0x3FFu;
+    const uint64_t sig = e ? (m | 0x400u) : m;
+    return sig << ((e ? e : 1u) + (uint32_t)(TP_FRAC_BITS - 25));
+}
+template <int KT>
+__device__ __forceinline__ uint64_t tp_w(uint32_t u, uint32_t xr) {
+    const uint32_t x = kth_unord<KT>(u, xr);
+    if constexpr (KT == KTH_F16) return tp_weight_f16(x);
+    else if constexpr (KT == KTH_BF16) return tp_weight_f32(x << 16);
+    else return tp_weight_f32(x);
+}
+
+// Per row and level, as KthState.  trem == 0: the row's total is zero and the row is kept whole.
+struct TpState {
+    uint64_t trem;  // what is left of the target among the keys that match the prefix (>= 1)
+    uint32_t prefix, d;
+};
+struct TpArgs {
+    const float *d_p;     // [rows], or nullptr: p
+    tp_mass_t *hist;      // long rows: [rows][TK_LEVELS][256]
+    tp_mass_t *cmass;     // long rows: [rows][nch][256]: each chunk's masses of the current level
+    TpState *st;          // long rows: [rows][TK_LEVELS + 1]
+    uint32_t *kept_out;   // [rows], or nullptr
+    float p;
+};
+
+// P of the row's p, from its bits; a p outside (0, 1] is reported in the header by the thread told to
+__device__ __forceinline__ uint64_t tp_fixed_p(const TpArgs &tp, uint32_t row, bool report, uint32_t *hdr) {
+    const uint32_t b = __float_as_uint(tp.d_p ? tp.d_p[row] : tp.p);
+    uint64_t P;
+    bool bad = true;
+    if ((b & 0x7FFFFFFFu) > 0x7F800000u) P = 1ull << 32;             // NaN
+    else if ((b >> 31) || b == 0u) P = 1u;                           // p <= 0
+    else if (b > 0x3F800000u) P = 1ull << 32;                        // p > 1
+    else {
+        bad = false;
+        const uint32_t e = b >> 23, m = b & 0x7FFFFFu;
+        const uint64_t sig = e ? (m | 0x800000u) : m;
+        const int sh = (int)(e ? e : 1u) - 118;  // p 2^32 = sig 2^sh, sh <= 9
+        P = sh >= 0 ? sig << sh : sh > -24 ? sig >> -sh : 0u;
+        if (P == 0u) P = 1u;
+    }
+    if (bad && report) hdr[0] = 1u;
+    return P;
+}
+// t of P and W >= 1: the 96-bit product by its two halves
+__device__ __forceinline__ uint64_t tp_target(uint64_t P, uint64_t W) {
+    const uint64_t hi = __umul64hi(P, W), lo = P * W;
+    const uint64_t t = (hi << 32) + (lo >> 32) + ((lo & 0xFFFFFFFFull) ? 1u : 0u);
+    return t ? t : 1u;
+}
+
+// kth_pick on masses, in two steps, since level 0 needs the total before it has a target.  Called by
+// a whole wave on a level histogram of 256 masses (global or LDS); the results are wave-uniform.
+struct TpScan {
+    uint64_t c[4], run, total;  // digits 4 lane .. 4 lane + 3, the mass below them, the row's
+};
+__device__ __forceinline__ uint64_t tp_shfl(uint64_t v, int src) { return (uint64_t)__shfl((tp_mass_t)v, src); }
+__device__ __forceinline__ TpScan tp_scan(const tp_mass_t *hrow, uint32_t lane) {
+    TpScan s;
+    uint64_t x = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s.c[j] = hrow[4u * lane + (uint32_t)j];
+        x += s.c[j];
+    }
+    const uint64_t own = x;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t t = (uint64_t)__shfl_up((tp_mass_t)x, off);
+        if (lane >= (uint32_t)off) x += t;
+    }
+    s.run = x - own;
+    s.total = tp_shfl(x, 63);
+    return s;
+}
+// The d with mass(< d) < trem <= mass(<= d), 1 <= trem <= total
+struct TpPick {
+    uint32_t d;
+    uint64_t below, in;  // the mass below digit d and of digit d
+};
+__device__ __forceinline__ TpPick tp_find(const TpScan &s, uint64_t trem, uint32_t lane) {
+    uint64_t run = s.run, below = 0u, in = 0u;
+    uint32_t d = 255u;
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (!found && run < trem && trem <= run + s.c[j]) {
+            found = true;
+            d = 4u * lane + (uint32_t)j;
+            below = run;
+            in = s.c[j];
+        }
+        run += s.c[j];
+    }
+    const uint64_t m = __ballot(found);
+    const int srcl = m ? __ffsll((long long)m) - 1 : 63;  // (no lane: trem exceeds the total, which cannot happen)
+    TpPick p;
+    p.d = __shfl(d, srcl);
+    p.below = tp_shfl(below, srcl);
+    p.in = tp_shfl(in, srcl);
+    if (p.below >= trem) p.below = trem - 1u;  // keeps trem >= 1 whatever the histogram held
+    return p;
+}
+// How many of the threshold's ties the rest of the target takes: ceil(trem / w), w = w(T) > 0
+__device__ __forceinline__ uint32_t tp_ties_kept(uint64_t trem, uint64_t w) {
+    if (w == 0u) w = 1u;  // (cannot happen: the digit picked held mass)
+    return (uint32_t)((trem + w - 1u) / w);
+}
+
+// Rows of up to BLOCK * KTH_KPT keys: k_kth_short<.., FILTER = true> with the mass select in place
+// of the count select, SLOTS replicas of 64-bit words per digit, and the number kept as one block
+// sum.  A row without mass is stored as it is and reported in the header.
+template <int KT, int BLOCK, int SLOTS>
+__global__ __launch_bounds__(BLOCK) void k_tp_short(KthArgs a, TkmArgs m, TpArgs tp) {
+    constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
+    constexpr int TG = T + 1;  // a row that starts inside a group has one group more
+    constexpr int NLEV = kth_levels(KT);
+    __shared__ tp_mass_t h[256 * SLOTS];
+    __shared__ __attribute__((aligned(16))) tp_mass_t hrow[256];
+    __shared__ uint32_t wsum[BLOCK / WAVE], tot, nkept;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t mis = group_mis(base, 0u), nq = group_count<E>(0u, a.cols, mis);  // <= T * BLOCK + 1
+    uint32_t u[TG][E], vm[TG];
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        const uint32_t q = (uint32_t)t * BLOCK + tid;
+        int64_t i0;
+        vm[t] = 0u;
+        if (q < nq) vm[t] = kth_load<KT>(base, 0u, a.cols, mis, q, a.xr, u[t], i0);
+        else
+#pragma unroll
+            for (int j = 0; j < E; ++j) u[t][j] = 0u;
+    }
+    if (tid == 0u) nkept = 0u;  // (the levels' barriers lie between this and the adds)
+    const uint64_t P = tp_fixed_p(tp, row, tid == 0u, a.hdr);
+    uint32_t prefix = 0u;
+    uint64_t trem = 0u, in = 0u;
+    bool whole = false;
+    for (int level = 0; level < NLEV; ++level) {
+        const uint32_t shift = 24u - 8u * (uint32_t)level;
+        const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+        for (uint32_t i = tid; i < 256u * SLOTS; i += BLOCK) h[i] = 0u;
+        __syncthreads();
+        // The weights do not depend on the level: left to itself the compiler computes all of them once
+        // and keeps two registers per key (139-172 VGPRs at 256 threads; 128 and 128-224 bytes of scratch
+        // per lane at 1024).  An xr that is opaque per level makes every level compute its own.
+        uint32_t xr = a.xr;
+        asm volatile("" : "+s"(xr));
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u) {
+                    const uint64_t w = tp_w<KT>(u[t][j], xr);
+                    if (w) atomicAdd(&h[((u[t][j] >> shift) & 255u) * SLOTS + (tid & (SLOTS - 1u))], (tp_mass_t)w);
+                }
+        __syncthreads();
+        if (tid < 256u) {
+            tp_mass_t sum = 0u;
+#pragma unroll
+            for (uint32_t q = 0; q < (uint32_t)SLOTS; ++q) sum += h[tid * SLOTS + ((q + tid) & (SLOTS - 1u))];
+            hrow[tid] = sum;
+        }
+        __syncthreads();
+        const TpScan sc = tp_scan(hrow, lane);  // (every wave: the same answer)
+        if (level == 0) {
+            whole = sc.total == 0u;
+            if (whole) break;  // (uniform)
+            trem = tp_target(P, sc.total);
+        }
+        const TpPick p = tp_find(sc, trem, lane);
+        prefix |= p.d << shift;
+        trem -= p.below;
+        in = p.in;
+    }
+    // km[t]: the elements of group (t, tid) that are kept: the keys below the threshold and the first
+    // krem of its ties in position order.  All of the ties (uniform): no scan.
+    uint32_t km[TG];
+    if (whole) {
+        if (tid == 0u) a.hdr[0] = 1u;
+#pragma unroll
+        for (int t = 0; t < TG; ++t) km[t] = vm[t];
+    } else {
+        const uint64_t wT = tp_w<KT>(prefix, a.xr);
+        const uint32_t krem = tp_ties_kept(trem, wT);
+        const bool all_ties = LABSORT_TKM_SKIP_SCAN && trem + wT > in;  // in = ties x wT
+        uint32_t carry = 0u;
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+            uint32_t lt = 0u, em = 0u;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const bool v = (vm[t] >> j) & 1u;
+                lt |= (v && u[t][j] < prefix ? 1u : 0u) << j;
+                em |= (v && u[t][j] == prefix ? 1u : 0u) << j;
+            }
+            km[t] = lt;
+            if (all_ties) km[t] |= em;
+            else if (carry < krem) {  // (uniform; past it no tie is kept)
+                const uint32_t c = (uint32_t)__popc(em);
+                const uint32_t before = kth_ordered_step<BLOCK>(c, carry, wsum, &tot);
+                const uint32_t room = before < krem ? krem - before : 0u;
+                uint32_t seen = 0u;
+#pragma unroll
+                for (int j = 0; j < E; ++j)
+                    if ((em >> j) & 1u) {
+                        if (seen < room) km[t] |= 1u << j;
+                        ++seen;
+                    }
+            }
+        }
+    }
+    if (tp.kept_out) {  // (uniform)
+        uint32_t mine = 0u;
+#pragma unroll
+        for (int t = 0; t < TG; ++t) mine += (uint32_t)__popc(km[t]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+        if (lane == 0u && mine) atomicAdd(&nkept, mine);
+        __syncthreads();
+        if (tid == 0u) tp.kept_out[row] = nkept;
+    }
+    if (!m.keys_out && !m.mask_out) return;
+    const size_t rowoff = (size_t)row * a.cols;
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        const uint32_t q = (uint32_t)t * BLOCK + tid;
+        if (q >= nq) continue;
+        uint32_t w[E];
+#pragma unroll
+        for (int j = 0; j < E; ++j) w[j] = (km[t] >> j) & 1u ? kth_unord<KT>(u[t][j], a.xr) : m.fill;
+        tkm_store<KT>(m, rowoff, (int64_t)E * q - (int64_t)mis, vm[t], w, km[t]);
+    }
+}
+
+// Longer rows, per level: one workgroup per (row, chunk) sums the level's digit masses of the keys
+// that match the prefix, per chunk (cmass, plain stores) and per row (hist, one atomic add per
+// digit that holds mass).  From level 1 on a chunk is read only if it held mass of the digit chosen
+// before; a skipped chunk's row of cmass is zeroed, as k_kth_hist zeroes its counts.
+template <int KT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_tp_hist(KthArgs a, TpArgs tp, int level) {
+    constexpr int E = KTH_E<KT>, T = KTH_KPT / E;
+    __shared__ tp_mass_t h[256 * TP_SLOTS];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = blockIdx.x / a.nch, c = blockIdx.x - row * a.nch;
+    TpState st{0u, 0u, 0u};
+    if (level) st = tp.st[(size_t)row * (TK_LEVELS + 1) + level];
+    tp_mass_t *crow = tp.cmass + ((size_t)row * a.nch + c) * 256u;
+    // every thread reads the same word, which only this workgroup writes, and only zero over zero
+    // before the barriers below
+    if (level && __builtin_amdgcn_readfirstlane((uint32_t)(st.trem != 0u && crow[st.d] != 0u)) == 0u) {
+        if (tid < 256u) crow[tid] = 0u;  // (no stale masses of the level before)
+        return;
+    }
+    const uint32_t shift = 24u - 8u * (uint32_t)level;
+    const uint32_t mask = level ? 0xFFFFFFFFu << (shift + 8u) : 0u;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t xr = a.xr, prefix = st.prefix;
+    for (uint32_t i = tid; i < 256u * TP_SLOTS; i += KTH_BLOCK) h[i] = 0u;
+    __syncthreads();
+    const KthChunk ch = kth_chunk<KT>(base, a.cols, c);
+    for (uint32_t q0 = 0; q0 < ch.nq; q0 += (uint32_t)T * KTH_BLOCK) {
+        uint32_t u[T][E], vm[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint32_t q = q0 + (uint32_t)t * KTH_BLOCK + tid;
+            int64_t i0;
+            vm[t] = 0u;
+            if (q < ch.nq) vm[t] = kth_load<KT>(base, ch.beg, ch.end, ch.mis, q, xr, u[t], i0);
+            else
+#pragma unroll
+                for (int j = 0; j < E; ++j) u[t][j] = 0u;
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if (((vm[t] >> j) & 1u) && ((u[t][j] ^ prefix) & mask) == 0u) {
+                    const uint64_t w = tp_w<KT>(u[t][j], xr);
+                    if (w) atomicAdd(&h[((u[t][j] >> shift) & 255u) * TP_SLOTS + (tid & (TP_SLOTS - 1u))], (tp_mass_t)w);
+                }
+    }
+    __syncthreads();
+    if (tid < 256u) {
+        tp_mass_t sum = 0u;
+#pragma unroll 8
+        for (uint32_t q = 0; q < (uint32_t)TP_SLOTS; ++q) sum += h[tid * TP_SLOTS + ((q + tid) & (TP_SLOTS - 1u))];
+        crow[tid] = sum;
+        if (sum) atomicAdd(&tp.hist[((size_t)row * TK_LEVELS + level) * 256u + tid], sum);
+    }
+}
+
+// One workgroup per row: the digit at which the running mass reaches what is left of the target,
+// and the next level's state.  Level 0 reads the row's p and clears its kept count.  After the
+// last level it divides each chunk's mass of the last digit by w(T), which is the chunk's count of
+// T, finds the chunk that holds the last tie kept and writes the KthState that k_kth_locate and
+// k_tkm_apply read.  A row without mass gets the pair that keeps everything.
+template <int KT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_tp_pick(KthArgs a, TpArgs tp, int level) {
+    constexpr int NLEV = kth_levels(KT);
+    __shared__ uint32_t wsum[KTH_BLOCK / WAVE], tot, hit[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, row = blockIdx.x;
+    TpState st{0u, 0u, 0u};
+    if (level) st = tp.st[(size_t)row * (TK_LEVELS + 1) + level];
+    const TpScan sc = tp_scan(tp.hist + ((size_t)row * TK_LEVELS + level) * 256u, lane);
+    if (level == 0) {
+        if (tid == 0u && tp.kept_out) tp.kept_out[row] = 0u;
+        const uint64_t P = tp_fixed_p(tp, row, tid == 0u, a.hdr);
+        if (sc.total) st.trem = tp_target(P, sc.total);
+        else if (tid == 0u) a.hdr[0] = 1u;
+    }
+    const bool last = level == NLEV - 1;
+    TpState *out = tp.st + (size_t)row * (TK_LEVELS + 1) + level + 1;
+    KthState *kout = a.st + (size_t)row * (TK_LEVELS + 1) + NLEV;
+    if (st.trem == 0u) {  // (uniform) krem == 0: k_kth_locate leaves the position alone
+        if (tid == 0u) {
+            if (!last) *out = TpState{0u, 0u, 0u};
+            else {
+                *kout = KthState{0xFFFFFFFFu, 0u, 0u, 0u};
+                a.idx_out[row] = a.cols - 1u;
+            }
+        }
+        return;
+    }
+    const TpPick p = tp_find(sc, st.trem, lane);
+    TpState ns;
+    ns.prefix = st.prefix | (p.d << (24u - 8u * (uint32_t)level));
+    ns.trem = st.trem - p.below;
+    ns.d = p.d;
+    if (!last) {
+        if (tid == 0u) *out = ns;
+        return;
+    }
+    uint64_t wT = tp_w<KT>(ns.prefix, a.xr);
+    if (wT == 0u) wT = 1u;  // (cannot happen: the digit picked held mass)
+    const uint32_t krem = tp_ties_kept(ns.trem, wT);
+    if (tid == 0u) {
+        hit[0] = 0u;
+        hit[1] = 1u;
+    }
+    __syncthreads();
+    uint32_t carry = 0u;
+    for (uint32_t b = 0; b < a.nch && carry < krem; b += KTH_BLOCK) {  // (uniform)
+        const uint32_t c = b + tid;
+        const uint32_t v = c < a.nch ? (uint32_t)(tp.cmass[((size_t)row * a.nch + c) * 256u + p.d] / wT) : 0u;
+        const uint32_t before = kth_ordered_step(v, carry, wsum, &tot);
+        if (v && before < krem && krem <= before + v) {
+            hit[0] = c;
+            hit[1] = krem - before;
+        }
+    }
+    __syncthreads();
+    if (tid == 0u) *kout = KthState{ns.prefix, hit[1], p.d, hit[0]};
 }
 
 // ---- launches.  kt: KthKey, the instantiation that runs: f gets it as a constant ----
@@ -554,9 +960,14 @@ hipError_t launch_kth_locate(const KthArgs &a, size_t rows, int kt, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_tkm_apply(const KthArgs &a, const TkmArgs &m, size_t rows, int kt, hipStream_t s) {
+// kept: nullptr, or (top-p filtering) one zeroed word per row that receives the number of elements kept
+hipError_t launch_tkm_apply(const KthArgs &a, const TkmArgs &m, uint32_t *kept, size_t rows, int kt, hipStream_t s) {
     const unsigned grid = (unsigned)(rows * a.nch);
-    kth_dispatch(kt, [&](auto K) { k_tkm_apply<decltype(K)::value><<<grid, KTH_BLOCK, 0, s>>>(a, m); });
+    kth_dispatch(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        if (kept) k_tkm_apply<KT, true><<<grid, KTH_BLOCK, 0, s>>>(a, m, kept);
+        else k_tkm_apply<KT, false><<<grid, KTH_BLOCK, 0, s>>>(a, m, nullptr);
+    });
     return hipGetLastError();
 }
 
@@ -645,6 +1056,64 @@ KthCall kth_call(const void *d_keys, size_t cols, size_t k, const uint32_t *d_k,
     return c;
 }
 
+// ---- top-p filtering: launches and workspace.  Only the float key types reach these ----
+template <class F>
+void tp_dispatch(int kt, F f) {
+    if (kt == KTH_BF16) f(std::integral_constant<int, KTH_BF16>{});
+    else if (kt == KTH_F16) f(std::integral_constant<int, KTH_F16>{});
+    else f(std::integral_constant<int, KTH_F32>{});
+}
+
+hipError_t launch_tp_short(const KthArgs &a, const TkmArgs &m, const TpArgs &tp, size_t rows, int kt, hipStream_t s) {
+    const unsigned grid = (unsigned)rows;
+    tp_dispatch(kt, [&](auto K) {
+        constexpr int KT = decltype(K)::value;
+        if (a.cols <= (uint32_t)KTH_SMALL_ROW_KEYS)
+            k_tp_short<KT, KTH_SMALL_BLOCK, TP_SMALL_SLOTS><<<grid, KTH_SMALL_BLOCK, 0, s>>>(a, m, tp);
+        else k_tp_short<KT, KTH_BLOCK, TP_SLOTS><<<grid, KTH_BLOCK, 0, s>>>(a, m, tp);
+    });
+    return hipGetLastError();
+}
+
+// Longer rows: a mass histogram and a pick per level, the position of the last pair kept, the
+// streaming pass (which counts what it keeps where the call asks for the count)
+int run_tp_long(const KthArgs &a, const TkmArgs &m, const TpArgs &tp, size_t rows, int kt, hipStream_t s) {
+    const unsigned grid = (unsigned)(rows * a.nch);
+    for (int level = 0; level < kth_levels(kt); ++level) {
+        tp_dispatch(kt, [&](auto K) { k_tp_hist<decltype(K)::value><<<grid, KTH_BLOCK, 0, s>>>(a, tp, level); });
+        HIP_TRY(hipGetLastError());
+        tp_dispatch(kt, [&](auto K) { k_tp_pick<decltype(K)::value><<<(unsigned)rows, KTH_BLOCK, 0, s>>>(a, tp, level); });
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(launch_kth_locate(a, rows, kt, s));
+    HIP_TRY(launch_tkm_apply(a, m, tp.kept_out, rows, kt, s));
+    return LABSORT_OK;
+}
+
+// header | mass histograms | the mass select's states | the final KthState slots | per-chunk masses |
+// the position and the key of each row's last pair kept.  Header and histograms are the only words
+// a call relies on being clear.  A short row needs the header alone.
+struct TpLayout {
+    size_t nch, off_hist, zero_bytes, off_tst, off_st, off_cmass, off_pos, off_key, total;
+};
+TpLayout tp_layout(size_t rows, size_t cols) {
+    TpLayout L{};
+    Carver c;
+    c.take(KTH_HDR_BYTES);
+    L.zero_bytes = L.total = c.o;
+    if (rows == 0 || cols <= (size_t)KTH_ROW_KEYS) return L;
+    L.nch = (cols + TK_CHUNK - 1) / TK_CHUNK;
+    L.off_hist = c.take(rows * TK_LEVELS * 256 * sizeof(tp_mass_t));
+    L.zero_bytes = c.o;
+    L.off_tst = c.take(rows * (TK_LEVELS + 1) * sizeof(TpState));
+    L.off_st = c.take(rows * (TK_LEVELS + 1) * sizeof(KthState));
+    L.off_cmass = c.take(rows * L.nch * 256 * sizeof(tp_mass_t));
+    L.off_pos = c.take(rows * sizeof(uint32_t));
+    L.off_key = c.take(rows * sizeof(uint32_t));
+    L.total = c.o;
+    return L;
+}
+
 }  // namespace
 
 }  // namespace labsort
@@ -728,10 +1197,74 @@ int labsort_topk_mask_device(const void *d_keys, size_t rows, size_t cols, size_
     c.a.idx_out = reinterpret_cast<uint32_t *>(ws + L.off_pos);
     m.pos = c.a.idx_out;
     if (const int st = run_kth_long(c.a, rows, c.kt, s)) return st;
-    HIP_TRY(launch_tkm_apply(c.a, m, rows, c.kt, s));
+    HIP_TRY(launch_tkm_apply(c.a, m, nullptr, rows, c.kt, s));
     return LABSORT_OK;
 }
 
 int labsort_topk_mask_workspace_status(const void *d_ws, void *stream) { return labsort_kth_workspace_status(d_ws, stream); }
+
+uint64_t labsort_top_p_weight(uint32_t word, int key_type) {
+    if (key_type == LABSORT_KEY_F32) return tp_weight_f32(word);
+    if (key_type == LABSORT_KEY_BF16) return tp_weight_f32((word & 0xFFFFu) << 16);
+    if (key_type == LABSORT_KEY_F16) return tp_weight_f16(word);
+    return 0;
+}
+
+size_t labsort_top_p_workspace_bytes(size_t rows, size_t cols) { return tp_layout(rows, cols).total; }
+
+int labsort_top_p_device(const void *d_keys, size_t rows, size_t cols, float p, const float *d_p, int key_type,
+                         uint32_t fill_bits, void *d_keys_out, uint8_t *d_mask_out, uint32_t *d_kept_out, void *d_ws,
+                         size_t ws_bytes, void *stream) {
+    if (rows == 0 || cols == 0) return LABSORT_OK;
+    if (!d_keys || (!d_keys_out && !d_mask_out && !d_kept_out)) return LABSORT_ERR_ARG;
+    if (key_type != LABSORT_KEY_F32 && !key_type_is16(key_type)) return LABSORT_ERR_ARG;
+    if (!d_p && !(p > 0.0f && p <= 1.0f)) return LABSORT_ERR_ARG;  // (a NaN fails both)
+    if (cols > TP_MAX_COLS || rows > (size_t)0x7FFFFFFFu / cols) return LABSORT_ERR_ARG;
+    const bool k16 = key_type_is16(key_type);
+    const size_t esz = k16 ? 2 : 4;  // bytes per key
+    if (k16 && ((((uintptr_t)d_keys | (uintptr_t)d_keys_out) & 1u) || (fill_bits >> 16))) return LABSORT_ERR_ARG;
+    if (((uintptr_t)d_kept_out | (uintptr_t)d_p) & 3u) return LABSORT_ERR_ARG;
+    // the one alias: the keys written over the input, element for element
+    const size_t key_bytes = rows * cols * esz, mask_bytes = rows * cols, w_bytes = rows * 4;
+    const struct {
+        const void *at;
+        size_t bytes;
+    } r[5] = {{d_keys, key_bytes}, {d_keys_out, key_bytes}, {d_mask_out, mask_bytes}, {d_kept_out, w_bytes}, {d_p, w_bytes}};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j) {
+            if (!r[i].at || !r[j].at || (i == 0 && j == 1 && d_keys_out == d_keys)) continue;
+            if (ranges_overlap(r[i].at, r[i].bytes, r[j].at, r[j].bytes)) return LABSORT_ERR_ARG;
+        }
+    const TpLayout L = tp_layout(rows, cols);
+    if (!d_ws || ws_bytes < L.total) return LABSORT_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    KthCall c = kth_call(d_keys, cols, 1, nullptr, 1, key_type, d_ws, KthLayout{});
+    TkmArgs m{};
+    m.keys_out = d_keys_out;
+    m.mask_out = d_mask_out;
+    m.fill = fill_bits;
+    TpArgs tp{};
+    tp.d_p = d_p;
+    tp.p = p;
+    tp.kept_out = d_kept_out;
+    HIP_TRY(launch_zero(ws, L.zero_bytes, s));
+    TimingScope ts(LABSORT_K_TOPK, s);
+    if (cols <= (size_t)KTH_ROW_KEYS) {
+        HIP_TRY(launch_tp_short(c.a, m, tp, rows, c.kt, s));
+        return LABSORT_OK;
+    }
+    c.a.nch = (uint32_t)L.nch;
+    c.a.st = reinterpret_cast<KthState *>(ws + L.off_st);
+    c.a.keys_out = ws + L.off_key;
+    c.a.idx_out = reinterpret_cast<uint32_t *>(ws + L.off_pos);
+    m.pos = c.a.idx_out;
+    tp.hist = reinterpret_cast<tp_mass_t *>(ws + L.off_hist);
+    tp.st = reinterpret_cast<TpState *>(ws + L.off_tst);
+    tp.cmass = reinterpret_cast<tp_mass_t *>(ws + L.off_cmass);
+    return run_tp_long(c.a, m, tp, rows, c.kt, s);
+}
+
+int labsort_top_p_workspace_status(const void *d_ws, void *stream) { return labsort_kth_workspace_status(d_ws, stream); }
 
 }  // extern "C"

@@ -725,6 +725,55 @@ int labsort_top_p_device(const void *d_keys, size_t rows, size_t cols, float p, 
                          void *d_workspace, size_t workspace_bytes, void *stream);
 int labsort_top_p_workspace_status(const void *d_workspace, void *stream);
 
+/* ---- categorical sampling per row: positions drawn by exact inverse CDF from caller-supplied random
+ * words (the step of a sampler after the filters above: labsort_top_p_device with fill 0 in place,
+ * then this call, is a sampler's whole tail; no renormalisation, the call sums the row itself; no
+ * lab.cu counterpart) ----
+ * d_keys is a dense rows x cols matrix of non-negative weights, never written; key_type: F32, BF16 or
+ * F16; addressing, 2-byte alignment of the 16-bit types and cols <= 2^23 as labsort_top_p_device.
+ * Weight.  labsort_top_p_weight exactly: w = min(floor(x 2^40), 2^40), 0 for a set sign bit and for a
+ * NaN, so a row filtered with fill 0 or a negative fill needs nothing more.  W_r is the row's sum,
+ * below 2^63.
+ * Random words.  d_u holds rows x ndraw uint32 words in device memory, row-major, never written.  The
+ * caller supplies them: the library has no generator.  U is the word itself, uniform in [0, 2^32).
+ * Target.  s = floor(U W_r / 2^32), the product (at most 95 bits) from its two 64-bit halves, so
+ * 0 <= s < W_r.
+ * Draw.  d_idx_out[r * ndraw + d] is the smallest position j whose inclusive prefix w_0 + .. + w_j, in
+ * position order, exceeds s.  An element of weight 0 is never drawn.  An element of weight w is drawn
+ * for floor or ceil of w 2^32 / W_r values of U.  Every sum is an exact integer, so the result does
+ * not depend on how the device adds, repeats bit for bit and can be reproduced on the host.
+ * A row with W_r == 0 writes 0xFFFFFFFF to each of its ndraw outputs and sets word 0 of the
+ * workspace's 256-byte header: labsort_sample_workspace_status (which synchronises `stream`) then
+ * returns LABSORT_ERR_ARG; the other rows' results are valid.
+ * rows == 0, cols == 0 or ndraw == 0 launches nothing (LABSORT_OK before anything else is looked at).
+ * LABSORT_ERR_ARG before any launch: NULL d_keys, d_u or d_idx_out, a key type other than the three,
+ * cols > 2^23, rows > (2^31 - 1) / cols, rows > (2^31 - 1) / ndraw, an odd d_keys address with a
+ * 16-bit type, a d_u or d_idx_out that is not 4-byte aligned, any overlap (by the real sizes) between
+ * d_keys, d_u and d_idx_out, a missing or short workspace.
+ * cols <= labsort_kth_row_keys(): one launch (after the header's clearing), one workgroup per row,
+ * the row in registers in 16-byte groups; every thread sums the weights of each group it holds, one
+ * ordered 64-bit scan across the workgroup gives every group its range [lo, hi) of the prefix and
+ * the row its total, and for each draw the one thread whose group has lo <= s < hi walks its
+ * elements and stores the position: no barrier per draw, no histogram, no atomic.
+ * Longer rows, three launches: one workgroup per (row, chunk of labsort_kth_row_keys() keys) stores
+ * the chunk's mass; one workgroup per row scans the chunk masses (at most 512) into W_r and writes
+ * for each draw its chunk and what is left of s inside it; one workgroup per (row, draw) loads that
+ * one chunk and searches it as above.  The matrix is read once, plus one chunk per draw.  No kernel
+ * waits on another workgroup.  A call with more than 2^21 rows (short rows) or rows x ndraw draws
+ * (long rows) sends those workgroups out in several launches of 2^21, so the limits above are the
+ * only ones.
+ * Asynchronous on `stream`, no allocation, nothing read back; the launch sequence depends on the
+ * host arguments only (a captured call replays on new keys and a new d_u); the call clears what it
+ * relies on in the workspace.  labsort_sample_workspace_bytes never shrinks as rows, cols or ndraw
+ * grow: 256 bytes for cols <= labsort_kth_row_keys(); above, in this order and each region 256-byte
+ * aligned: the header, rows x chunks 8-byte chunk masses, rows x ndraw 16-byte draw states (the
+ * residual target and the chunk).
+ * Timing hooks: the kernels count under LABSORT_K_TOPK. */
+size_t labsort_sample_workspace_bytes(size_t rows, size_t cols, size_t ndraw);
+int labsort_sample_device(const void *d_keys, size_t rows, size_t cols, const uint32_t *d_u, size_t ndraw, int key_type,
+                          uint32_t *d_idx_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int labsort_sample_workspace_status(const void *d_workspace, void *stream);
+
 /* ---- unique: the distinct keys of an array with their counts, the position of each one's first
  * occurrence and every element's index into them (torch.unique(return_inverse, return_counts) on
  * index tensors, vocabulary and id compaction, edge deduplication on packed (src << 32) | dst keys,

@@ -69,6 +69,7 @@ C_SYMBOLS = [
     "labsort_kth_row_keys", "labsort_kth_workspace_bytes", "labsort_kth_device", "labsort_kth_workspace_status",
     "labsort_topk_mask_workspace_bytes", "labsort_topk_mask_device", "labsort_topk_mask_workspace_status",
     "labsort_top_p_weight", "labsort_top_p_workspace_bytes", "labsort_top_p_device", "labsort_top_p_workspace_status",
+    "labsort_sample_workspace_bytes", "labsort_sample_device", "labsort_sample_workspace_status",
     "labsort_key_order_bits", "labsort_key_from_order_bits",
     "labsort_unique_chunk_keys", "labsort_unique_workspace_bytes", "labsort_unique_device",
     "labsort_unique_workspace_status",
@@ -254,6 +255,11 @@ def _load() -> ctypes.CDLL:
         L.labsort_top_p_workspace_bytes.argtypes = [sz, sz]
         L.labsort_top_p_device.argtypes = [p, sz, sz, ctypes.c_float, p, i, ctypes.c_uint32, p, p, p, p, sz, p]
         L.labsort_top_p_workspace_status.argtypes = [p, p]
+    if hasattr(L, "labsort_sample_device"):  # (as labsort_radix_path above)
+        L.labsort_sample_workspace_bytes.restype = sz
+        L.labsort_sample_workspace_bytes.argtypes = [sz, sz, sz]
+        L.labsort_sample_device.argtypes = [p, sz, sz, p, sz, i, p, p, sz, p]
+        L.labsort_sample_workspace_status.argtypes = [p, p]
     if hasattr(L, "labsort_unique_device"):  # (as labsort_radix_path above)
         L.labsort_unique_chunk_keys.restype = sz
         L.labsort_unique_chunk_keys.argtypes = []
@@ -1191,6 +1197,76 @@ def top_p_mask(x, p, return_kept: bool = False, workspace=None, stream=None):
     kept = torch.empty((rows,), dtype=torch.int32, device=x.device) if return_kept else None
     top_p_device(x, rows, cols, p, d_mask_out=mask, d_kept_out=kept, key=key, workspace=workspace, stream=stream)
     return (mask, kept) if return_kept else mask
+
+
+def sample_workspace_bytes(rows: int, cols: int, ndraw: int) -> int:
+    return int(lib.labsort_sample_workspace_bytes(rows, cols, ndraw))
+
+
+def sample_device(d_keys, rows: int, cols: int, d_u, ndraw: int, d_idx_out, key: str = "f32", workspace=None,
+                  stream=None) -> None:
+    """Categorical sampling from every row of the dense rows x cols matrix d_keys of non-negative weights
+    (probabilities, normalised or not; never written): d_idx_out[r, d] (rows x ndraw uint32 words) is the
+    position drawn for the random word d_u[r, d] (rows x ndraw uint32 words, uniform in [0, 2^32), supplied
+    by the caller, never written) by exact inverse CDF: with top_p_device's integer weights w and the row's
+    total W, the smallest j whose inclusive prefix w_0 + .. + w_j exceeds floor(U W / 2^32) (labsort.h has
+    the rule).  An element of weight zero (a NaN, a negative, anything below 2^-40) is never drawn.  A row
+    without mass draws 0xFFFFFFFF and is reported by sample_workspace_status as ERR_ARG; the other rows
+    stay valid.  key: f32, bf16 or f16.  Workspace and status follow top_p_device: with a caller-owned
+    `workspace` (>= sample_workspace_bytes(rows, cols, ndraw)) the call stays asynchronous; without one it
+    allocates, synchronises and checks."""
+    workspace, wsb, own = _workspace(workspace, lambda: sample_workspace_bytes(rows, cols, ndraw))
+    _check(lib.labsort_sample_device(_ptr(d_keys), rows, cols, _ptr(d_u), ndraw, KEY[key], _ptr(d_idx_out),
+                                     _ptr(workspace), wsb, _stream(stream)), "sample_device")
+    if own:
+        sample_workspace_status(workspace, stream)
+
+
+def sample_workspace_status(workspace, stream=None) -> None:
+    """Synchronise `stream`; raise LabsortError with ERR_ARG if in the last sample_device call on
+    `workspace` a row's weights were all zero (its draws are 0xFFFFFFFF)."""
+    _check(lib.labsort_sample_workspace_status(_ptr(workspace), _stream(stream)), "sample (status)")
+
+
+def sample(x, num_samples: int = 1, u=None, generator=None, workspace=None, stream=None):
+    """The int32 tensor of shape (rows, num_samples) of positions drawn from every row of x by its
+    weights, with replacement: sample_device with its output allocated (what torch.multinomial(x,
+    num_samples, replacement=True) does, as exact integer arithmetic).  x: a contiguous 1-D (one row)
+    or 2-D CUDA tensor of float32, bfloat16 or float16.  u: None, or a contiguous tensor of shape
+    (rows, num_samples) on x's device: int32 or uint32 are the random words themselves, float32 values in
+    [0, 1) are taken as floor(u 2^32) (exact in float64); a value below 0 and a NaN are taken as word 0, a
+    value of 1 or more as word 2^32 - 1.  u=None draws the words with torch on x's
+    device from `generator`: two 16-bit halves from torch.randint, since one call does not reach 2^32.
+    TypeError before the device is touched for anything else.  Equal words give equal draws, bit for
+    bit.  Workspace and status as sample_device."""
+    import torch
+    if isinstance(x, torch.Tensor) and x.dtype == torch.int32:
+        raise TypeError(f"sample: float32, bfloat16 or float16 tensor expected, got {x.dtype}")
+    rows, cols, key = _dense_rows("sample", x)
+    if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or num_samples < 0:
+        raise TypeError(f"sample: num_samples must be a non-negative int, got {num_samples!r}")
+    ndraw = int(num_samples)
+    if cols == 0:
+        raise TypeError("sample: x has no columns to draw from")
+    if u is None:
+        hi = torch.randint(0, 1 << 16, (rows, ndraw), dtype=torch.int32, device=x.device, generator=generator)
+        lo = torch.randint(0, 1 << 16, (rows, ndraw), dtype=torch.int32, device=x.device, generator=generator)
+        words = (hi << 16) | lo  # (int32 wraps: the bits are the word)
+    else:
+        word_dtypes = [torch.int32] + ([torch.uint32] if hasattr(torch, "uint32") else [])
+        if (not isinstance(u, torch.Tensor) or u.dtype not in word_dtypes + [torch.float32] or u.device != x.device
+                or not u.is_contiguous() or tuple(u.shape) != (rows, ndraw)):
+            raise TypeError(f"sample: u must be None or a contiguous int32, uint32 or float32 tensor of shape ({rows}, {ndraw}) "
+                            "on x's device")
+        if u.dtype == torch.float32:
+            words = (u.to(torch.float64) * 4294967296.0).floor().nan_to_num_(nan=0.0).clamp_(0.0, 4294967295.0).to(torch.int64).to(torch.int32)
+        else:
+            words = u
+    out = torch.empty((rows, ndraw), dtype=torch.int32, device=x.device)
+    if rows == 0 or ndraw == 0:
+        return out  # (nothing is launched: there is no status to read)
+    sample_device(x, rows, cols, words, ndraw, out, key=key, workspace=workspace, stream=stream)
+    return out
 
 
 def unique_chunk_keys() -> int:

@@ -35,5 +35,13 @@ constexpr int TP_SLOTS = TK_SLOTS / 2;
 #define LABSORT_TP_SMALL_SLOTS 8  // (A/B build knob)
 #endif
 constexpr int TP_SMALL_SLOTS = LABSORT_TP_SMALL_SLOTS;
+// Categorical sampling (labsort_sample_device): the weights and the column limit of top-p filtering,
+// so a long row has at most 512 chunks, which one workgroup of as many threads scans (k_smp_pick).
+constexpr int SMP_MAX_CHUNKS = (int)(TP_MAX_COLS / TK_CHUNK);
+// One workgroup per row (short rows) or per draw (long rows): up to 2^31 - 1 of them, launched
+// SMP_MAX_GRID at a time, 2^31 threads at 1024 a workgroup.
+constexpr unsigned SMP_MAX_GRID = 1u << 21;
+static_assert((unsigned long long)SMP_MAX_GRID * KTH_BLOCK < (1ull << 32), "the runtime's limit on a grid's threads");
+static_assert(SMP_MAX_CHUNKS == 512 && SMP_MAX_CHUNKS <= KTH_BLOCK, "one thread per chunk of the longest row");
 
 }  // namespace labsort

@@ -46,6 +46,14 @@
 //                pick writes the KthState that k_kth_locate and k_tkm_apply read, and those two run
 //                as they do for the top-k filter (k_tkm_apply<.., COUNT = true> also counts what it
 //                keeps, for the call's kept-count output).
+//
+// Categorical sampling (labsort_sample_device) draws positions by inverse CDF on the same weights: a
+// prefix sum in position order and a search for where it crosses floor(U W / 2^32).
+//   k_smp_short  rows of up to KTH_ROW_KEYS keys, one launch: the row in registers, one ordered 64-bit
+//                scan of the groups' masses, then every draw of the row by the thread whose group holds it.
+//   k_smp_sum / k_smp_pick / k_smp_locate  longer rows: each chunk's mass; per row the prefix of the
+//                chunk masses and per draw its chunk and what is left of the target; per (row, draw)
+//                that one chunk searched as k_smp_short searches a row.
 #include "kth.h"
 
 #include <type_traits>
@@ -920,6 +928,248 @@ __global__ __launch_bounds__(KTH_BLOCK) void k_tp_pick(KthArgs a, TpArgs tp, int
     if (tid == 0u) *kout = KthState{ns.prefix, hit[1], p.d, hit[0]};
 }
 
+// ---- categorical sampling (labsort_sample_device): positions drawn by exact inverse CDF.  With the
+// weights above, W the row's total and U a caller's uniform 32-bit word, the target is
+// s = floor(U W / 2^32) < W and the draw is the smallest position whose inclusive prefix of weights,
+// in position order, exceeds s.  A prefix sum and a search: no sort, no select, no histogram.
+// Integer sums: any order gives the same. ----
+constexpr uint32_t SMP_NO_DRAW = 0xFFFFFFFFu;  // the position a row without mass draws, and its chunk
+struct SmpDraw {
+    uint64_t s;      // what is left of the draw's target inside its chunk
+    uint32_t chunk;  // SMP_NO_DRAW: the row has no mass
+    uint32_t pad;
+};
+static_assert(sizeof(SmpDraw) == 16, "labsort.h states the size of a draw state");
+struct SmpArgs {
+    const uint32_t *u;  // [rows][ndraw]
+    uint32_t *idx_out;  // [rows][ndraw]
+    uint64_t *cmass;    // long rows: [rows][nch]
+    SmpDraw *draw;      // long rows: [rows][ndraw]
+    uint32_t ndraw;
+    uint32_t first;     // k_smp_short, k_smp_locate: the launch's first workgroup, of rows or rows x ndraw
+};
+
+// s of U and W < 2^63: the 95-bit product by its two halves (tp_target's, rounded down)
+__device__ __forceinline__ uint64_t smp_target(uint32_t U, uint64_t W) {
+    const uint64_t hi = __umul64hi((uint64_t)U, W), lo = (uint64_t)U * W;
+    return (hi << 32) | (lo >> 32);
+}
+// Inclusive prefix sum of x over the wave's lanes (all 64 active): wave_incl_scan on 64-bit words
+__device__ __forceinline__ uint64_t smp_wave_scan(uint64_t x, uint32_t lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t t = tp_shfl(x, (int)lane - off);
+        if (lane >= (uint32_t)off) x += t;
+    }
+    return x;
+}
+
+// Up to BLOCK * KTH_KPT keys [beg, end) of a row in the registers of one workgroup, as k_tp_short holds
+// them: thread tid has groups q = t BLOCK + tid, and of each the mass c and the mass lo of
+// everything before it in position order.
+template <int KT, int BLOCK>
+struct SmpRow {
+    static constexpr int E = KTH_E<KT>, TG = KTH_KPT / E + 1, NW = BLOCK / WAVE, NE = TG * NW;
+    uint32_t u[TG][E], vm[TG];
+    uint64_t lo[TG], c[TG];
+};
+// Loads and scans; returns the total.  The 64-bit twin of kth_ordered_step, for all stripes at once:
+// a wave scan per stripe, the wave totals in LDS in position order (stripe, wave), one barrier, and
+// every wave scans those NE totals for what lies before each of its stripes.
+template <int KT, int BLOCK>
+__device__ __forceinline__ uint64_t smp_scan(SmpRow<KT, BLOCK> &r, const kth_elem_t<KT> *base, uint32_t beg, uint32_t end,
+                                             uint32_t mis, uint32_t nq, uint32_t xr, uint64_t *wtot) {
+    using R = SmpRow<KT, BLOCK>;
+    constexpr int E = R::E, TG = R::TG, NW = R::NW, NE = R::NE, H = (NE + 63) / 64;
+    static_assert(64 % NW == 0, "a stripe's wave totals lie in one 64-entry half");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        const uint32_t q = (uint32_t)t * BLOCK + tid;
+        int64_t i0;
+        r.vm[t] = 0u;
+        if (q < nq) r.vm[t] = kth_load<KT>(base, beg, end, mis, q, xr, r.u[t], i0);
+        else
+#pragma unroll
+            for (int j = 0; j < E; ++j) r.u[t][j] = 0u;
+    }
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        uint64_t c = 0u;
+#pragma unroll
+        for (int j = 0; j < E; ++j)
+            if ((r.vm[t] >> j) & 1u) c += tp_w<KT>(r.u[t][j], xr);
+        const uint64_t inc = smp_wave_scan(c, lane);
+        r.c[t] = c;
+        r.lo[t] = inc - c;
+        if (lane == 63u) wtot[(uint32_t)t * NW + wid] = inc;
+    }
+    __syncthreads();
+    uint64_t ex[H], total = 0u;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+        const uint32_t e = 64u * (uint32_t)h + lane;
+        const uint64_t v = e < (uint32_t)NE ? wtot[e] : 0u;
+        const uint64_t inc = smp_wave_scan(v, lane);
+        ex[h] = total + inc - v;
+        total += tp_shfl(inc, 63);
+    }
+#pragma unroll
+    for (int t = 0; t < TG; ++t) r.lo[t] += tp_shfl(ex[(t * NW) / 64], (int)(((uint32_t)t * NW + wid) & 63u));
+    return total;
+}
+// The draw of target s < total: the one thread whose group has lo <= s < lo + c walks its elements
+// and stores the position.  No barrier.
+template <int KT, int BLOCK>
+__device__ __forceinline__ void smp_find(const SmpRow<KT, BLOCK> &r, uint64_t s, uint32_t xr, uint32_t beg, uint32_t mis,
+                                         uint32_t *out) {
+    using R = SmpRow<KT, BLOCK>;
+    constexpr int E = R::E, TG = R::TG;
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+        if (s - r.lo[t] >= r.c[t]) continue;  // (s < lo wraps to more than any c)
+        uint64_t run = r.lo[t];
+        uint32_t at = 0u;
+        bool found = false;
+#pragma unroll
+        for (int j = 0; j < E; ++j)
+            if ((r.vm[t] >> j) & 1u) {
+                run += tp_w<KT>(r.u[t][j], xr);
+                if (!found && s < run) {
+                    found = true;
+                    at = (uint32_t)j;
+                }
+            }
+        *out = beg - mis + (uint32_t)E * ((uint32_t)t * BLOCK + threadIdx.x) + at;  // (at >= mis in the row's first group)
+    }
+}
+
+// Rows of up to BLOCK * KTH_KPT keys: one launch, one workgroup per row, every draw of the row from
+// the row in registers.  A row without mass stores SMP_NO_DRAW and reports in the header.
+template <int KT, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_smp_short(KthArgs a, SmpArgs sm) {
+    using R = SmpRow<KT, BLOCK>;
+    __shared__ uint64_t wtot[R::NE];
+    const uint32_t tid = threadIdx.x, row = sm.first + blockIdx.x;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t mis = group_mis(base, 0u), nq = group_count<R::E>(0u, a.cols, mis);  // <= T * BLOCK + 1
+    R r;
+    const uint64_t W = smp_scan<KT, BLOCK>(r, base, 0u, a.cols, mis, nq, a.xr, wtot);
+    const uint32_t *urow = sm.u + (size_t)row * sm.ndraw;
+    uint32_t *orow = sm.idx_out + (size_t)row * sm.ndraw;
+    if (W == 0u) {  // (uniform)
+        if (tid == 0u) a.hdr[0] = 1u;
+        for (uint32_t d = tid; d < sm.ndraw; d += BLOCK) orow[d] = SMP_NO_DRAW;
+        return;
+    }
+    for (uint32_t d = 0; d < sm.ndraw; ++d) {
+        // The weights do not depend on the draw: left to itself the compiler computes all of them ahead
+        // of the loop and keeps two registers per key (136 VGPRs at 256 threads, 44 bytes of scratch per
+        // lane at 1024 for bfloat16).  An xr that is opaque per draw makes the one walk compute its own.
+        uint32_t xr = a.xr;
+        asm volatile("" : "+s"(xr));
+        smp_find<KT, BLOCK>(r, smp_target(urow[d], W), xr, 0u, mis, orow + d);
+    }
+}
+
+// Longer rows.  One workgroup per (row, chunk): the chunk's mass, a plain store.
+template <int KT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_smp_sum(KthArgs a, SmpArgs sm) {
+    constexpr int E = KTH_E<KT>, T = KTH_KPT / E, NW = KTH_BLOCK / WAVE;
+    __shared__ uint64_t wtot[NW];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t row = blockIdx.x / a.nch, c = blockIdx.x - row * a.nch;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const uint32_t xr = a.xr;
+    const KthChunk ch = kth_chunk<KT>(base, a.cols, c);
+    uint64_t mine = 0u;
+    for (uint32_t q0 = 0; q0 < ch.nq; q0 += (uint32_t)T * KTH_BLOCK) {
+        uint32_t u[T][E], vm[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint32_t q = q0 + (uint32_t)t * KTH_BLOCK + tid;
+            int64_t i0;
+            vm[t] = 0u;
+            if (q < ch.nq) vm[t] = kth_load<KT>(base, ch.beg, ch.end, ch.mis, q, xr, u[t], i0);
+            else
+#pragma unroll
+                for (int j = 0; j < E; ++j) u[t][j] = 0u;
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                if ((vm[t] >> j) & 1u) mine += tp_w<KT>(u[t][j], xr);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += tp_shfl(mine, (int)(lane ^ (uint32_t)off));
+    if (lane == 0u) wtot[tid >> 6] = mine;
+    __syncthreads();
+    if (tid == 0u) {
+        uint64_t sum = 0u;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum += wtot[w];
+        sm.cmass[(size_t)row * a.nch + c] = sum;
+    }
+}
+
+// One workgroup per row: the running sums of the row's chunk masses (thread tid: chunk tid), and per
+// draw the chunk whose range of the prefix holds the target, with what is left of the target inside
+// it.  A row without mass stores SMP_NO_DRAW to its draws and their states and reports in the header.
+__global__ __launch_bounds__(SMP_MAX_CHUNKS) void k_smp_pick(KthArgs a, SmpArgs sm) {
+    constexpr int NW = SMP_MAX_CHUNKS / WAVE;
+    __shared__ uint64_t wtot[NW], cum[SMP_MAX_CHUNKS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6, row = blockIdx.x;
+    const uint32_t nch = a.nch < (uint32_t)SMP_MAX_CHUNKS ? a.nch : (uint32_t)SMP_MAX_CHUNKS;
+    const uint64_t v = tid < nch ? sm.cmass[(size_t)row * a.nch + tid] : 0u;
+    uint64_t inc = smp_wave_scan(v, lane);
+    if (lane == 63u) wtot[wid] = inc;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < NW; ++w)
+        if ((uint32_t)w < wid) inc += wtot[w];
+    cum[tid] = inc;
+    __syncthreads();
+    const uint64_t W = cum[SMP_MAX_CHUNKS - 1];
+    const uint32_t *urow = sm.u + (size_t)row * sm.ndraw;
+    uint32_t *orow = sm.idx_out + (size_t)row * sm.ndraw;
+    SmpDraw *drow = sm.draw + (size_t)row * sm.ndraw;
+    if (W == 0u && tid == 0u) a.hdr[0] = 1u;
+    for (uint32_t d = tid; d < sm.ndraw; d += SMP_MAX_CHUNKS) {
+        if (W == 0u) {
+            orow[d] = SMP_NO_DRAW;
+            drow[d] = SmpDraw{0u, SMP_NO_DRAW, 0u};
+            continue;
+        }
+        const uint64_t s = smp_target(urow[d], W);
+        uint32_t lo = 0u, hi = nch - 1u;  // the first chunk with cum > s: cum[nch - 1] = W > s
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (cum[mid] > s) hi = mid;
+            else lo = mid + 1u;
+        }
+        drow[d] = SmpDraw{s - (lo ? cum[lo - 1u] : 0u), lo, 0u};
+    }
+}
+
+// One workgroup per (row, draw): the draw's chunk in registers and k_smp_short's search on what is
+// left of the target.
+template <int KT>
+__global__ __launch_bounds__(KTH_BLOCK) void k_smp_locate(KthArgs a, SmpArgs sm) {
+    using R = SmpRow<KT, KTH_BLOCK>;
+    __shared__ uint64_t wtot[R::NE];
+    const uint32_t at = sm.first + blockIdx.x;  // the draw, of rows x ndraw
+    const uint32_t row = at / sm.ndraw;
+    const SmpDraw dr = sm.draw[at];
+    if (dr.chunk == SMP_NO_DRAW) return;  // (uniform: k_smp_pick stored the draw)
+    const uint32_t c = dr.chunk < a.nch ? dr.chunk : a.nch - 1u;
+    const kth_elem_t<KT> *base = kth_row<KT>(a, row);
+    const KthChunk ch = kth_chunk<KT>(base, a.cols, c);
+    R r;
+    smp_scan<KT, KTH_BLOCK>(r, base, ch.beg, ch.end, ch.mis, ch.nq, a.xr, wtot);
+    smp_find<KT, KTH_BLOCK>(r, dr.s, a.xr, ch.beg, ch.mis, sm.idx_out + at);
+}
+
 // ---- launches.  kt: KthKey, the instantiation that runs: f gets it as a constant ----
 template <class F>
 void kth_dispatch(int kt, F f) {
@@ -1114,6 +1364,62 @@ TpLayout tp_layout(size_t rows, size_t cols) {
     return L;
 }
 
+// ---- categorical sampling: launches and workspace ----
+// A grid of up to 2^31 - 1 workgroups (rows, or rows x ndraw) goes out in launches of at most
+// SMP_MAX_GRID: the runtime takes no grid of 2^32 threads or more.  f(sm, grid) launches the
+// workgroups sm.first .. sm.first + grid - 1.  One launch for everything but the largest calls.
+template <class F>
+hipError_t smp_launches(SmpArgs sm, size_t total, F f) {
+    for (size_t first = 0; first < total; first += SMP_MAX_GRID) {
+        sm.first = (uint32_t)first;
+        f(sm, (unsigned)(total - first < (size_t)SMP_MAX_GRID ? total - first : (size_t)SMP_MAX_GRID));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_smp_short(const KthArgs &a, const SmpArgs &sm, size_t rows, int kt, hipStream_t s) {
+    return smp_launches(sm, rows, [&](const SmpArgs &part, unsigned grid) {
+        tp_dispatch(kt, [&](auto K) {
+            constexpr int KT = decltype(K)::value;
+            if (a.cols <= (uint32_t)KTH_SMALL_ROW_KEYS) k_smp_short<KT, KTH_SMALL_BLOCK><<<grid, KTH_SMALL_BLOCK, 0, s>>>(a, part);
+            else k_smp_short<KT, KTH_BLOCK><<<grid, KTH_BLOCK, 0, s>>>(a, part);
+        });
+    });
+}
+
+// Longer rows: the chunk masses, each draw's chunk, each draw's position.  rows x chunks and rows
+// are far below SMP_MAX_GRID here (rows x cols <= 2^31 - 1 with cols > KTH_ROW_KEYS).
+int run_smp_long(const KthArgs &a, const SmpArgs &sm, size_t rows, int kt, hipStream_t s) {
+    tp_dispatch(kt, [&](auto K) { k_smp_sum<decltype(K)::value><<<(unsigned)(rows * a.nch), KTH_BLOCK, 0, s>>>(a, sm); });
+    HIP_TRY(hipGetLastError());
+    k_smp_pick<<<(unsigned)rows, SMP_MAX_CHUNKS, 0, s>>>(a, sm);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(smp_launches(sm, rows * sm.ndraw, [&](const SmpArgs &part, unsigned grid) {
+        tp_dispatch(kt, [&](auto K) { k_smp_locate<decltype(K)::value><<<grid, KTH_BLOCK, 0, s>>>(a, part); });
+    }));
+    return LABSORT_OK;
+}
+
+// header | per-chunk masses | per-draw states.  The header is the only word a call relies on being
+// clear.  A short row needs the header alone.
+struct SmpLayout {
+    size_t nch, off_cmass, off_draw, total;
+};
+SmpLayout smp_layout(size_t rows, size_t cols, size_t ndraw) {
+    SmpLayout L{};
+    Carver c;
+    c.take(KTH_HDR_BYTES);
+    L.total = c.o;
+    if (rows == 0 || ndraw == 0 || cols <= (size_t)KTH_ROW_KEYS) return L;
+    L.nch = (cols + TK_CHUNK - 1) / TK_CHUNK;
+    L.off_cmass = c.take(rows * L.nch * sizeof(uint64_t));
+    L.off_draw = c.take(rows * ndraw * sizeof(SmpDraw));
+    L.total = c.o;
+    return L;
+}
+
 }  // namespace
 
 }  // namespace labsort
@@ -1266,5 +1572,43 @@ int labsort_top_p_device(const void *d_keys, size_t rows, size_t cols, float p, 
 }
 
 int labsort_top_p_workspace_status(const void *d_ws, void *stream) { return labsort_kth_workspace_status(d_ws, stream); }
+
+size_t labsort_sample_workspace_bytes(size_t rows, size_t cols, size_t ndraw) { return smp_layout(rows, cols, ndraw).total; }
+
+int labsort_sample_device(const void *d_keys, size_t rows, size_t cols, const uint32_t *d_u, size_t ndraw, int key_type,
+                          uint32_t *d_idx_out, void *d_ws, size_t ws_bytes, void *stream) {
+    if (rows == 0 || cols == 0 || ndraw == 0) return LABSORT_OK;
+    if (!d_keys || !d_u || !d_idx_out) return LABSORT_ERR_ARG;
+    if (key_type != LABSORT_KEY_F32 && !key_type_is16(key_type)) return LABSORT_ERR_ARG;
+    if (cols > TP_MAX_COLS || rows > (size_t)0x7FFFFFFFu / cols || rows > (size_t)0x7FFFFFFFu / ndraw) return LABSORT_ERR_ARG;
+    const bool k16 = key_type_is16(key_type);
+    if (k16 && ((uintptr_t)d_keys & 1u)) return LABSORT_ERR_ARG;
+    if (((uintptr_t)d_u | (uintptr_t)d_idx_out) & 3u) return LABSORT_ERR_ARG;
+    const size_t key_bytes = rows * cols * (k16 ? 2 : 4), w_bytes = rows * ndraw * 4;
+    if (ranges_overlap(d_keys, key_bytes, d_u, w_bytes) || ranges_overlap(d_keys, key_bytes, d_idx_out, w_bytes) ||
+        ranges_overlap(d_u, w_bytes, d_idx_out, w_bytes))
+        return LABSORT_ERR_ARG;
+    const SmpLayout L = smp_layout(rows, cols, ndraw);
+    if (!d_ws || ws_bytes < L.total) return LABSORT_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    char *ws = static_cast<char *>(d_ws);
+    KthCall c = kth_call(d_keys, cols, 1, nullptr, 1, key_type, d_ws, KthLayout{});
+    SmpArgs sm{};
+    sm.u = d_u;
+    sm.idx_out = d_idx_out;
+    sm.ndraw = (uint32_t)ndraw;
+    HIP_TRY(launch_zero(ws, KTH_HDR_BYTES, s));
+    TimingScope ts(LABSORT_K_TOPK, s);
+    if (cols <= (size_t)KTH_ROW_KEYS) {
+        HIP_TRY(launch_smp_short(c.a, sm, rows, c.kt, s));
+        return LABSORT_OK;
+    }
+    c.a.nch = (uint32_t)L.nch;
+    sm.cmass = reinterpret_cast<uint64_t *>(ws + L.off_cmass);
+    sm.draw = reinterpret_cast<SmpDraw *>(ws + L.off_draw);
+    return run_smp_long(c.a, sm, rows, c.kt, s);
+}
+
+int labsort_sample_workspace_status(const void *d_ws, void *stream) { return labsort_kth_workspace_status(d_ws, stream); }
 
 }  // extern "C"

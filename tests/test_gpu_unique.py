@@ -1,13 +1,27 @@
 """GPU tests of labsort_unique_device / ls.unique_device / ls.unique against the numpy model
 (tests/unique_model.py): every requested output, m and the sentinel past m compared bit for bit, the
-input unchanged.  C = ls.unique_chunk_keys() is the chunk of the run-edge passes; the workspace of
-every call is filled with garbage first and sized for exactly the outputs that are passed."""
+input unchanged.  C = ls.unique_chunk_keys() is the chunk of the run-edge passes.
+
+Guards.  run() places the keys, every output and the one word of m inside a storage of its own with
+GUARD_BYTES (512: 64 elements of the widest type) of the byte 0x3C in front and behind, which is
+neither the outputs' pre-fill 0xA5 nor the workspace's 0xCD / 0xFF, and check() asserts that every
+guard byte is unchanged, naming the buffer and the side.  The workspace is a view 256 bytes into a
+storage of 512 bytes more than is asked for, with the same guard byte on both sides; unless a case
+passes its own it is sized for exactly the outputs that are passed and filled with 0xCD.
+
+Offsets.  in_off, uniq_off, counts_off, first_off and inv_off are counted in elements from a 256-byte
+aligned address, so a buffer's address is off * element size mod 256; Guarded asserts that residue
+mod 16, and the cases that rely on an unaligned (or aligned) pointer assert which one they have.
+
+Workspace alignment.  Every workspace here starts on a 256-byte boundary, as the allocator's do: no
+entry of the library but searchsorted defines a smaller one, and none is tested."""
 import functools
 
 import numpy as np
 import pytest
 
 import unique_model as U
+import whole_sort_model as W
 
 pytestmark = pytest.mark.gpu
 
@@ -15,34 +29,79 @@ S32 = np.uint32(U.SENTINEL32)
 S64 = np.uint64((U.SENTINEL32 << 32) | U.SENTINEL32)
 COUNTS, FIRST, INVERSE = 1, 2, 4
 ALL = COUNTS | FIRST | INVERSE
+GUARD_BYTE, GUARD_BYTES = 0x3C, 512
+SENT_BYTE = U.SENTINEL32 & 0xFF
+assert U.SENTINEL32 == SENT_BYTE * 0x01010101 and GUARD_BYTE not in (SENT_BYTE, 0xCD, 0xFF)
 
 
 def signed(a):
     return a.view(np.int64 if a.dtype == np.uint64 else np.int32)
 
 
-def run(ls, torch, x, kind, consecutive=False, outputs=ALL, exp=None, tag=""):
-    """One unique_device call on the words x, checked against the model."""
+class Guarded:
+    """n elements of esize bytes, `off` elements behind a 256-byte aligned address, with `lead` guard
+    bytes in front of that address and at least as many behind the last element.  view: the elements
+    (int32, int64, or uint8 for esize 1), filled with the byte `fill`."""
+
+    def __init__(self, torch, name, n, esize, off=0, fill=SENT_BYTE, lead=GUARD_BYTES):
+        assert lead % 256 == 0 and lead >= 64 * esize
+        self.name, self.lo = name, lead + off * esize
+        self.hi = self.lo + n * esize
+        self.store = torch.full((self.hi + lead,), GUARD_BYTE, dtype=torch.uint8, device="cuda")
+        assert self.store.data_ptr() % 256 == 0
+        body = self.store[self.lo:self.hi]
+        body.fill_(fill)
+        self.view = body if esize == 1 else body.view(torch.int64 if esize == 8 else torch.int32)
+        assert self.view.numel() == n and self.view.data_ptr() % 16 == (off * esize) % 16
+
+    def check(self, msg):
+        for side, part in (("in front of", self.store[:self.lo]), ("behind", self.store[self.hi:])):
+            assert bool((part == GUARD_BYTE).all()), f"the guard {side} {self.name} was written: {msg}"
+
+
+def workspace(torch, nbytes, fill=0xCD):
+    """A guarded workspace of nbytes on a 256-byte boundary, 256 bytes into its storage."""
+    g = Guarded(torch, "the workspace", nbytes, 1, fill=fill, lead=256)
+    assert g.view.data_ptr() % 256 == 0
+    return g
+
+
+def run(ls, torch, x, kind, consecutive=False, outputs=ALL, exp=None, tag="", in_off=0, uniq_off=0, counts_off=0,
+        first_off=0, inv_off=0, ws=None, ws_positions=False):
+    """One unique_device call on the words x, checked against the model.  *_off: elements between a
+    256-byte aligned address and the buffer.  ws: a Guarded workspace (workspace()) that is used as it
+    is and not cleared; without one, one of exactly the size asked for, with positions when the call
+    passes first or inverse or when ws_positions is set."""
     x = np.ascontiguousarray(x, dtype=U.word_dtype(kind))
-    n = x.size
-    values, counts, first, inverse, m = exp if exp is not None else U.expected(x, kind, consecutive)
-    sent = S64 if x.dtype == np.uint64 else S32
-    dev = lambda a: torch.from_numpy(signed(a).copy()).cuda()  # noqa: E731
-    words = lambda on: dev(np.full(n, S32, dtype=np.uint32)) if on else None  # noqa: E731
-    d_keys = dev(x)
-    d_uniq = dev(np.full(n, sent, dtype=x.dtype))
-    d_num = dev(np.full(1, S32, dtype=np.uint32))
-    d_counts, d_first, d_inverse = words(outputs & COUNTS), words(outputs & FIRST), words(outputs & INVERSE)
-    pos = bool(outputs & (FIRST | INVERSE))
-    ws = torch.full((ls.unique_workspace_bytes(n, kind, consecutive, pos),), 0xCD, dtype=torch.uint8, device="cuda")
-    ls.unique_device(d_keys, n, d_uniq, d_num, d_counts, d_first, d_inverse, key=kind, consecutive=consecutive, workspace=ws)
-    ls.unique_workspace_status(ws, n, kind, consecutive)  # (synchronises)
-    check(x, d_keys, d_uniq, d_num, d_counts, d_first, d_inverse, (values, counts, first, inverse, m),
-          f"{tag} {kind} n={n} consecutive={consecutive} outputs={outputs}")
+    n, esize = x.size, x.dtype.itemsize
+    exp = exp if exp is not None else U.expected(x, kind, consecutive)
+    keys = Guarded(torch, "the keys", n, esize, in_off)
+    keys.view.copy_(torch.from_numpy(signed(x).copy()))
+    uniq = Guarded(torch, "unique_out", n, esize, uniq_off)
+    num = Guarded(torch, "num_out", 1, 4)
+    words = lambda on, name, off: Guarded(torch, name, n, 4, off) if on else None  # noqa: E731
+    counts = words(outputs & COUNTS, "counts_out", counts_off)
+    first = words(outputs & FIRST, "first_out", first_off)
+    inverse = words(outputs & INVERSE, "inverse_out", inv_off)
+    if ws is None:
+        pos = bool(outputs & (FIRST | INVERSE)) or ws_positions
+        ws = workspace(torch, ls.unique_workspace_bytes(n, kind, consecutive, pos))
+    view = lambda g: None if g is None else g.view  # noqa: E731
+    msg = f"{tag} {kind} n={n} consecutive={consecutive} outputs={outputs}"
+    ls.unique_device(keys.view, n, uniq.view, num.view, view(counts), view(first), view(inverse), key=kind,
+                     consecutive=consecutive, workspace=ws.view)
+    try:
+        ls.unique_workspace_status(ws.view, n, kind, consecutive)  # (synchronises)
+    except ls.LabsortError as e:
+        raise AssertionError(f"unique_workspace_status: {e}: {msg}") from e
+    check(x, keys.view, uniq.view, num.view, view(counts), view(first), view(inverse), exp, msg,
+          guards=[g for g in (keys, uniq, num, counts, first, inverse, ws) if g is not None])
 
 
-def check(x, d_keys, d_uniq, d_num, d_counts, d_first, d_inverse, exp, msg):
+def check(x, d_keys, d_uniq, d_num, d_counts, d_first, d_inverse, exp, msg, guards=()):
     values, counts, first, inverse, m = exp
+    for g in guards:
+        g.check(msg)
     host = lambda t: t.cpu().numpy().view(np.uint64 if t.element_size() == 8 else np.uint32)  # noqa: E731
     sent = S64 if x.dtype == np.uint64 else S32
     assert int(host(d_num)[0]) == m, f"m: {msg}"
@@ -277,3 +336,261 @@ def test_unique_against_torch(ls, torch_gpu):
     fv, fc = ls.unique(f, return_counts=True)
     assert fc.tolist() == [2, 1, 1, 2] and fv[:3].tolist() == [-0.0, 0.0, 1.5] and bool(torch.isnan(fv[3]))
     assert bool(torch.signbit(fv[0])) and not bool(torch.signbit(fv[1]))
+
+
+# ---- unaligned views -----------------------------------------------------------------------------------
+ODD = dict(uniq_off=1, counts_off=3, first_off=5, inv_off=7)  # every output at an odd offset of its own
+EVEN = dict(uniq_off=0, counts_off=0, first_off=0, inv_off=0)
+# (keys' offset in elements, the outputs' offsets): every unaligned residue of the keys with unaligned
+# outputs, then aligned keys with unaligned outputs and unaligned keys with aligned outputs
+VIEWS4 = [(1, ODD), (2, ODD), (3, ODD), (0, ODD), (1, EVEN)]
+VIEWS8 = [(1, ODD), (0, ODD), (1, EVEN)]
+VIEW_CASES = [(k, i) for k in ("u32", "f32") for i in range(len(VIEWS4))] + \
+             [(k, i) for k in ("i64", "f64") for i in range(len(VIEWS8))]
+
+
+@functools.lru_cache(maxsize=None)
+def runs_case(div, n, kind):
+    """i // div as keys of the kind, with the consecutive mode's expectation (read-only)."""
+    x = U.from_ints(np.arange(n, dtype=np.int64) // div, kind)
+    exp = U.expected(x, kind, True)
+    U.freeze(x, *exp)
+    return x, exp
+
+
+@pytest.mark.parametrize("kind,view", VIEW_CASES, ids=[f"{k}-{i}" for k, i in VIEW_CASES])
+def test_unaligned_views(ls, torch_gpu, kind, view):
+    """Keys 4, 8 or 12 bytes (8-byte kinds: 8 bytes) past a 16-byte boundary and every output at an odd
+    element offset of its own: uq_load_heads reads every group of every chunk element by element in
+    consecutive mode, k_uq_iota_copy takes its element-wise branch in the pair sort's, the keys-only
+    sort and sort64 read an unaligned input.  n = 2C + 3 (two full chunks and one of three elements:
+    full groups, the partial group and lane 0's read across a chunk's end) and 65; ALL (pair sort),
+    COUNTS (keys sort) and no optional output.  Consecutive mode on i // 3 and i // 5, whose heads fall
+    on different lanes from group to group, so an element loaded from the wrong place changes m;
+    sorted mode on mod1000 and full-width words."""
+    wide = kind in U.KINDS64
+    in_off, outs = (VIEWS8 if wide else VIEWS4)[view]
+    esize = 8 if wide else 4
+    # the residues mod 16 that this configuration is about (Guarded asserts each pointer's against its offset)
+    residues = {"keys": in_off * esize % 16, "unique_out": outs["uniq_off"] * esize % 16,
+                **{name: outs[name] * 4 % 16 for name in ("counts_off", "first_off", "inv_off")}}
+    assert (residues["keys"] != 0) == (in_off != 0) and residues["keys"] == (in_off * esize if in_off else 0)
+    assert all(r != 0 for name, r in residues.items() if name != "keys") if outs is ODD else outs is EVEN
+    assert len({outs[name] for name in outs}) == (4 if outs is ODD else 1)
+    assert in_off or outs is ODD  # (something is unaligned in every configuration)
+    C = chunk(ls)
+    for n in (2 * C + 3, 65):
+        for outputs in (ALL, COUNTS, 0):
+            for div in (3, 5):
+                x, exp = runs_case(div, n, kind)
+                assert exp[4] == (n + div - 1) // div
+                run(ls, torch_gpu, x, kind, True, outputs, exp, tag=f"i//{div} in_off={in_off}", in_off=in_off, **outs)
+            for gen in ("mod1000", "uniform"):
+                x, exp = U.case(gen, n, 0x0A11 + n, kind, False)
+                run(ls, torch_gpu, x, kind, False, outputs, exp, tag=f"{gen} in_off={in_off}", in_off=in_off, **outs)
+
+
+# ---- the workspace contract ----------------------------------------------------------------------------
+def reuse_sequence(C):
+    """(n, kind, consecutive, outputs, generator): sizes, key widths, modes and output sets in turn.
+    Call 1 is a keys-only sort of one tile on the untouched garbage: it has no status word, so its
+    status must not read one.  Calls 2-4: a pair sort (radix), a consecutive call, a keys-only sort of
+    a smaller n.  Calls 5-6: a 64-bit call, then a 4-byte one.  Call 11: a keys-only sort of one tile
+    behind a 64-bit call's use of the same bytes."""
+    big = (1 << 18) + 3
+    return [(3 * C + 5, "u32", False, COUNTS, "mod1000"),
+            (big, "u32", False, ALL, "uniform"),
+            (3 * C + 5, "i32", True, ALL, "sorted_runs"),
+            (C + 1, "u32", False, COUNTS, "mod1000"),
+            (big, "i64", False, ALL, "mod1000"),
+            (65, "f32", False, FIRST, "mod17"),
+            (big, "f32", False, 0, "uniform"),
+            (3 * C + 5, "f64", True, COUNTS | INVERSE, "sorted_runs"),
+            (3 * C + 5, "u32", False, ALL, "mod1000"),
+            (C + 1, "u64", False, COUNTS, "uniform"),
+            (3 * C + 5, "i32", False, COUNTS, "mod17"),
+            (65, "u64", True, ALL, "mod17"),
+            (big, "i32", False, COUNTS | INVERSE, "mod1000"),
+            (65, "u32", False, 0, "uniform")]
+
+
+def test_workspace_reuse(ls, torch_gpu):
+    """One workspace, sized with positions for the largest call of the sequence, filled with 0xFF once
+    and never cleared, serves fourteen calls of changing n, key width, mode and output set: every
+    output is exact, no guard is touched and unique_workspace_status with the call's own (n, kind,
+    consecutive) is OK after each (run() raises otherwise), although header word UQ_HDR_SORT and the
+    inner sort's status word are whatever the calls before left there."""
+    seq = reuse_sequence(chunk(ls))
+    assert len(seq) >= 12 and {c[0] for c in seq} == {65, chunk(ls) + 1, 3 * chunk(ls) + 5, (1 << 18) + 3}
+    pair = lambda c: c[1] in U.KINDS32 and not c[2] and bool(c[3] & (FIRST | INVERSE))  # noqa: E731
+    keys = lambda c: c[1] in U.KINDS32 and not c[2] and not c[3] & (FIRST | INVERSE)  # noqa: E731
+    assert any(pair(a) and b[2] and keys(c) and c[0] < a[0] for a, b, c in zip(seq, seq[1:], seq[2:]))
+    assert any(a[1] in U.KINDS64 and b[1] in U.KINDS32 for a, b in zip(seq, seq[1:]))
+    assert keys(seq[0]) and ls.pair_tile_keys() < seq[0][0] <= ls.tile_keys()
+    ws = workspace(torch_gpu, max(ls.unique_workspace_bytes(n, kind, cons, True) for n, kind, cons, _, _ in seq), fill=0xFF)
+    for i, (n, kind, cons, outputs, gen) in enumerate(seq):
+        assert ws.view.numel() >= ls.unique_workspace_bytes(n, kind, cons, bool(outputs & (FIRST | INVERSE)))
+        x, exp = U.case(gen, n, 0x2E05 + i, kind, cons)
+        run(ls, torch_gpu, x, kind, cons, outputs, exp, tag=f"reuse call {i + 1} {gen}", ws=ws)
+
+
+@pytest.mark.parametrize("kind", ["u32", "f32", "i64"])
+def test_oversized_workspace(ls, torch_gpu, kind):
+    """The output sets without first and inverse on a workspace sized with positions, and every kind
+    of call on one sized for 2 n keys: the layout is the call's own, whatever the size.  n = 3C + 5
+    (one tile of the keys-only sort, a merge of pairs) and 2^16 + 1 (the gathered radix without
+    positions, whose layout shares nothing with the merge sort's)."""
+    for n in (3 * chunk(ls) + 5, ls.GS_MIN_N + 1):
+        for consecutive in (False, True):
+            x, exp = U.case("mod1000", n, 0x0B16, kind, consecutive)
+            for outputs in (0, COUNTS):
+                with_pos, without = (ls.unique_workspace_bytes(n, kind, consecutive, p) for p in (True, False))
+                assert with_pos >= without
+                run(ls, torch_gpu, x, kind, consecutive, outputs, exp, tag="sized with positions", ws_positions=True)
+            for outputs in (0, COUNTS, ALL):
+                pos = bool(outputs & (FIRST | INVERSE))
+                twice = ls.unique_workspace_bytes(2 * n, kind, consecutive, pos)
+                assert twice >= ls.unique_workspace_bytes(n, kind, consecutive, pos)
+                run(ls, torch_gpu, x, kind, consecutive, outputs, exp, tag="sized for 2n", ws=workspace(torch_gpu, twice))
+
+
+# ---- every inner-sort route ----------------------------------------------------------------------------
+ROUTE_CLASSES = ("tile_sort", "merge", "merge4", "gsweep", "gcopy", "histogram", "onesweep")
+
+
+def route_of(ls, n, pairs):
+    """The sort that LABSORT_ALGO_AUTO runs for n 4-byte keys (api.hip: resolve_algo, small_path and
+    use_gather for the keys-only entry, resolve_pairs_algo and the one-tile test for key/value)."""
+    if pairs:
+        return "tile" if n <= ls.pair_tile_keys() else "merge" if n <= W.constants()["AUTO_PAIRS_MERGE_MAX_KEYS"] else "onesweep"
+    return "tile" if n <= ls.tile_keys() else "merge" if n <= ls.GS_MIN_N else ls.radix_impl(n)
+
+
+def run_routed(ls, torch, x, kind, outputs, exp, tag):
+    """run() with the timing hooks on; the launches that the inner sort's classes counted must be the
+    route's: one tile sort alone; one tile sort and merge passes; gathered passes and their copy; one
+    histogram and four onesweep passes."""
+    route = route_of(ls, x.size, bool(outputs & (FIRST | INVERSE)))
+    ls.timing_enable(True)
+    try:
+        run(ls, torch, x, kind, False, outputs, exp, tag=f"{tag} route={route}")
+        got = {c: ls.timing_read(c)[1] for c in ROUTE_CLASSES}
+    finally:
+        ls.timing_enable(False)
+    merges, gathered = got["merge"] + got["merge4"], got["gsweep"]
+    want = {"tile": got["tile_sort"] == 1 and merges == 0 and gathered == 0 and got["onesweep"] == 0,
+            "merge": got["tile_sort"] == 1 and merges >= 1 and gathered == 0 and got["onesweep"] == 0,
+            "gather": got["tile_sort"] == 0 and merges == 0 and gathered >= 1 and got["gcopy"] == 1 and got["onesweep"] == 0,
+            "onesweep": got["tile_sort"] == 0 and merges == 0 and gathered == 0 and got["histogram"] == 1 and got["onesweep"] == 4}
+    assert want[route], f"{tag} n={x.size} outputs={outputs}: route {route} expected, launches {got}"
+    return route
+
+
+ROUTE_IDS = [i for i, _ in U.route_sizes(1, 1, 1, 1)]
+
+
+@pytest.mark.parametrize("outputs", [ALL, COUNTS], ids=["pairs", "keys"])
+@pytest.mark.parametrize("sid", ROUTE_IDS)
+@pytest.mark.parametrize("kind", U.KINDS32)
+def test_inner_sort_routes(ls, torch_gpu, kind, sid, outputs):
+    """The sizes at which the inner sort of 4-byte keys changes algorithm, one below, at and one above,
+    with every output (labsort_sort_pairs_device) and with counts only (labsort_sort_device).  By
+    api.hip, with LABSORT_ALGO_AUTO:
+      keys   n <= tile_keys() (32768): one tile sort, no workspace; n <= 2^16: tile sort and merge
+             passes; 2^16 < n < 2^25: the gathered radix; from 2^25: histogram, plan and onesweep passes;
+      pairs  n <= pair_tile_keys() (16384): one key/value tile sort; n <= 2^18: tile sort and merge
+             passes; above: histogram, plan and onesweep passes with payloads (no gathered radix).
+    So 2^18 is no edge of the keys-only route and tile_keys() and 2^16 are none of the pairs'; they are
+    edges of the workspace layout all the same (uq_inner_bytes).  The timing hooks tell the routes
+    apart by launch counts (run_routed); they do not tell a keys-only from a key/value launch of the
+    same class.  Full-width words (m = n or nearly) and 1000 values at every size."""
+    sizes = dict(U.route_sizes(ls.pair_tile_keys(), ls.tile_keys(), ls.GS_MIN_N, W.constants()["AUTO_PAIRS_MERGE_MAX_KEYS"]))
+    assert sizes["pair_tile"] == ls.pair_tile_keys() < sizes["tile"] == ls.tile_keys() < sizes["2^16"] == 1 << 16
+    assert sizes["2^18"] == 1 << 18 and list(sizes) == ROUTE_IDS
+    n = sizes[sid]
+    routes = set()
+    for gen in ("uniform", "mod1000"):
+        x, exp = U.case(gen, n, 0x4007 + n, kind, False)
+        assert exp[4] <= 1000 if gen == "mod1000" else exp[4] > n - n // 64 - 8  # (f32: the NaNs are one value)
+        routes.add(run_routed(ls, torch_gpu, x, kind, outputs, exp, gen))
+    pairs = outputs == ALL
+    edge, d = (sid[:-2], int(sid[-2:])) if sid[-2] in "+-" else (sid, 0)
+    low, high = {("pair_tile", True): ("tile", "merge"), ("tile", True): ("merge", "merge"), ("2^16", True): ("merge", "merge"),
+                 ("2^18", True): ("merge", "onesweep"), ("pair_tile", False): ("tile", "tile"), ("tile", False): ("tile", "merge"),
+                 ("2^16", False): ("merge", "gather"), ("2^18", False): ("gather", "gather")}[(edge, pairs)]
+    assert routes == {high if d > 0 else low}
+
+
+LARGE = [((1 << 25) - 1, ALL), (1 << 25, ALL), ((1 << 25) - 1, COUNTS), (1 << 25, COUNTS)]
+
+
+@pytest.mark.parametrize("V", [1000, (1 << 20) + 7])
+@pytest.mark.parametrize("n,outputs", LARGE, ids=["2^25-1-pairs", "2^25-pairs", "2^25-1-keys", "2^25-keys"])
+def test_gathered_radix_end(ls, torch_gpu, n, outputs, V):
+    """GS_MAX_N = 2^25 keys and one fewer, u32: the keys-only inner sort runs the gathered radix for
+    the last time at 2^25 - 1 and onesweep from 2^25; the key/value sort runs onesweep with payloads
+    on both sides (api.hip), where the workspace layout still changes (uq_inner_bytes).  The keys are
+    spread(n, V): V distinct full-width values in turn, whose expectation is a closed form that
+    sorts V values, not n."""
+    assert n in (ls.GS_MAX_N - 1, ls.GS_MAX_N) and ls.GS_MAX_N == 1 << 25
+    x, exp = U.spread(n, V, "u32"), U.spread_expected(n, V, "u32")
+    assert exp[4] == V
+    route = run_routed(ls, torch_gpu, x, "u32", outputs, exp, f"spread V={V}")
+    assert route == ("onesweep" if outputs == ALL or n == ls.GS_MAX_N else "gather")
+
+
+# ---- ls.unique on views ----------------------------------------------------------------------------------
+PY_DTYPES = [("int32", "i32"), ("float32", "f32"), ("int64", "i64"), ("float64", "f64"), ("uint32", "u32"), ("uint64", "u64")]
+
+
+@pytest.mark.parametrize("name,kind", PY_DTYPES, ids=[d for d, _ in PY_DTYPES])
+def test_python_views_and_dtypes(ls, torch_gpu, name, kind):
+    """ls.unique on x[1:], a contiguous view of 2C + 3 elements that starts one element into its
+    allocation, with a caller's workspace that serves three calls: every output in sorted mode, every
+    output in consecutive mode, the values alone.  Against the model on the words; the integer dtypes
+    against torch.unique and torch.unique_consecutive (on the host, as int64 or by the words' order)
+    as well.  A dtype that this torch does not have has nothing to run."""
+    torch = torch_gpu
+    if not hasattr(torch, name):
+        return
+    dtype, n = getattr(torch, name), 2 * chunk(ls) + 3
+    esize = 8 if kind in U.KINDS64 else 4
+    raw = torch.int64 if esize == 8 else torch.int32
+    words = lambda t: t.view(raw).cpu().numpy().view(U.word_dtype(kind))  # noqa: E731
+
+    def view_of(x):
+        store = torch.from_numpy(signed(np.concatenate([x[:1], x])).copy()).cuda().view(dtype)
+        v = store[1:]
+        assert v.data_ptr() % 16 == esize and v.is_contiguous() and v.numel() == n and v.dtype == dtype
+        return v
+
+    ws = torch.full((max(ls.unique_workspace_bytes(n, kind, c, True) for c in (False, True)),), 0xCD, dtype=torch.uint8,
+                    device="cuda")
+    xs = U.generate("mod1000", n, 0x9107, kind)
+    xc = U.from_ints(np.arange(n, dtype=np.int64) // 3 % 11, kind)
+    for x, consecutive in ((xs, False), (xc, True)):
+        v = view_of(x)
+        values, inverse, counts, index = ls.unique(v, return_inverse=True, return_counts=True, return_index=True,
+                                                   consecutive=consecutive, workspace=ws)
+        ev, ec, ef, ei, m = U.expected(x, kind, consecutive)
+        assert values.dtype == dtype and inverse.dtype == counts.dtype == index.dtype == torch.int32
+        assert values.numel() == counts.numel() == index.numel() == m and inverse.numel() == n
+        for what, got, want in (("values", values, ev), ("counts", counts, ec), ("index", index, ef), ("inverse", inverse, ei)):
+            got = got.view(raw).cpu().numpy().view(want.dtype) if what == "values" else got.cpu().numpy().view(np.uint32)
+            np.testing.assert_array_equal(got, want, err_msg=f"{what}: {name} consecutive={consecutive}")
+        np.testing.assert_array_equal(words(v), x, err_msg="the input was written")
+        if kind in U.INT_KINDS:
+            # an order-preserving map of the keys into int64 (uint64: by rank), so torch's own kernels take them
+            ints = {"i32": lambda w: w.view(np.int32).astype(np.int64), "u32": lambda w: w.astype(np.int64),
+                    "i64": lambda w: w.view(np.int64), "u64": lambda w: np.searchsorted(np.unique(x), w).astype(np.int64)}[kind]
+            t = torch.from_numpy(ints(x).copy())
+            if consecutive:
+                tv, ti, tc = torch.unique_consecutive(t, return_inverse=True, return_counts=True)
+            else:
+                tv, ti, tc = torch.unique(t, sorted=True, return_inverse=True, return_counts=True)
+            np.testing.assert_array_equal(ints(words(values)), tv.numpy())
+            np.testing.assert_array_equal(inverse.cpu().numpy(), ti.numpy())
+            np.testing.assert_array_equal(counts.cpu().numpy(), tc.numpy())
+    only = ls.unique(view_of(xs), workspace=ws)
+    assert isinstance(only, torch.Tensor) and only.dtype == dtype
+    np.testing.assert_array_equal(words(only), U.expected(xs, kind)[0])

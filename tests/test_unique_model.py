@@ -86,6 +86,35 @@ def test_float_equality(ls, kind):
     assert [int(v) for v in values] == [canon, pz, mz, canon] and list(counts) == [3, 1, 2, 1] and list(first) == [0, 3, 4, 6]
 
 
+@pytest.mark.parametrize("kind", U.INT_KINDS)
+@pytest.mark.parametrize("V", [1, 7, 1000])
+def test_spread_closed_form(kind, V):
+    """spread_expected, which sorts V values, against expected(), which sorts all n; the V values are
+    distinct and, from V = 1000 on, differ in every byte of the word."""
+    b = U.spread_values(V, kind)
+    assert np.unique(b).size == V and b.dtype == U.word_dtype(kind)
+    if V == 1000:
+        for byte in range(b.dtype.itemsize):
+            assert np.unique((b >> b.dtype.type(8 * byte)) & b.dtype.type(0xFF)).size > 200
+    for n in sorted({1, max(V - 1, 1), V, V + 1, 10 * V + 3}):
+        x = U.spread(n, V, kind)
+        assert x.size == n and x.dtype == U.word_dtype(kind)
+        np.testing.assert_array_equal(x, b[np.arange(n) % V])
+        want, got = U.expected(x, kind), U.spread_expected(n, V, kind)
+        assert got[4] == want[4] == min(V, n)
+        for name, g, w in zip(("values", "counts", "first", "inverse"), got, want):
+            assert g.dtype == w.dtype, name
+            np.testing.assert_array_equal(g, w, err_msg=f"{name}: n={n} V={V} {kind}")
+    with pytest.raises(ValueError):
+        U.spread_values(V, "f32")
+
+
+def test_route_sizes():
+    ids, ns = zip(*U.route_sizes(16384, 32768, 1 << 16, 1 << 18))
+    assert ids[:3] == ("pair_tile-1", "pair_tile", "pair_tile+1") and ns[:3] == (16383, 16384, 16385)
+    assert len(set(ids)) == len(set(ns)) == 12 and ns[-3:] == ((1 << 18) - 1, 1 << 18, (1 << 18) + 1)
+
+
 def test_sweep_is_reproducible(ls):
     C = ls.unique_chunk_keys()
     a, b = list(U.sweep_cases(0x7171, C)), list(U.sweep_cases(0x7171, C))

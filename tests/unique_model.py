@@ -116,6 +116,47 @@ def sizes(C):
     return [1, 2, 63, 64, 65, C - 1, C, C + 1, 3 * C + 5, (1 << 18) + 3]
 
 
+def route_sizes(pair_tile, tile, keys_merge_max, pairs_merge_max):
+    """(id, n) at one below, at and one above every size at which an inner sort of the 4-byte keys
+    changes algorithm below the gathered radix's end: the key/value tile, the keys-only tile, the
+    keys' and the pairs' switch from the merge sort to a radix."""
+    edges = (("pair_tile", pair_tile), ("tile", tile), ("2^16", keys_merge_max), ("2^18", pairs_merge_max))
+    return [(f"{name}{d:+d}" if d else name, e + d) for name, e in edges for d in (-1, 0, 1)]
+
+
+SPREAD_A = {32: 0x9E3779B1, 64: 0x9E3779B97F4A7C15}  # odd: v -> v * A mod 2^bits is a bijection
+INT_KINDS = ("u32", "i32", "u64", "i64")
+
+
+def spread_values(V, kind):
+    """The words (v * A) mod 2^bits for v = 0 .. V - 1: distinct, and different in every digit."""
+    if kind not in INT_KINDS:
+        raise ValueError(f"spread: an integer kind expected (float images merge NaNs), got {kind}")
+    bits = 64 if kind in KINDS64 else 32
+    b = np.arange(V, dtype=np.uint64) * np.uint64(SPREAD_A[bits])  # (wraps mod 2^64)
+    return (b & np.uint64((1 << bits) - 1)).astype(word_dtype(kind))
+
+
+def spread(n, V, kind):
+    """x[i] = ((i mod V) * A) mod 2^bits: V distinct values in turn, n elements."""
+    return np.resize(spread_values(V, kind), n)
+
+
+def spread_expected(n, V, kind):
+    """expected(spread(n, V, kind), kind) in closed form: only the min(V, n) values are sorted.  Value
+    v occurs at v, v + V, ...: n // V times and once more if v < n % V, first at v."""
+    assert n >= 1 and V >= 1
+    m = min(V, n)
+    b = spread_values(V, kind)[:m]
+    order = np.argsort(image(b, kind), kind="stable")  # order[j]: the v of the j-th smallest value
+    values = b[order]
+    counts = (n // V + (order < n % V)).astype(np.uint32)
+    first = order.astype(np.uint32)
+    rank = np.empty(m, dtype=np.uint32)
+    rank[order] = np.arange(m, dtype=np.uint32)
+    return values, counts, first, np.resize(rank, n), m
+
+
 def sweep_cases(seed, C, count=40):
     """The seeded sweep: size, key type, mode, output combination and generator drawn per case."""
     rng = np.random.default_rng(seed)

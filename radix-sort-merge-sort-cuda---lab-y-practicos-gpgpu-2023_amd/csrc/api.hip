@@ -233,7 +233,7 @@ int sort_radix8(const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *
     }
     // the look-back clear rides in the plan launch (k_plan8's workgroups 1..)
     HIP_TRY(launch_plan8(hps, joint, n, ki == ko ? 1 : 0, plan, sps, hist, ws + L.off_lookback,
-                         L.zero_bytes - L.off_lookback, s, hyb ? &hc : nullptr));
+                         L.zero_bytes - L.off_lookback, L.ntiles * L.R * 4, s, hyb ? &hc : nullptr));
     for (int p = 0; p < L.P; ++p) {
         // (host gate open: only digits 2 and 3 are timed as passes, so the class's time per launch
         // stays the average of real passes on either path)

@@ -230,8 +230,8 @@ hipError_t launch_hist_seg(const uint32_t *keys, size_t n, uint32_t flip, uint32
 hipError_t launch_hist_lean(const uint32_t *keys, size_t n, uint32_t flip, uint32_t *joint, hipStream_t s,
                             const HyCounts &hy);
 hipError_t launch_plan8(const uint32_t *hps, const uint32_t *joint, size_t n, int in_is_out, Plan *plan,
-                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, hipStream_t s,
-                        const HyCounts *hy = nullptr);
+                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, size_t pass_bytes,
+                        hipStream_t s, const HyCounts *hy = nullptr);
 hipError_t launch_onesweep_p(Bufs b, const Plan *plan, int pass, size_t n, uint32_t flip, const SegPlan *sp,
                              uint32_t *lookback, uint32_t *counter, uint32_t *err, hipStream_t s,
                              const Bufs *vb = nullptr);

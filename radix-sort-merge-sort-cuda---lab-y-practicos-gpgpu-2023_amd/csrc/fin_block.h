@@ -23,6 +23,15 @@ namespace {
 #ifndef LABSORT_FIN_PREFETCH
 #define LABSORT_FIN_PREFETCH 1
 #endif
+// List entries granted per ticket.  One per ticket is 65536 returning adds on one word in the
+// kernel's 0.56 ms, more than the word takes (one per 12.5 ns): the finish of 2^28 uniform keys ran
+// 0.816 ms against 0.562 with two and 0.560 with four (A/B builds, DESIGN.md §3.9,
+// profiles/fin_tickets_ab.txt).  Four also leaves room for lists of the class's shortest buckets.
+#ifndef LABSORT_FIN_GRANT
+#define LABSORT_FIN_GRANT 4
+#endif
+constexpr int FIN_GRANT = LABSORT_FIN_GRANT;
+static_assert(FIN_GRANT >= 1, "a ticket grants at least one entry");
 
 // Inclusive scan over the wave in registers: four row shifts scan each row of 16 lanes, the two
 // row broadcasts of gfx9 carry lane 15 into the next row and lane 31 into the upper half (six
@@ -47,6 +56,7 @@ struct FinSmem {
     alignas(16) uint32_t offs[W * R];  // offs[w * 256 + d]: first slot of wave w's keys of digit d; wave w's own
     uint32_t probe[WAVE];
     uint32_t ordered;
+    uint32_t tick[2];  // the ticket thread 0 drew, by the iteration's parity (k_fin_block)
 };
 
 // A bucket [b, b + len) striped over the W waves as block_stripe (lds_class.h) stripes a unit.  Wave-uniform
@@ -172,7 +182,7 @@ __device__ __forceinline__ void fin_pass(FinSmem<BLOCK, KPT> &sm, const uint32_t
 template <int BLOCK, int KPT, int WPE>
 __global__ __launch_bounds__(BLOCK, WPE) void k_fin_block(uint32_t *out, const uint32_t *__restrict__ off,
                                                            const uint32_t *__restrict__ hdr,
-                                                           const uint32_t *__restrict__ list, HySel hy) {
+                                                           const uint32_t *__restrict__ list, uint32_t *ticket, HySel hy) {
     using S = FinSmem<BLOCK, KPT>;
     constexpr int W = S::W;
     constexpr int CLS = 3;
@@ -184,9 +194,19 @@ __global__ __launch_bounds__(BLOCK, WPE) void k_fin_block(uint32_t *out, const u
     const uint32_t cnt = hdr[SEG_HDR_CNT + CLS];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (blockIdx.x >= cnt) return;  // (an empty class costs its launch only; uniform over the workgroup)
+    // The list is handed out by ticket (hdr[SEG_HDR_TICKET], zero at launch): entry blockIdx.x is
+    // this workgroup's first, every later one comes from a grant of FIN_GRANT consecutive entries
+    // from gridDim.x + FIN_GRANT * ticket on, so a workgroup that runs slow takes fewer buckets and
+    // nobody waits for anybody.  Thread 0 draws; the grant reaches the other waves through sm.tick.
+    // `nxt` is the entry after the one being sorted (>= cnt: none), `left` the entries of its grant
+    // behind it.  The first draw is waited for at the probe's barrier, once per workgroup.
+    const bool any_more = cnt > gridDim.x;  // else the first entries are all there is: no draw
+    if (any_more && tid == 0u) sm.tick[1] = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     probe_lane_order(sm.probe, &sm.ordered, lane, wid);
     __syncthreads();
     const bool atomic_rank = lane_order_probed(&sm.ordered);
+    uint32_t nxt = any_more ? gridDim.x + (uint32_t)FIN_GRANT * __builtin_amdgcn_readfirstlane(sm.tick[1]) : cnt;
+    uint32_t left = (uint32_t)FIN_GRANT - 1u;
     // the list entry and the two offsets are three dependent loads: those of the bucket after
     // the next are issued before this one is sorted
     uint32_t nb, ne;
@@ -198,14 +218,19 @@ __global__ __launch_bounds__(BLOCK, WPE) void k_fin_block(uint32_t *out, const u
     uint32_t k[KPT];
     FinStripe g = fin_stripe<W, KPT>(nb, ne - nb, lane, wid);
     if constexpr (PREFETCH) fin_load(in, g, lane, k);
-    for (uint32_t it = blockIdx.x; it < cnt; it += gridDim.x) {
+    for (uint32_t it = blockIdx.x, par = 0u; it < cnt; par ^= 1u) {
         if constexpr (!PREFETCH) {
             g = fin_stripe<W, KPT>(nb, ne - nb, lane, wid);
             fin_load(in, g, lane, k);
         }
-        const bool more = it + gridDim.x < cnt;
+        const bool more = nxt < cnt;
+        // the entry after the next: the next one of the same grant, or a draw, issued here and not
+        // waited for before the second pass (workgroup-uniform)
+        const bool draw = more && (FIN_GRANT == 1 || left == 0u);
+        uint32_t drawn = 0u;
+        if (draw && tid == 0u) drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (more) {
-            const uint32_t seg = __builtin_amdgcn_readfirstlane(list[it + gridDim.x]);
+            const uint32_t seg = __builtin_amdgcn_readfirstlane(list[nxt]);
             nb = __builtin_amdgcn_readfirstlane(off[seg]);
             ne = __builtin_amdgcn_readfirstlane(off[seg + 1]);
         }
@@ -217,7 +242,18 @@ __global__ __launch_bounds__(BLOCK, WPE) void k_fin_block(uint32_t *out, const u
             for (int j = 0; j < KPT; ++j)
                 if ((uint32_t)j < n2) k[j] = sm.keys[g.ws0 + (uint32_t)j * WAVE + lane];
         }
+        // the drawn ticket: stored before the second pass's barriers, read behind them; two words
+        // by the iteration's parity, so the next store never meets a wave still reading this one
+        if (draw && tid == 0u) sm.tick[par] = drawn;
         fin_pass(sm, k, 8u, g.ng, atomic_rank, lane, wid);
+        it = nxt;
+        if (draw) {
+            nxt = gridDim.x + (uint32_t)FIN_GRANT * __builtin_amdgcn_readfirstlane(sm.tick[par]);
+            left = (uint32_t)FIN_GRANT - 1u;
+        } else {
+            nxt += 1u;  // (no more entries: past cnt, as it is)
+            left -= 1u;
+        }
         // the sorted bucket is in sm.keys and k is free: the next bucket's loads go out first
         FinStripe gn = g;
         uint32_t kn[PREFETCH ? KPT : 1];

@@ -451,15 +451,21 @@ __device__ void build_segplan_later(SegPlan *__restrict__ out, int q, uint32_t p
 // once (r31: one workgroup building them in turn took 18.7 us per sort); workgroup 0 also
 // writes the Plan.  Workgroups 4.. clear the look-back region (zp, zn4 uint4s): one launch
 // instead of a k_zero launch and this one (the look-back words are only read by the
-// passes after it).
+// passes after it).  The region is four passes' of zr4 uint4s each.  After a lean count that left
+// the hybrid verdict (stored before this launch; the plan workgroups take it as it is) only the
+// regions of passes 2 and 3 are cleared: the launches of digits 0 and 1 return at their SKIP
+// before they touch theirs, k_fin_edges reads region 3, the error path none.  A verdict this
+// launch's own rule reaches (the full count) is not known to these workgroups: all four.
 __global__ __launch_bounds__(256) void k_plan8(const uint32_t *__restrict__ hps, const uint32_t *__restrict__ joint,
                                                uint32_t n, int in_is_out, int seg_later, Plan *__restrict__ plan,
                                                SegPlan *__restrict__ sps, uint32_t *__restrict__ hist_out,
-                                               uint4 *__restrict__ zp, size_t zn4, HyCounts hy) {
+                                               uint4 *__restrict__ zp, size_t zn4, size_t zr4, HyCounts hy) {
     constexpr uint32_t PW = 4;  // plan workgroups, one per pass
     if (blockIdx.x >= PW) {
         const size_t stride = (size_t)(gridDim.x - PW) * blockDim.x;
-        for (size_t i = (size_t)(blockIdx.x - PW) * blockDim.x + threadIdx.x; i < zn4; i += stride)
+        const bool lean_hybrid = hy.ctl && hy.ctl[HY_CTL_VERDICT] == HY_VERDICT_HYBRID;
+        const size_t first = lean_hybrid ? min(2 * zr4, zn4) : (size_t)0;
+        for (size_t i = first + (size_t)(blockIdx.x - PW) * blockDim.x + threadIdx.x; i < zn4; i += stride)
             zp[i] = make_uint4(0u, 0u, 0u, 0u);
         return;
     }
@@ -1802,10 +1808,10 @@ hipError_t launch_hist_seg(const uint32_t *keys, size_t n, uint32_t flip, uint32
 }
 
 hipError_t launch_plan8(const uint32_t *hps, const uint32_t *joint, size_t n, int in_is_out, Plan *plan,
-                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, hipStream_t s,
-                        const HyCounts *hy) {
+                        SegPlan *segplans, uint32_t *hist, void *zero_p, size_t zero_bytes, size_t pass_bytes,
+                        hipStream_t s, const HyCounts *hy) {
     // the look-back clear rides in the plan launch (workgroups 1..): one launch fewer (r27)
-    const bool fold = zero_bytes % 16 == 0;
+    const bool fold = zero_bytes % 16 == 0 && pass_bytes % 16 == 0 && zero_bytes == 4 * pass_bytes;
     if (!fold && zero_bytes) {
         const hipError_t z = launch_zero(zero_p, zero_bytes, s);
         if (z != hipSuccess) return z;
@@ -1813,7 +1819,7 @@ hipError_t launch_plan8(const uint32_t *hps, const uint32_t *joint, size_t n, in
     const size_t zn4 = fold ? zero_bytes / 16 : 0;
     const unsigned g = 4u + (zn4 ? blocks_for(zn4, 256 * 4, 2048) : 0u);
     k_plan8<<<g, 256, 0, s>>>(hps, joint, (uint32_t)n, in_is_out, 1, plan, segplans, hist,
-                              static_cast<uint4 *>(zero_p), zn4, hy ? *hy : HyCounts{});
+                              static_cast<uint4 *>(zero_p), zn4, pass_bytes / 16, hy ? *hy : HyCounts{});
     return hipGetLastError();
 }
 

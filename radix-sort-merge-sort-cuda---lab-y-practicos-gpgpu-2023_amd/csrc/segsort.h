@@ -88,8 +88,10 @@ hipError_t seg_class_dispatch(int c, Fn &&fn) {
 //   word 0: offsets rejected by k_seg_bin (labsort_segments_workspace_status: ERR_ARG)
 //   word 1: an inner pair sort of the general path reported an error (ERR_DEVICE)
 //   words 4..8: entries in the class lists
+//   word 9: the hybrid radix finish's ticket, the next grant of its block class's list (fin_block.h)
 constexpr int SEG_HDR_BYTES = 256;
-constexpr int SEG_HDR_DEVERR = 1, SEG_HDR_CNT = 4;
+constexpr int SEG_HDR_DEVERR = 1, SEG_HDR_CNT = 4, SEG_HDR_TICKET = SEG_HDR_CNT + SEG_CLASSES;
+static_assert((SEG_HDR_TICKET + 1) * 4 <= SEG_HDR_BYTES, "the ticket lies inside the cleared header");
 
 // Validate the offsets (ends, monotonicity, every length <= max_len when max_len != 0) and,
 // with lists != nullptr, append each segment to the list of its class (lists + c * stride).
@@ -113,7 +115,9 @@ struct HySel {
 };
 // finish classes: the three wave classes, a 256 x 20 block class that holds the 4096 +- 300-key
 // buckets of 2^28 uniform keys (a 4096-key edge would send half of them to the tile class:
-// 2.07 ms against 0.69, profiles/hybrid_finish_shapes.txt), the tile class
+// 2.07 ms against 0.69, profiles/hybrid_finish_shapes.txt), the tile class.  (Binning every bucket
+// up to 5120 keys into the block class and dropping the three wave launches saves their ~14 us on
+// uniform keys, but 49152 buckets of ~4 keys beside 16384 of ~16K took 2.60 ms against 2.32: kept.)
 constexpr int HY_BLOCK = 256, HY_BLOCK_KPT = 20, HY_BLOCK_WPE = 5, HY_BLOCK_KEYS = HY_BLOCK * HY_BLOCK_KPT;  // 5120
 static_assert((uint32_t)SEG_TILE_KEYS == HY_MAX_BUCKET, "the plan's bound is the tile class's capacity");
 static_assert(SEG_WAVE3_KEYS < HY_BLOCK_KEYS && HY_BLOCK_KEYS < SEG_TILE_KEYS, "class edges ascend");

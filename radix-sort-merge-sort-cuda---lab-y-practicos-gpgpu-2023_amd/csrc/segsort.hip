@@ -304,8 +304,9 @@ hipError_t launch_hybrid_finish(const Plan *plan, Bufs b, size_t n, uint32_t fli
     const unsigned cus = (unsigned)cu_count();
     for (int c = 0; c < SEG_CLASSES; ++c) {
         const uint32_t *list = lists + (size_t)c * stride;
-        if (c == 3) {  // the finish's own block class
-            k_fin_block<HY_BLOCK, HY_BLOCK_KPT, HY_BLOCK_WPE><<<cus * (unsigned)HY_BLOCK_WPE, HY_BLOCK, 0, s>>>(out, off, hdr, list, hy);
+        if (c == 3) {  // the finish's own block class, its list handed out by the header's ticket
+            k_fin_block<HY_BLOCK, HY_BLOCK_KPT, HY_BLOCK_WPE><<<cus * (unsigned)HY_BLOCK_WPE, HY_BLOCK, 0, s>>>(
+                out, off, hdr, list, hdr + SEG_HDR_TICKET, hy);
             e = hipGetLastError();
         } else {
             e = launch_seg_sort(c, out, out, nullptr, nullptr, off, hdr, list, flip, s, hy);
